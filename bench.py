@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: ELBO-steps/sec of the 3-layer doubly-stochastic DGP (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = minibatch gather + forward ELBO (dgp.py:92-98) + reverse-mode gradient w.r.t. every trainable parameter +
 Adam(0.01) update — i.e. one `session.run(opt_op)` of demos/demo_regression_UCI.ipynb:324 — on kin8nm-SHAPED synthetic
@@ -13,14 +13,20 @@ minibatch stays 1000 rows x S=20, every rank takes 1000/N rows x all S samples (
 flat gradient is summed with one all-reduce per step and every rank applies the same Adam update; value = global steps/s
 (NO x N).  `--scaling weak` keeps 1000 rows per GPU (global batch 1000 N) and reports N x steps/s.
 
-Timing protocol: the secondary measurements (forward-only evals/s, predict_f rows/s, per-kernel HIP-event times, the
-sub-rooflines, the other configs) run FIRST and bring the GPU to its steady clocks; then W untimed warm-up steps, then EXACTLY K
-steps between barrier + synchronize -> `value`.  After the timed region: the CPU baseline (rank 0, N = 1), a fixed loop of 1200
-single steps bracketed by HIP events (median / p10 / p90 -> `step_time`), and at N = 1 the flat data-parallel step on the 500 / 250 /
-125-row shards of a 2 / 4 / 8-GPU strong-scaling run over a one-rank RCCL group (`shard_steps`: the strong-scaling ceiling).
+Timing protocol (plain run): set-up, SETTLE_STEPS + W untimed warm-up steps, then EXACTLY K steps between barrier +
+synchronize -> `value` and `ms_per_step`; `final_elbo` is the ELBO of the last timed step.  `--dump-outputs DIR` then writes what
+that last timed step computed (dump_outputs); with the same arguments the inputs (data, inducing points, minibatch order, N(0,1)
+draws) are the same in every run.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (HIP-event timed dominant kernel) and
-`cpu_baseline` (the CPU oracle — a port of the GPflow/TF op sequence, NOT TF itself — timed on this box's host cores).
+`--full` adds the secondary measurements: forward-only evals/s, predict_f rows/s, per-kernel HIP-event times, the sub-rooflines and
+the other configs run BEFORE the warm-up and bring the GPU to its steady clocks; after the timed region come the kernel launches per
+step, the CPU baseline (rank 0, N = 1), a fixed loop of 1200 single steps bracketed by HIP events (median / p10 / p90 -> `step_time`)
+and at N = 1 the flat data-parallel step on the 500 / 250 / 125-row shards of a 2 / 4 / 8-GPU strong-scaling run over a one-rank RCCL
+group (`shard_steps`: the strong-scaling ceiling).  `--no-extras` / `--no-cpu-baseline` drop parts of that again.
+
+Rank 0 prints ONE JSON line with `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`; under `--full` also
+`roofline` (HIP-event timed dominant kernel) and `cpu_baseline` (the CPU oracle — a port of the GPflow/TF op sequence, NOT TF
+itself — timed on the host cores); the fields of measurements that did not run are null.
 """
 import argparse
 import json
@@ -37,6 +43,7 @@ for p in (ROOT, os.path.join(ROOT, "doubly-stochastic-dgp_amd")):
 
 FP64_MFMA_PEAK_TFLOPS = 78.6     # MI355X datasheet FP64 matrix (= FP64 vector) peak; microbench in profiles/
 CFG = dict(n_data=7372, D=8, M=128, S=20, mb=1000, L=3)
+SETTLE_STEPS = 2000              # untimed steps in front of the W warm-up ones when the secondary measurements do not run (~1 s)
 
 
 def layer_shapes(cfg):
@@ -401,6 +408,16 @@ def csrc_hash():
     return h.hexdigest()[:16]
 
 
+def dump_outputs(eng, d):
+    """What the last step computed, as its caller receives it: `elbo_terms` = [ELBO, data term, KL term, Cholesky info] (summed over
+    the ranks at N > 1), `grad` = d(-ELBO)/d(every unconstrained parameter), `theta` = the unconstrained parameters after that step's
+    Adam update.  float64, ~4.5 MB in all at configs[1]."""
+    os.makedirs(d, exist_ok=True)
+    eng.ctx.sync()
+    for name, t in (("elbo_terms", eng.out4), ("grad", eng.grad), ("theta", eng.theta)):
+        np.save(os.path.join(d, f"{name}.npy"), t.detach().cpu().numpy().astype(np.float64))
+
+
 def self_launch(n):
     """Re-run this command line as `n` ranks of one node: python -m torch.distributed.run --nnodes=1 --nproc-per-node n
     --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>.  Returns the launcher's exit status."""
@@ -422,13 +439,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (evals/s, predict_f rows/s, per-kernel roofline, sub-rooflines, the other "
+                         "configs, launches per step, CPU baseline, step-time distribution, shard steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N>1: strong = global minibatch fixed at 1000 (BASELINE's metric), weak = 1000 rows per GPU")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (profiler runs)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (profiler runs)")
     ap.add_argument("--allreduce", choices=["auto", "flat", "bucketed"], default="auto",
                     help="N > 1: one flat gradient all-reduce per step, or one per layer from inside the reverse pass; auto = by gradient size")
     args = ap.parse_args()
+    extras = args.full and not args.no_extras
 
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -477,16 +499,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    for _ in range(3):
-        model.train_step(0.01)
-    torch.cuda.synchronize()
+    if args.full:
+        for _ in range(3):
+            model.train_step(0.01)
+        torch.cuda.synchronize()
 
     evals_per_s = predict_rows_per_s = predict_fwd = None
     prof = {}
     sub = {}
     others = None
     steady = None
-    if not args.no_extras:
+    if extras:
         # secondary metrics: forward-only ELBO evals/s and predict_f rows/s (per rank)
         n_ev = 50
         Xb, Yb = model.next_minibatch()
@@ -535,6 +558,12 @@ def main():
             sub = sub_rooflines(ctx)
             if world == 1:
                 others = all_configs()
+    if not extras:
+        # without the secondary measurements in front, the first milliseconds of stepping from idle run ~7 % slow (20 timed steps
+        # after 5 warm-up ones); a fixed count of untimed steps, not a time budget, so that every run with the same arguments computes
+        # the same numbers
+        for _ in range(SETTLE_STEPS):
+            model.train_step(0.01)
     # ---- the contract's timed region: W warm-up steps, then EXACTLY K steps
     for _ in range(args.warmup):
         model.train_step(0.01)
@@ -549,18 +578,22 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    elbo = model.train_step(0.01, sync=True)
-    from doubly_stochastic_dgp import _lib
-    lib = _lib.load()
-    l0 = lib.dsdgp_launch_count()
-    for _ in range(10):
-        model.train_step(0.01)
-    torch.cuda.synchronize()
-    launches_per_step = (lib.dsdgp_launch_count() - l0) / 10.0
+    elbo = model._sync_result(eng, None, world)       # the last timed step's ELBO (all-reduced with the gradient at N > 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
+    launches_per_step = None
+    if args.full:
+        from doubly_stochastic_dgp import _lib
+        lib = _lib.load()
+        l0 = lib.dsdgp_launch_count()
+        for _ in range(10):
+            model.train_step(0.01)
+        torch.cuda.synchronize()
+        launches_per_step = (lib.dsdgp_launch_count() - l0) / 10.0
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(cfg, X, Y, Z)
-    if not args.no_extras:
+    if extras:
         # steady-state distribution: single steps bracketed by events on the launch stream (ctx stream == torch's current stream),
         # a fixed sample of four batches of 300
         nb_ev, n_batches = 300, 4
@@ -585,7 +618,7 @@ def main():
                       note="per-step HIP events on the launch stream, run after the timed region (and after the CPU baseline at N = 1); "
                            "the gradient all-reduce (N>1) is inside each step")
     shards = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if rank == 0 and world == 1 and extras:
         shards = shard_steps(cfg)
     rccl_ranks = 1
     if world > 1:

@@ -2,12 +2,22 @@
 (gpflow 1.1.1 / TF 1.8 unavailable), so these vectors pin the ORACLE + the HIP path against each other and against
 regressions; the oracle in turn is pinned relationally by tests/test_oracle_identities.py.
 
-    python -m tests.golden.make_golden
+    python -m tests.golden.make_golden [case ...]
+
+Run as a script it pins the BLAS code paths (REPRODUCIBLE_BLAS) before numpy / torch load them: MKL's default kernels differ between
+CPU vendors (AVX-512 on Intel, AVX2 on AMD) and OpenBLAS picks its kernels by CPU model, and either changes the last bits of the
+oracle's numbers.  tests/test_golden_generator.py regenerates fixtures the same way and compares them to 1e-12.
 """
 import os
 import sys
 
-import numpy as np
+# MKL's vendor-independent code path and OpenBLAS's AVX-512 kernels (what it picks itself on AVX-512 hosts): the same bits on Intel
+# AVX-512 hosts at any thread count; MKL on AMD hosts still differs in the last bits (5e-13 of the largest entry, multiclass case)
+REPRODUCIBLE_BLAS = {"MKL_CBWR": "COMPATIBLE", "OPENBLAS_CORETYPE": "SkylakeX"}
+if __name__ == "__main__":
+    os.environ.update(REPRODUCIBLE_BLAS)
+
+import numpy as np  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
@@ -40,8 +50,8 @@ def outputs(name):
     return out
 
 
-def main():
-    for name in cases.CASES:
+def main(names=None):
+    for name in names or cases.CASES:
         out = outputs(name)
         path = os.path.join(HERE, f"golden_{name}.npz")
         np.savez_compressed(path, **out)
@@ -49,4 +59,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

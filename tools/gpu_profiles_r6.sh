@@ -32,7 +32,7 @@ for c in 1 2 3 4 5; do
 done
 python $R/tools/executed_flops.py parse $P/r06_executed_flops.json $H $EX >> $P/summary.log 2>&1
 cp $P/r06_executed_flops.json $R/profiles/r06_executed_flops.json
-(cd $R && timeout 900 python bench.py > $P/r06_bench.json 2> $O/bench.err; tail -c 400 $P/r06_bench.json >> $P/summary.log)
+(cd $R && timeout 900 python bench.py --full > $P/r06_bench.json 2> $O/bench.err; tail -c 400 $P/r06_bench.json >> $P/summary.log)
 DSDGP_NO_OVERLAP=1 timeout 600 rocprofv3 --kernel-trace --stats -d $O/serial -o t -- python $R/bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras > $O/serial.json 2> $O/serial.err
 DB=$(find $O/serial -name "*.db" | head -1)
 python $R/tools/rocprof_summary.py $DB $P/r06_kernel_stats_serial.md "round 6: bench.py --steps 40 --warmup 5 --no-extras under rocprofv3 --kernel-trace --stats, DSDGP_NO_OVERLAP=1 (overlap-free: every duration is the kernel's own)" > /dev/null

@@ -29,7 +29,7 @@ def main(fdb, wdb, prefix, title):
                      traffic_MB_max_launch=(2 * max(fv) + max(wv)) * 1024 / 1e6)
     with open(prefix + ".md", "w") as fh:
         fh.write(f"# {title}\n\nseparate `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes (`--kernel-trace` only) of "
-                 "`python bench.py --steps 4 --warmup 2 --no-cpu-baseline` (cfg 2; launch mix: 3 layers, training + the secondary "
+                 "`python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline` (cfg 2; launch mix: 3 layers, training + the secondary "
                  "eval/predict loops of bench.py); values in KB per launch; traffic = 2*FETCH + WRITE (gfx950 correction).\n\n"
                  "| kernel | launches | FETCH avg | FETCH max | WRITE avg | WRITE max | traffic/launch (MB, avg) |\n|---|---|---|---|---|---|---|\n")
         fh.write("\n".join(rows) + "\n")

@@ -1,5 +1,5 @@
 import ctypes as C, os, sys, time
-ROOT = "/root/repo"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "doubly-stochastic-dgp_amd"))
 import torch
 from doubly_stochastic_dgp import _lib
