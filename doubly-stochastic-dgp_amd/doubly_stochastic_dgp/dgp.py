@@ -100,6 +100,13 @@ class DGP_Base(Parameterized):
         self._seed += 1
         return self._seed
 
+    def _draw_seed(self):
+        """Philox seed of the next device evaluation: distinct across calls and across the ranks of a data-parallel run (every call
+        draws the streams 0 .. L-1 under it).  One formula at every call site: a prediction seed of plain _next_seed() equalled an
+        earlier training seed t * world + rank of its own rank or of another one once world > 1.  (world = 1: 1, 2, 3, ...)"""
+        rank, world = self._dist[:2] if self._dist else (0, 1)
+        return self._next_seed() * world + rank
+
     def _next_index_span(self):
         """(device index tensor, offset, n) of the next minibatch.  The row indices of the next CHUNK minibatches are drawn on the
         host in one go and uploaded once (pinned, asynchronous); a step then only moves an offset.  One upload per epoch (or per step
@@ -156,7 +163,7 @@ class DGP_Base(Parameterized):
                 F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=True)
                 Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
             return Fs, Fmeans, Fvars
-        Fs, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._next_seed())
+        Fs, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._draw_seed())
         eng.ctx.sync()
         Fs, Fmeans, Fvars = self._np(Fs), self._np(Fmeans), self._np(Fvars)
         if any(layer.input_prop_dim for layer in self.layers):
@@ -177,7 +184,7 @@ class DGP_Base(Parameterized):
             _, Fmeans, Fvars = self.propagate(X, full_cov=True, S=S, zs=zs)
             return Fmeans[-1], Fvars[-1]
         eng = self.engine()
-        _, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._next_seed(), want=("mean", "var"))
+        _, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._draw_seed(), want=("mean", "var"))
         eng.ctx.sync()
         return Fmeans[-1].cpu().numpy(), Fvars[-1].cpu().numpy()
 
@@ -201,7 +208,7 @@ class DGP_Base(Parameterized):
             eng._ensure(n_local, self.num_samples)
             eng._upload_if_needed()            # may re-create the device model (layout / jitter change): before the hook looks at it
             hook(eng)
-        out = eng.elbo(X, Y, self.num_samples, zs=zs, seed=self._next_seed() * world + rank, data_scale=scale,
+        out = eng.elbo(X, Y, self.num_samples, zs=zs, seed=self._draw_seed(), data_scale=scale,
                        kl_weight=klw, with_grad=with_grad, sync=allreduce is None, grad_from_layer=grad_from_layer,
                        grad_q_only=grad_q_only)
         if allreduce is not None:
@@ -224,7 +231,7 @@ class DGP_Base(Parameterized):
             Xd, Yd = self._device_data()
             idx, off, n = self._next_index_span()
             scale, klw = shard_terms(self.num_data, n, 1)
-            eng.train_step_minibatch(Xd, Yd, idx, off, n, self.num_samples, seed=self._next_seed(), data_scale=scale, kl_weight=klw,
+            eng.train_step_minibatch(Xd, Yd, idx, off, n, self.num_samples, seed=self._draw_seed(), data_scale=scale, kl_weight=klw,
                                      lr=lr, beta1=beta1, beta2=beta2, eps=eps)
             return self._sync_result(eng, None, world) if sync else None
         if X is None:
@@ -235,7 +242,7 @@ class DGP_Base(Parameterized):
         scale, klw = shard_terms(self.num_data, n_local, world)
         if allreduce is None:
             # single process: ELBO, gradient and Adam update in one library call (the update rides in the reverse pass's last launch)
-            eng.train_step(X, Y, self.num_samples, zs=zs, seed=self._next_seed(), data_scale=scale, kl_weight=klw, lr=lr, beta1=beta1,
+            eng.train_step(X, Y, self.num_samples, zs=zs, seed=self._draw_seed(), data_scale=scale, kl_weight=klw, lr=lr, beta1=beta1,
                            beta2=beta2, eps=eps)
             out = None
         else:
@@ -244,7 +251,7 @@ class DGP_Base(Parameterized):
                 eng._ensure(n_local, self.num_samples)
                 eng._upload_if_needed()
                 hook(eng)
-            out = eng.elbo(X, Y, self.num_samples, zs=zs, seed=self._next_seed() * world + rank, data_scale=scale,
+            out = eng.elbo(X, Y, self.num_samples, zs=zs, seed=self._draw_seed(), data_scale=scale,
                            kl_weight=klw, with_grad=True, sync=False)
             out = allreduce(eng, True, sync=sync)
             eng.adam_step(lr, beta1, beta2, eps)
