@@ -114,7 +114,8 @@ struct WgradJob {
   int32_t sym;          // P == Q (symmetric result): only tiles with tile_j <= tile_i are computed
   int32_t qrows16;      // rows of Q / 16 (= columns of the result / 16)
   int32_t ns_diag;      // sym: K splits of the (cheaper, 10/16) diagonal tiles; their tasks follow the off-diagonal ones
-  int32_t pad;
+  int32_t ng;           // 0: one result per task.  1..4: a GROUP of ng symmetric, scaled results that share P = Q (the P_d of a layer)
+                        // on 32 x 32 tiles, result o at out + o * ostride, scaled by scale + o * sstride (see k_wgrad_coop)
   // In-launch split-K reduction (round 6): with `fin` set the LAST of a tile's splits to arrive (ticket counter `tick[tile]`, zero between
   // launches) adds the tile's partials in split order and writes rows < fin_rows, columns < fin_cols of the result (leading dimension
   // fin_ld) — and, for sym, the mirror tile / the uncomputed upper blocks of a diagonal tile — so that no reduction launch follows the
@@ -122,9 +123,11 @@ struct WgradJob {
   double* fin;
   int32_t* tick;
   int32_t fin_ld, fin_rows, fin_cols, pad2;
+  int64_t ostride, sstride;      // ng > 0: distance between the group's results / between their scale vectors (doubles)
 };
 
-// jobs_dev: device copy of `njobs` jobs with task_start filled (64 x 64 tiles, one workgroup per (job, split, tile) task)
+// jobs_dev: device copy of `njobs` jobs with task_start filled (64 x 64 tiles, one workgroup per (job, split, tile) task; grouped
+// jobs: one workgroup per (split, 32 x 32 tile) task of the group's outputs)
 int wgrad_launch(dsdgp_ctx* ctx, const WgradJob* jobs_dev, int njobs, int total_tasks, int nsplit, int64_t ld, int64_t Rp,
                  hipStream_t stream = nullptr);
 // chain kernels (layer_sm.hip): the NW waves of a workgroup cooperate on one block of 16 rows

@@ -353,14 +353,36 @@ static int ensure_plan(dsdgp_model* m, int64_t n, int S) {
       tick_off += J.sym ? J.ti * (J.ti + 1) / 2 : J.ti * J.tj;
     };
     // ---- A jobs: operands from the forward chain (A, [X^T;1]) and from the producer of this layer's upstream adjoints (VB, MB)
-    for (int j = 1; j <= v.D_out; ++j) {
+    // The D_out P_d share their operand A: grouped jobs (WgradJob::ng: up to four P_d per 32 x 32 tile task) load each A fragment once
+    // for the whole group.  Same K splits (ns above fixes every element's order of summation: it must not depend on the grouping), same
+    // partials.  Half the L2 requests but more L2 misses: at config 2 the launch is faster beside the next layer's backward chain and
+    // slower alone; config 3 (Mw = 256) was slower.  So by default only on the two-stream schedule at Mw = 128 with
+    // D_out >= 3 (groups of 3 or 4: a group of two moves as many bytes per MFMA as a 64 x 64 tile), and only for partials (wfuse jobs
+    // keep the 64 x 64 tiles their in-launch reduction stages).  wg_group = 0: never; 2: every shape and schedule (parity tests).
+    const bool wgroup = !wfuse && (m->force.wg_group >= 2 || (m->force.wg_group == 1 && v.D_out >= 3 && ti <= 2 && overlap_on(m, n, S)));
+    const int ngroups = wgroup ? ceil_div(v.D_out, 4) : 0;
+    for (int k = 0, j = 1; k < ngroups; ++k) {
+      const int ng = v.D_out / ngroups + (k < v.D_out % ngroups ? 1 : 0);
+      WgradJob J{};
+      J.P = St.A; J.Q = St.A;
+      J.scale = St.VB + (int64_t)(j - 1) * ld; J.sstride = ld;
+      J.out = St.part_big + (int64_t)j * ns * MMw; J.ostride = (int64_t)ns * MMw;
+      J.ti = ti; J.tj = ti; J.ldo = Mw; J.task_start = startA;
+      J.sym = 1; J.qrows16 = Mw / 16;
+      J.ns_diag = ns_diag; J.ng = ng;
+      startA += 4 * ns * n_off + 3 * ns_diag * ti;      // per split: 4 32-tiles of an off-diagonal 64-tile, 3 of a diagonal one
+      jobsA.push_back(J);
+      for (int o = 0; o < ng; ++o, ++j)
+        redA.push_back(RedJob{J.out + o * J.ostride, v.bigred + (int64_t)j * MM, MM, ns, 0, 0, v.Mp, 16, MMw, Mw, v.Mp});
+    }
+    for (int j = 1; j <= (wgroup ? 0 : v.D_out); ++j) {
       WgradJob J{};
       J.P = St.A; J.Q = St.A;
       J.scale = St.VB + (int64_t)(j - 1) * ld;
       J.out = St.part_big + (int64_t)j * ns * MMw;
       J.ti = ti; J.tj = ti; J.ldo = Mw; J.task_start = startA;
       J.sym = 1; J.qrows16 = Mw / 16;                     // P_d = sum_r vbar_d a a^T is symmetric
-      J.ns_diag = ns_diag; J.pad = 0;
+      J.ns_diag = ns_diag; J.ng = 0;
       startA += ns * n_off + ns_diag * ti;
       fuse(J, v.bigred + (int64_t)j * MM, v.Mp, v.Mp, v.Mp);
       jobsA.push_back(J);
@@ -388,7 +410,7 @@ static int ensure_plan(dsdgp_model* m, int64_t n, int S) {
       J.P = St.E; J.Q = St.A; J.scale = nullptr;
       J.out = St.part_big;
       J.ti = ti; J.tj = ti; J.ldo = Mw; J.task_start = startB;
-      J.sym = 0; J.qrows16 = Mw / 16; J.ns_diag = ns_diag; J.pad = 0;
+      J.sym = 0; J.qrows16 = Mw / 16; J.ns_diag = ns_diag; J.ng = 0;
       startB += ns * ti * ti;
       fuse(J, v.bigred, v.Mp, v.Mp, v.Mp);
       jobsB.push_back(J);

@@ -165,10 +165,10 @@ struct dsdgp_model {
   // backward chain 0 off / 1 from Mp = 512 / 2 everywhere; pipe_tail: per-layer reduction + P_d T_d products behind each layer's
   // weight-gradient products 0 / 1; head / tail / adj_fuse / lik_fuse = 0: the unfused launches (parity tests of the fusions);
   // ext_ev = 0: plain event record behind the head launch; red_ahead = 0: one split-K reduction after the stream join;
-  // white_fwd = 0: forward-only evaluations in plain coordinates.  last_fuse = 0: the last layer of a training step as its two chains
+  // white_fwd = 0: forward-only evaluations in plain coordinates; wg_group: grouped P_d weight-gradient tasks 0 never / 1 default / 2 every D_out.  last_fuse = 0: the last layer of a training step as its two chains
   // instead of the fused launch (layer_last.hip); last_min_blocks: fewest row blocks for which the fused launch is taken.  gemm_mp: smallest padded inducing count whose layers take the
   // GEMM-formulated passes (layer_gemm.hip) instead of the fused chains, 0 = never (parity tests force it onto small shapes).
-  struct Force { int save_c = 1, cs_min_blocks = 160, cs_min_dout = 3, cs_max_dout = 1 << 20, wg_defer = -1, alg_g = -1, bwd_split = 1, pipe_tail = 0, head = 1, tail = 1, adj_fuse = 1, ext_ev = 1, lik_fuse = 1, red_ahead = 1, white_fwd = 1, gemm_mp = 512, last_fuse = 1, last_min_blocks = 1, asm_pre = 1, overlap_min = 1 << 18, wg_red = 1; } force;
+  struct Force { int save_c = 1, cs_min_blocks = 160, cs_min_dout = 3, cs_max_dout = 1 << 20, wg_defer = -1, alg_g = -1, bwd_split = 1, pipe_tail = 0, head = 1, tail = 1, adj_fuse = 1, ext_ev = 1, lik_fuse = 1, red_ahead = 1, white_fwd = 1, gemm_mp = 512, last_fuse = 1, last_min_blocks = 1, asm_pre = 1, overlap_min = 1 << 18, wg_red = 1, wg_group = 1; } force;
 };
 static void parse_force(dsdgp_model* m) {
   const char* e = getenv("DSDGP_FORCE");
@@ -204,6 +204,7 @@ static void parse_force(dsdgp_model* m) {
       else if (k == "asm_pre") m->force.asm_pre = v;
       else if (k == "overlap_min") m->force.overlap_min = v;
       else if (k == "wg_red") m->force.wg_red = v;
+      else if (k == "wg_group") m->force.wg_group = v;
     }
     pos = end + 1;
   }

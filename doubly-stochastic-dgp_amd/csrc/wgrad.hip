@@ -96,6 +96,157 @@ __device__ __forceinline__ void wgrad_loop_rolling(gcptr Pp, gcptr Qp, gcptr sca
   }
 }
 
+// The rolling K loop of a GROUPED task: NG symmetric results P_o = A diag(s_o) A^T of one layer share their operand A, so the wave
+// loads the 32 x 32 tile's P and Q fragments once per half chunk and feeds them to the MFMAs of all NG results; result o's MFMAs take
+// a copy of Q scaled by s_o (Q scaled, P not — as in wgrad_loop_rolling).  Per 64 MFMAs at NG = 4: 4 fragments + 4 scale lines
+// (~8.5 KB) where a 64 x 64 single-result task moves 8 fragments + 1 scale line (~16.1 KB); 32 v_mul_f64 instead of 16.  Every
+// element sees the operands, the k order (t = 0..3 chunk by chunk) and the accumulator of the single-result loop: the same bits.
+// DIAG: 32 x 32 diagonal tile — blocks on or below the block diagonal only (3 of 4), Q = P.
+template <int NG, bool DIAG>
+__device__ __forceinline__ void wgrad_loop_grouped(gcptr Pp, gcptr Qp, gcptr sp, int64_t sstride, int64_t ld, int64_t c_lo, int64_t c_hi,
+                                                   d4 (&acc)[NG][2][2]) {
+  if (c_lo >= c_hi) return;
+  typedef const wd2 __attribute__((address_space(1)))* h2ptr;
+  wd2 p[2][2], q[2][2], sc[2][NG];
+  auto request = [&](int64_t ch, int h) {
+    const int64_t rb = ch * 16 + 2 * h;
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii) p[h][ii] = *reinterpret_cast<h2ptr>(Pp + (int64_t)16 * ii * ld + rb);
+    if constexpr (!DIAG) {
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) q[h][jj] = *reinterpret_cast<h2ptr>(Qp + (int64_t)16 * jj * ld + rb);
+    }
+#pragma unroll
+    for (int o = 0; o < NG; ++o) sc[h][o] = *reinterpret_cast<h2ptr>(sp + o * sstride + rb);
+  };
+  // (fenced like the loop's requests: the wait counts the loop needs, older half first, hold only if the prologue issues the halves
+  // in that order — merged, its scale loads came out interleaved and every phase waited for all loads in flight)
+  request(c_lo, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  request(c_lo, 1);
+  __builtin_amdgcn_sched_barrier(0);
+  for (int64_t ch = c_lo; ch < c_hi; ++ch) {
+    const int64_t nx = ch + 1 < c_hi ? ch + 1 : ch;        // (the last chunk re-requests itself: unused)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int o = 0; o < NG; ++o) {
+        wd2 qs[2];
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) qs[jj] = (DIAG ? p[h][jj] : q[h][jj]) * sc[h][o];
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < 2; ++jj)
+              if (!DIAG || jj <= ii) acc[o][ii][jj] = mfma_f64(p[h][ii][t], qs[jj][t], acc[o][ii][jj]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      request(nx, h);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// One (split, 32 x 32 tile) task of a grouped job (WgradJob::ng = NG > 0): the K range, the four waves' quarters of it, the fixed-order
+// LDS tree and the partial layout are those of the 64 x 64 single-result task that covers the tile, so every element of every P_o is
+// summed exactly as there.  Tasks per split: the four 32-tiles of each off-diagonal 64-tile (nsplit K splits), then the three lower
+// 32-tiles (diagonal, off-diagonal, diagonal) of each diagonal 64-tile (ns_diag K splits, as its 64-tile).
+template <int NG>
+__device__ __forceinline__ void wgrad_grouped_task(const WgradJob& J, int local, int nsplit, int64_t ld, int64_t Rp, double* red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c = lane & 15;
+  const int n_off = J.ti * (J.ti - 1) / 2;
+  int split, t32i, t32j, ns_eff = nsplit;
+  if (local < nsplit * n_off * 4) {
+    split = local / (n_off * 4);
+    local = local % (n_off * 4);
+    const int sub = local & 3;
+    local >>= 2;
+    int tile_i = 1;
+    while (tile_i * (tile_i + 1) / 2 <= local) ++tile_i;
+    const int tile_j = local - tile_i * (tile_i - 1) / 2;
+    t32i = 2 * tile_i + (sub >> 1);
+    t32j = 2 * tile_j + (sub & 1);
+  } else {
+    local -= nsplit * n_off * 4;
+    split = local / (3 * J.ti);
+    local = local % (3 * J.ti);
+    const int sub = local % 3;
+    t32i = 2 * (local / 3) + (sub > 0);
+    t32j = 2 * (local / 3) + (sub > 1);
+    ns_eff = J.ns_diag;
+  }
+  const int64_t nch = Rp / 16;
+  const int64_t s_lo = split * nch / ns_eff, s_hi = (split + 1) * nch / ns_eff;
+  const int64_t c_lo = s_lo + (s_hi - s_lo) * wave / 4, c_hi = s_lo + (s_hi - s_lo) * (wave + 1) / 4;
+  d4 acc[NG][2][2];
+#pragma unroll
+  for (int o = 0; o < NG; ++o)
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj) acc[o][ii][jj] = (d4){0, 0, 0, 0};
+  gcptr Pp = (gcptr)(J.P + (int64_t)(32 * t32i + c) * ld + 4 * g);
+  gcptr Qp = (gcptr)(J.Q + (int64_t)(32 * t32j + c) * ld + 4 * g);
+  gcptr sp = (gcptr)(J.scale + 4 * g);
+  const bool diag = t32i == t32j;
+  if (diag)
+    wgrad_loop_grouped<NG, true>(Pp, Qp, sp, J.sstride, ld, c_lo, c_hi, acc);
+  else
+    wgrad_loop_grouped<NG, false>(Pp, Qp, sp, J.sstride, ld, c_lo, c_hi, acc);
+  // the fixed-order tree of k_wgrad_coop: ((w0 + w2) + (w1 + w3))
+  constexpr int NS = NG * 16;
+  if (wave >= 2) {
+    double* r = red + (wave - 2) * NS * 64 + lane;
+#pragma unroll
+    for (int o = 0; o < NG; ++o)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) r[((o * 4 + b) * 4 + t) * 64] = acc[o][b >> 1][b & 1][t];
+  }
+  __syncthreads();
+  if (wave < 2) {
+    const double* r = red + wave * NS * 64 + lane;
+#pragma unroll
+    for (int o = 0; o < NG; ++o)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[o][b >> 1][b & 1][t] += r[((o * 4 + b) * 4 + t) * 64];
+  }
+  __syncthreads();
+  if (wave == 1) {
+    double* r = red + lane;
+#pragma unroll
+    for (int o = 0; o < NG; ++o)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) r[((o * 4 + b) * 4 + t) * 64] = acc[o][b >> 1][b & 1][t];
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const double* r = red + lane;
+  const int rowsP = 64 * J.ti;
+#pragma unroll
+  for (int o = 0; o < NG; ++o) {
+    gptr out = (gptr)(J.out + o * J.ostride + (int64_t)split * rowsP * J.ldo);
+#pragma unroll
+    for (int ii = 0; ii < 2; ++ii)
+#pragma unroll
+      for (int jj = 0; jj < 2; ++jj)
+        if (!(diag && jj > ii)) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            out[(int64_t)(32 * t32i + 16 * ii + g + 4 * t) * J.ldo + 32 * t32j + 16 * jj + c] =
+                acc[o][ii][jj][t] + r[((o * 4 + ii * 2 + jj) * 4 + t) * 64];
+        }
+  }
+}
+
 // ONE WORKGROUP per (job, split, tile) task; its four waves take a quarter of the split's row range each and reduce their
 // accumulators through LDS in a fixed order ((w0 + w2) + (w1 + w3)) before wave 0 stores the partial: a quarter of the split-K
 // partials of a one-wave-per-task form at the same wave-level parallelism (fp64 MFMA needs >= 2 waves per SIMD for its pipe rate).
@@ -113,6 +264,15 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_coop(const WgradJob* __restric
   DS_FIND_SEGMENT(jb, jobs, njobs, task_start, w);
   const WgradJob J = jobs[jb];
   int local = w - J.task_start;
+  if (J.ng) {      // (uniform: one job per workgroup)
+    switch (J.ng) {
+      case 1: wgrad_grouped_task<1>(J, local, nsplit, ld, Rp, red); break;
+      case 2: wgrad_grouped_task<2>(J, local, nsplit, ld, Rp, red); break;
+      case 3: wgrad_grouped_task<3>(J, local, nsplit, ld, Rp, red); break;
+      default: wgrad_grouped_task<4>(J, local, nsplit, ld, Rp, red); break;
+    }
+    return;
+  }
   int split, tile_i, tile_j, ns_eff = nsplit;
   if (J.sym) {
     const int n_off = J.ti * (J.ti - 1) / 2;
