@@ -32,6 +32,10 @@ struct PotrfItem {
   double* W;      // in: SPD matrix (lower part read); out: lower Cholesky factor, upper zeroed
   double* Linv;   // out: W^-1 (lower), may alias nothing else; may be NULL (skip inverse)
   double* LinvT;  // out: transpose of Linv (may be NULL)
+                  // PRECONDITION on Linv / LinvT: zero above (Linv) / below (LinvT) the diagonal on entry.  The LDS core (chol_lds.hpp), the
+                  // one-workgroup kernel and the look-ahead sequence (chol_xrow) write the triangular half only and never touch the other
+                  // one; only the plain blocked sequence rewrites all of LinvT (k_transpose_lower).  Nothing may use those halves as
+                  // scratch between two factorisations (tests/test_gpu_factor_direct.py reads them back after every kind of model call).
   double* scal;   // out: [0] = sum_i<nreal 2 log L_ii (= logdet), [1] = info (0 ok, else 1-based bad pivot)
   int32_t n, ld, nreal, pad;   // pad bits: 8 = skip factor write-back, 16 = accumulate into scal (blocked driver), 7 = timing
   int32_t info_offset, pad2;   // added to a failing pivot index (position of this block inside a larger matrix)

@@ -416,6 +416,29 @@ extern "C" int dsdgp_model_layer_kl(dsdgp_model* m, int32_t l, double* out) {
   return DSDGP_OK;
 }
 
+// Read-only copy of one of layer l's factorisation buffers AS STORED (the whole padded Mp x Mp, pad rows and never-written halves
+// included): no arithmetic and no clean-up, so that a test sees exactly what the kernels left.
+extern "C" int dsdgp_model_layer_matrix(dsdgp_model* m, int32_t l, int32_t which, double* out, int64_t ld_out) {
+  DS_CHECK_ARG(m && out && l >= 0 && l < m->desc.L);
+  DS_CHECK_ARG(which >= DSDGP_MAT_LU && which <= DSDGP_MAT_KUINV);
+  const LayerDev& v = m->L[l].dev;
+  DS_CHECK_ARG(ld_out >= v.Mp);
+  if (which == DSDGP_MAT_LU && !m->desc.white) {
+    // white = False: nobody reads Lu, so no path writes it back (the one-workgroup kernels skip the write-back, the head launch keeps
+    // Ku and Lu in LDS only, the look-ahead sequence leaves its panels parked above the diagonal): the buffer holds no factor
+    dsdgp_set_error("dsdgp_model_layer_matrix: layer %d keeps no Lu (it is written back for white = True models only)", l);
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(join_prep(m));
+  const double* src = which == DSDGP_MAT_LU ? v.Kp : which == DSDGP_MAT_LUINV ? v.Linv : which == DSDGP_MAT_LUINVT ? v.LinvT : v.Kinv;
+  const size_t row = (size_t)v.Mp * sizeof(double);
+  DS_HIP(hipStreamSynchronize(m->side));      // (Ku^-1 of a training step is the side stream's)
+  DS_HIP(hipMemcpy2DAsync(out, (size_t)ld_out * sizeof(double), src, row, row, (size_t)v.Mp, hipMemcpyDefault, m->ctx->stream));
+  DS_HIP(hipStreamSynchronize(m->ctx->stream));
+  return DSDGP_OK;
+}
+
 extern "C" int dsdgp_model_layer_conditional(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean,
                                              double* var) {
   DS_CHECK_ARG(m && X && mean && var && l >= 0 && l < m->desc.L && n > 0);

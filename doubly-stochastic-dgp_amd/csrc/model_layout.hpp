@@ -55,6 +55,9 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
     v.TpT = b.take<double>(d.D_out * MM);
     v.qmu = b.take<double>(Mp * d.D_out);
     v.qmu4 = b.take<double>(Mp * v.DP4);
+    // Linv / LinvT (and Tp / TpT): the factorisations write their triangular halves only — the upper half of Lu^-1 and the lower half of
+    // Lu^-T are zero because dsdgp_model_create clears the whole workspace ONCE and no kernel ever writes there (the PotrfItem
+    // precondition of linalg.hpp).  A buffer carved here must not be lent out as scratch.
     if (uniform) {
       v.Kp = Kp_all + l * MM; v.Linv = Linv_all + l * MM; v.LinvT = LinvT_all + l * MM; v.scal = scal_all + l * 8;
     } else {

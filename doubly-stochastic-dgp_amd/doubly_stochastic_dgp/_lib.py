@@ -12,6 +12,8 @@ KERN_RBF, KERN_MATERN52 = 0, 1
 MEAN_ZERO, MEAN_IDENTITY, MEAN_LINEAR = 0, 1, 2
 LIK_GAUSSIAN, LIK_MULTICLASS, LIK_BERNOULLI, LIK_POISSON, LIK_EXPONENTIAL, LIK_STUDENT_T, LIK_GAMMA, LIK_BETA = 0, 1, 2, 3, 4, 5, 6, 7
 ERR_NOT_SPD = -2
+ERR_UNSUPPORTED = -4
+MAT_LU, MAT_LUINV, MAT_LUINVT, MAT_KUINV = 0, 1, 2, 3
 ERR_RCCL = -6
 
 c_double_p = C.POINTER(C.c_double)
@@ -94,6 +96,7 @@ _PROTOS = {
     "dsdgp_model_set_sample_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "dsdgp_model_natgrad_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.POINTER(C.c_int)]),
     "dsdgp_model_layer_kl": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "dsdgp_model_layer_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "dsdgp_model_layer_conditional": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dsdgp_model_layer_conditional_full": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dsdgp_reparameterize_full": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int64, C.c_int32,

@@ -68,6 +68,14 @@ class Context:
         return ms.value, cnt.value
 
 
+def padded_M(M):
+    """pad_M of csrc/common.hpp: the order of every device-side M x M operand"""
+    if M <= 32:
+        return 32
+    q = 16 if M <= 128 else 32 if M <= 256 else 64 if M <= 512 else 128
+    return -(-M // q) * q
+
+
 def ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
@@ -487,6 +495,16 @@ class Engine:
         _lib.check(self.lib.dsdgp_model_layer_kl(self.model, l, ptr(out)))
         self.ctx.sync()
         return float(out.cpu().numpy()[0])
+
+    def layer_matrix(self, l, which):
+        """One of layer l's factorisation buffers as the kernels left it: the whole padded (Mp, Mp) array, nothing cleaned up.
+        which: "Lu" (white = True models only: DsdgpError otherwise), "Linv" = Lu^-1, "LinvT" = Lu^-T, "Kinv" = Ku^-1."""
+        code = {"Lu": _lib.MAT_LU, "Linv": _lib.MAT_LUINV, "LinvT": _lib.MAT_LUINVT, "Kinv": _lib.MAT_KUINV}[which]
+        self._prepare_checked()
+        Mp = padded_M(self.layers[l].feature.Z.shape[0])
+        out = np.empty((Mp, Mp), dtype=np.float64)
+        _lib.check(self.lib.dsdgp_model_layer_matrix(self.model, l, code, out.ctypes.data_as(C.c_void_p), Mp))
+        return out
 
     def layer_conditional(self, l, X):
         Xd = X if hasattr(X, "data_ptr") else self.ctx.to_device(X)

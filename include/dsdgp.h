@@ -241,6 +241,21 @@ int dsdgp_model_theta_changed(dsdgp_model* m);
 /* SVGP_Layer.KL (layers.py:221-246) of layer l after dsdgp_model_prepare; out: device scalar. */
 int dsdgp_model_layer_kl(dsdgp_model* m, int32_t l, double* out);
 
+/* Read-only view of what the factorisation of layer l's Ku left behind (verification aid: nothing on the evaluation path calls it).
+ * Copies the WHOLE padded Mp x Mp buffer exactly as stored — identity pad rows / columns and the halves that no kernel ever writes
+ * included, no arithmetic, no clean-up — to out (host or device memory, row-major, leading dimension ld_out >= Mp; Mp is the padded
+ * inducing count: 32 up to M = 32, then M rounded up to 16 / 32 / 64 / 128 for M <= 128 / 256 / 512 / above).  Prepares the model if
+ * needed (dsdgp_model_prepare), waits for the parameter-side work of the side stream, and returns after the copy has completed.
+ *   DSDGP_MAT_LU      Lu = chol(Ku), lower, zero above the diagonal.  Kept by white = True models only (the Cholesky adjoint reads
+ *                     it); with white = False no path writes the factor back (the head launch never leaves LDS, the one-workgroup
+ *                     kernels skip the write-back, the look-ahead sequence leaves its panels parked above the diagonal):
+ *                     DSDGP_ERR_UNSUPPORTED rather than stale data.
+ *   DSDGP_MAT_LUINV   Lu^-1, lower.  Every model, every path.
+ *   DSDGP_MAT_LUINVT  Lu^-T, upper: the same numbers as DSDGP_MAT_LUINV, transposed.  Every model, every path.
+ *   DSDGP_MAT_KUINV   Ku^-1 = Lu^-T Lu^-1, full symmetric matrix.  Every model, every path. */
+enum { DSDGP_MAT_LU = 0, DSDGP_MAT_LUINV = 1, DSDGP_MAT_LUINVT = 2, DSDGP_MAT_KUINV = 3 };
+int dsdgp_model_layer_matrix(dsdgp_model* m, int32_t l, int32_t which, double* out, int64_t ld_out);
+
 /* SVGP_Layer.conditional_ND (layers.py:178-219, full_cov=False) of layer l on X (n x D_in_l):
  * mean, var: (n x D_out_l). */
 int dsdgp_model_layer_conditional(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean, double* var);

@@ -32,6 +32,11 @@ def test_cabi_exports_every_declared_symbol():
     missing = [s for s in sorted(declared) if not hasattr(lib, s)]
     assert not missing, missing
     assert set(_lib.EXPORTED_SYMBOLS) <= declared
+    # the verification accessor of tests/test_gpu_factor_direct.py: header, ctypes mirror, library and the call-site table agree
+    assert "dsdgp_model_layer_matrix" in declared and "dsdgp_model_layer_matrix" in _lib.EXPORTED_SYMBOLS
+    assert "`dsdgp_model_layer_matrix`" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name, code in (("LU", _lib.MAT_LU), ("LUINV", _lib.MAT_LUINV), ("LUINVT", _lib.MAT_LUINVT), ("KUINV", _lib.MAT_KUINV)):
+        assert re.search(r"\bDSDGP_MAT_%s = %d\b" % (name, code), header), name
     assert lib.dsdgp_version() >= 100
 
 
