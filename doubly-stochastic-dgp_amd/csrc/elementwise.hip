@@ -176,7 +176,7 @@ __global__ void k_lik_over_samples(int kind, double p0, double p1, const double*
     }
   }
 }
-static bool lik_quad_kind_ok(int kind, double p0, double p1) {
+bool lik_quad_kind_ok(int kind, double p0, double p1) {      // (also checked by evaluate.hip)
   if (kind == DSDGP_LIK_POISSON) return p1 > 0.0;
   if (kind == DSDGP_LIK_EXPONENTIAL) return true;
   if (kind == DSDGP_LIK_GAMMA || kind == DSDGP_LIK_BETA) return p0 > 0.0;

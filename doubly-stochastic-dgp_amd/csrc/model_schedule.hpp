@@ -306,6 +306,28 @@ extern "C" int dsdgp_model_propagate(dsdgp_model* m, const double* X, int64_t n,
   return forward_layers(m, X, n, S, zs, zstride, seed, false, true, Fs, Fmeans, Fvars);
 }
 
+// Held-out evaluation (demos/run_regression.py:108-123 on dgp.py:116-126): the forward pass of dsdgp_model_propagate with only the last
+// layer's mean and variance wanted (they stay in the workspace), then the mixture reduction of evaluate.hip on them, on the same stream.
+// The likelihood's positive parameter is read from the model's own device copy: nothing goes through the host.
+int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const double* p0_dev, const double* mean, const double* var,
+                        const double* Y, int64_t n, int S, int DY, double* rows_out, double* acc, int accumulate);
+extern "C" int dsdgp_model_evaluate(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                                    const int64_t* zstride, uint64_t seed, double* rows_out, double* acc, int accumulate) {
+  DS_CHECK_ARG(m && X && Y && acc);
+  DS_CHECK_ARG(!zs || zstride);
+  if (m->sample_w) {
+    dsdgp_set_error("dsdgp_model_evaluate: quadrature sample weights are set (dsdgp_model_set_sample_weights); the mixture is an unweighted mean");
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
+  const LayerState& last = m->L[m->desc.L - 1];
+  const int kind = m->desc.lik_kind;
+  DS_CHECK_ARG(kind != DSDGP_LIK_MULTICLASS || last.dev.D_out == m->desc.num_classes);
+  return eval_mixture_launch(m->ctx, kind, 1.0, m->desc.lik_aux, lik_has_param(kind) ? m->lik_const : nullptr, last.mean, last.var, Y, n, S,
+                             last.dev.D_out, rows_out, acc, accumulate);
+}
+
 // (re)build the split-K job lists for minibatch shape (n, S); uploaded once, reused by every step of that shape
 static int ensure_plan(dsdgp_model* m, int64_t n, int S) {
   if (m->plan_n == n && m->plan_S == S) return DSDGP_OK;

@@ -288,6 +288,69 @@ class DGP_Base(Parameterized):
         Fmean, Fvar = self._build_predict(Xnew, full_cov=False, S=num_samples)
         return self.likelihood.predict_density_logmeanexp(Fmean, Fvar, np.asarray(Ynew, dtype=np.float64))
 
+    def evaluate(self, Xs, Ys, num_samples, batch_size=1000, Y_std=1.0, zs=None, return_rows=False):
+        """Held-out scores as demos/run_regression.py:108-123 computes them, without leaving the device: over row batches of
+        `batch_size` (a ragged last one allowed) the forward pass and the reduction over the `num_samples` mixture components add into
+        one device accumulator, read back once at the end.  Xs / Ys: numpy arrays or device tensors.  zs: explicit N(0, 1) draws per
+        layer, broadcastable to (S, N*, D_out) (dgp.py:62,68); else one `_draw_seed()` per batch, in batch order.
+        Returns a dict: `rmse` = Y_std sqrt(mean((Ys - mhat)^2)) over rows and outputs (run_regression.py:121) and `rmse_per_output`
+        (MultiClass: `error_rate` of argmax_k of the mixture class probabilities instead), `log_density` = the mean over rows and
+        outputs of logsumexp_S log p(y | .) - log S (dgp.py:121-126), `n`, and with return_rows the (N*, D, 3) array `rows` of
+        [mixture mean, mixture variance, log density]."""
+        from .gpflow_compat import MultiClass
+        eng = self.engine()
+        ctx = eng.ctx
+        torch = ctx.torch
+        S = int(num_samples)
+        batch_size = int(batch_size)
+        if batch_size < 1 or S < 1:
+            raise ValueError("batch_size and num_samples must be positive")
+        gaussian = not self.likelihood.needs_broadcasting
+        Y_std = float(Y_std)
+        if not Y_std > 0.0 or (not gaussian and Y_std != 1.0):
+            raise ValueError("Y_std rescales a Gaussian density only (and must be positive)")
+        if not hasattr(Ys, "data_ptr"):
+            self.likelihood.check_targets(Ys)
+        Xd = Xs.contiguous() if hasattr(Xs, "data_ptr") else ctx.to_device(Xs)
+        Yd = Ys.contiguous() if hasattr(Ys, "data_ptr") else ctx.to_device(Ys)
+        N = Xd.shape[0]
+        if N < 1 or Yd.shape[0] != N:
+            raise ValueError(f"Xs has {N} rows, Ys {Yd.shape[0]}")
+        D = self.layers[-1].num_outputs
+        if zs is not None:
+            if len(zs) != len(self.layers):
+                raise ValueError("zs needs one entry (or None) per layer")
+            zs = [z if z is None or hasattr(z, "data_ptr") else ctx.to_device(np.asarray(z, dtype=np.float64)) for z in zs]
+            if any(z is not None and z.dim() != 3 for z in zs):
+                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
+        acc = ctx.empty(3, D)
+        rows = ctx.empty(N, D, 3) if return_rows else None
+        keep = []
+        for a in range(0, N, batch_size):
+            b = min(a + batch_size, N)
+            zb = None
+            if zs is not None:      # the batch's rows of every draw that is not broadcast over rows
+                zb = [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
+            keep.append(eng.evaluate_batch(Xd[a:b], Yd[a:b], S, acc, a > 0, zs=zb, seed=self._draw_seed(),
+                                           rows=rows[a:b] if return_rows else None))
+        ctx.sync()
+        sums = acc.cpu().numpy()
+        cnt = float(sums[2].sum()) if not isinstance(self.likelihood.likelihood, MultiClass) else float(sums[2, 0])
+        out = {"n": N}
+        if isinstance(self.likelihood.likelihood, MultiClass):
+            out["error_rate"] = float(sums[0, 0]) / cnt
+            out["log_density"] = float(sums[1, 0]) / cnt
+        else:
+            out["rmse"] = Y_std * float(np.sqrt(sums[0].sum() / cnt))
+            out["rmse_per_output"] = Y_std * np.sqrt(sums[0] / sums[2])
+            # the model lives in standardised units y = y_orig / Y_std; the density of y_orig is that of y divided by Y_std,
+            # N(y c | m c, v c^2) = N(y | m, v) / c, component by component, hence also for the mixture: log p(y_orig) = l - log Y_std
+            # (run_regression.py:122 scales targets, means and standard deviations by Y_std before norm.logpdf)
+            out["log_density"] = float(sums[1].sum()) / cnt - (np.log(Y_std) if gaussian else 0.0)
+        if return_rows:
+            out["rows"] = rows.cpu().numpy()
+        return out
+
 
 class DGP_Quad(DGP_Base):
     """A DGP evaluated with Gauss-Hermite quadrature over the inner layers instead of Monte-Carlo samples (dgp.py:129-166):

@@ -416,6 +416,18 @@ class Engine:
             raise _lib.CholeskyError(f"Cholesky decomposition was not successful (Kuu pivot {int(out[3])})")
         return out
 
+    def evaluate_batch(self, Xd, Yd, S, acc, accumulate, zs=None, seed=0, rows=None):
+        """dsdgp_model_evaluate on one batch of device rows: forward pass + mixture reduction into the device accumulator `acc`
+        (3 x D_out of the last layer; added to when `accumulate`), per-row values into `rows` (n, D_out, 3) if given.  Asynchronous."""
+        n = Xd.shape[0]
+        self._check_targets_shape(Yd, n)
+        self._ensure(n, S)
+        self._prepare_checked()
+        zp, zst, keep = self._zs_args(zs, S, n)
+        _lib.check(self.lib.dsdgp_model_evaluate(self.model, ptr(Xd), ptr(Yd), n, S, zp, zst, C.c_uint64(seed), ptr(rows), ptr(acc),
+                                                 int(bool(accumulate))))
+        return keep
+
     def adam_step(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8):
         # the library refuses a pruned gradient: count the step only once it has been taken
         _lib.check(self.lib.dsdgp_model_adam_step(self.model, lr, beta1, beta2, eps, self.adam_t + 1))

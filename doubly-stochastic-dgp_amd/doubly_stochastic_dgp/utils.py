@@ -74,6 +74,38 @@ class BroadcastingLikelihood:
             return _lib.LIK_BETA, float(lik.scale.value), 1.0
         return _lib.LIK_STUDENT_T, float(lik.scale.value), lik.deg_free
 
+    def mixture_args(self):
+        """(kind, p0, p1) of dsdgp_eval_mixture for the wrapped likelihood: generic_args for the quadrature likelihoods, p0 = the noise
+        variance for the Gaussian, nothing for Bernoulli / MultiClass."""
+        from . import _lib
+        from .gpflow_compat import MultiClass
+        if not self.needs_broadcasting:
+            return _lib.LIK_GAUSSIAN, float(self.likelihood.variance.value), 1.0
+        if self.bernoulli:
+            return _lib.LIK_BERNOULLI, 1.0, 1.0
+        if self.generic:
+            return self.generic_args()
+        assert isinstance(self.likelihood, MultiClass)
+        return _lib.LIK_MULTICLASS, 1.0, 1.0
+
+    def evaluate_mixture(self, Fmu, Fvar, Y, rows=False):
+        """dsdgp_eval_mixture on (S, N, D) component means / variances and targets Y: the accumulator as a (3, D) array [squared error
+        (MultiClass: misclassifications), log density, rows] summed over N, and with rows=True the (N, D, 3) per-row values
+        [mixture mean, mixture variance, log density] as well."""
+        self.check_targets(Y)
+        from . import _lib
+        from .engine import Context, ptr
+        ctx = Context.get()
+        Fmu = np.asarray(Fmu, dtype=np.float64)
+        S, N, D = Fmu.shape
+        m, v, y = ctx.to_device(Fmu), ctx.to_device(np.broadcast_to(Fvar, Fmu.shape)), ctx.to_device(Y)
+        acc = ctx.empty(3, D)
+        out = ctx.empty(N, D, 3) if rows else None
+        kind, p0, p1 = self.mixture_args()
+        _lib.check(ctx.lib.dsdgp_eval_mixture(ctx.handle, kind, p0, p1, ptr(m), ptr(v), ptr(y), N, S, D, ptr(out), ptr(acc), 0))
+        ctx.sync()
+        return (acc.cpu().numpy(), out.cpu().numpy()) if rows else acc.cpu().numpy()
+
     def check_targets(self, Y):
         """MultiClass: Y must hold integer class labels in [0, num_classes) — the device kernel indexes its per-class
         accumulators with them ([UPSTREAM] tf.one_hot / gather would error or zero-fill; one-hot or NaN targets are a bug)."""

@@ -60,7 +60,7 @@ int dsdgp_ctx_destroy(dsdgp_ctx* ctx);
 int dsdgp_sync(dsdgp_ctx* ctx);
 /* HIP-event timing of the most recent launch of a named kernel class on the ctx stream (bench.py roofline):
  * enable, run, then read the accumulated milliseconds and launch count. name in
- * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm"}. */
+ * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate"}. */
 int dsdgp_prof_enable(dsdgp_ctx* ctx, int on);
 int dsdgp_prof_read(dsdgp_ctx* ctx, const char* name, double* total_ms, int64_t* launches, int reset);
 /* Kernel launches this library has enqueued in this process so far (all contexts; memsets / copies not counted): the difference
@@ -343,6 +343,27 @@ int dsdgp_lik_var_exp(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const 
 /* Likelihood.predict_mean_and_var by the same rule: E_y = sum w cm(f_k), V_y = sum w (cv(f_k) + cm(f_k)^2) - E_y^2. */
 int dsdgp_lik_predict(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const double* mean, const double* var, int64_t count,
                       double* out_mean, double* out_var);
+
+/* Held-out evaluation, the reduction of demos/run_regression.py:108-123 over the S components of DGP_Base.predict_y / predict_density
+ * (dgp.py:116-126), on caller-supplied mean / var ((S*n) x DY, row s*n + i, as dsdgp_model_propagate writes them) and Y (n x DY;
+ * MultiClass: n x 1 labels, DY = K).  With (E_s, V_s) = predict_mean_and_var of component s, per (i, d):
+ *   mhat = mean_s E_s ;  mixture variance = mean_s (V_s + E_s^2) - mhat^2 ;  l = logsumexp_s log p(y | mean_s, var_s) - log S
+ * (S = 1: the component's own values, exactly).  kind = any DSDGP_LIK_*; p0 = Gaussian.variance / StudentT.scale / Gamma.shape /
+ * Beta.scale, p1 = Poisson.binsize / StudentT.deg_free (ignored where the likelihood has no such parameter).
+ *   rows_out (device, n x DY x 3, or NULL): [mhat, mixture variance, l] per (i, d); MultiClass: per class k its mixture probability
+ *            and that probability's variance, l of the row repeated for every k.
+ *   acc (device, 3*DY doubles): acc[d] = sum_i (Y - mhat)^2, acc[DY + d] = sum_i l, acc[2*DY + d] = n — overwritten, or added to when
+ *            accumulate != 0 (batches; the sums of data-parallel ranks add up).  MultiClass: d = 0 only (the other entries stay 0), with
+ *            acc[0] = the number of rows whose argmax_k mhat_k (ties: the lowest k) differs from the label.
+ * Fixed-order reductions: the same inputs and n give the same bits.  DSDGP_ERR_UNSUPPORTED for a kind outside DSDGP_LIK_* or K > 32. */
+int dsdgp_eval_mixture(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const double* mean, const double* var, const double* Y,
+                       int64_t n, int32_t S, int32_t DY, double* rows_out, double* acc, int accumulate);
+/* The same on a model's own predictions: the forward pass of dsdgp_model_propagate (same kernels, same Philox draws from `seed`, same
+ * `zs` injection) with only the last layer's mean and variance kept, in the workspace, then dsdgp_eval_mixture on them with the
+ * model's likelihood — one batch of the loop of demos/run_regression.py:108-123 without a copy to the host.  X (n x D_in0), Y as above.
+ * DSDGP_ERR_UNSUPPORTED while quadrature sample weights are set (dsdgp_model_set_sample_weights). */
+int dsdgp_model_evaluate(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                         const int64_t* zstride, uint64_t seed, double* rows_out, double* acc, int accumulate);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
