@@ -62,6 +62,22 @@ struct LayerBwdArgs {
   const double* Tp;     // (D_out x Mp x Mp) q_sqrt, and its transpose (Csave form)
   const double* TpT;
   int64_t ldA;
+  // Pad columns [Rin, ldA) of the row-major (.. x ldA) buffers.  ldA = round_up(Rin, 16) is set per call, so on a reused model the pad
+  // of a small call lies on the data of an earlier, larger one: nothing is zeroed between calls, every producer writes its own pad on
+  // every call (tests/test_gpu_model_reuse.py holds a reused model to the bits of a fresh one):
+  //   Asave     the forward chain stores 0 for r >= Rin (k_layer_fwd_sm's A store, the fused last-layer launch; the GEMM pass through
+  //             the zero pad of k_kuf's K)
+  //   XT1       [X^T;1]: 0 for r >= Rin — the forward chain's XT1 store, k_xt1 (GEMM pass), k_adj_prep
+  //   VB, MB    whoever produces the adjoints: the next layer's backward chain (MBp / VBp: zeros for Rin <= row < ldA), the adjoint
+  //             prologue of this chain (MBw / VBw, same), k_adj_prep (every r < ld, 0 where r >= Rin or d >= D_out), the likelihood
+  //             epilogue of the last forward chain (lik_MB / lik_VB) and the k_lik_* kernels (MBt / VBt)
+  //   GW        this chain, all ldA columns: 0 where r >= Rin or m >= M
+  //   E         this chain, all ldA columns; the pad holds whatever the chain computed for the clamped rows — its only consumer, the
+  //             product E A^T, meets Asave's zero pad there
+  // Most consumers do not rely on one pad alone: the chain selects vbar = 0 for r >= ldA only, but the products over the row index
+  // (A diag(vbar_d) A^T, A mbar^T, E A^T) have Asave's zero pad as an operand, GW [X^T;1]^T has two zero pads, and the
+  // hyper-parameter partial sums are masked with r < Rin.  The split-K partials are another matter: ensure_plan zeroes part_big and the
+  // tickets when the shape changes, because diagonal tiles fill only their first ns_diag slots (dropping that reset fails the test).
   const double* VB;     // (D_out.. x ldA)  d loss / d var, transposed, zero beyond Rin
   const double* MB;     // (>=DP4 x ldA)    d loss / d mean, transposed, zero padded
   double* E;            // (Mp x ldA)  out: so that d loss/d Ku (data) = -sym(E A^T)
