@@ -73,12 +73,20 @@ __global__ __launch_bounds__(256) void k_ng_theta1(const LayerDev* __restrict__ 
 // m+ = T+ (T+^T theta1) with T+[i][j] = Lr^-1[M-1-j][M-1-i]: both products walk ROWS of the inverse factor / its transpose
 //   w[j]  = sum_i T+[i][j] theta1[i] = sum_c Lr^-1[M-1-j][c] theta1[M-1-c]         (second = 0: row M-1-j of ngLAinv)
 //   m+[i] = sum_j T+[i][j] w[j]      = sum_c Lr^-T[M-1-i][c] w[M-1-c]              (second = 1: row M-1-i of ngLAinvT)
+// A step in which some A_d failed to factor (ngScal[2 d + 1] != 0) is refused as a whole — [UPSTREAM] tf.cholesky raises on the batch
+// and no variable is assigned: neither the second product nor k_ng_write stores into theta then.
+__device__ __forceinline__ bool ng_refused(const LayerDev& v) {
+  bool bad = false;
+  for (int d = 0; d < v.D_out; ++d) bad |= v.ngScal[2 * d + 1] != 0.0;
+  return bad;
+}
 __global__ __launch_bounds__(256) void k_ng_mu(const LayerDev* __restrict__ layers, int l, double* __restrict__ theta, int second) {
   const LayerDev v = layers[l];
   const int Mp = v.Mp, M = v.M;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= v.D_out * M) return;
   const int d = row / M, i = row % M;
+  if (second && ng_refused(v)) return;
   const double* R = (second ? v.ngLAinvT : v.ngLAinv) + (int64_t)d * Mp * Mp + (int64_t)(M - 1 - i) * Mp;
   const double* x = (second ? v.ngV : v.ngTheta1) + d * Mp;
   // only the triangle that holds the factor is read: columns <= the row of Lr^-1, >= the row of its transpose
@@ -96,6 +104,7 @@ __global__ void k_ng_write(const LayerDev* __restrict__ layers, int l, double* _
   const LayerDev v = layers[l];
   const int Mp = v.Mp, M = v.M;
   const int64_t tot = (int64_t)v.D_out * M * M;
+  if (ng_refused(v)) return;
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < tot; idx += (int64_t)gridDim.x * blockDim.x) {
     const int d = (int)(idx / ((int64_t)M * M)), rem = (int)(idx % ((int64_t)M * M)), i = rem / M, j = rem % M;
     theta[v.off_q_sqrt + idx] = (j <= i) ? v.ngLAinvT[((int64_t)d * Mp + (M - 1 - i)) * Mp + (M - 1 - j)] : 0.0;

@@ -488,11 +488,15 @@ class Engine:
 
     def natgrad_step(self, l, gamma, check=True):
         """[UPSTREAM] NatGradOptimizer(gamma) step on layer l's (q_mu, q_sqrt) from the gradient of the last
-        elbo(with_grad=True)."""
+        elbo(with_grad=True).  A step whose A = S^-1 + 2 gamma Sbar is not positive definite for some output is refused: the library
+        leaves theta as it was (CholeskyError with check=True; silently with check=False, as every unchecked call)."""
         info = C.c_int(0)
-        _lib.check(self.lib.dsdgp_model_natgrad_step(self.model, l, float(gamma), C.byref(info) if check else None))
-        self._dev_dirty = True
-        self._needs_prepare = True
+        try:
+            _lib.check(self.lib.dsdgp_model_natgrad_step(self.model, l, float(gamma), C.byref(info) if check else None))
+        finally:
+            # also on the error path: the launches were issued and the library has dropped its prepared state
+            self._dev_dirty = True
+            self._needs_prepare = True
 
     def set_sample_weights(self, w_dev):
         """DGP_Quad (dgp.py:160-166): weight the S propagated samples by w (device tensor, kept alive here) instead of 1/S;

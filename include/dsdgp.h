@@ -208,7 +208,8 @@ int dsdgp_model_train_step_minibatch(dsdgp_model* m, const double* X_all, const 
 /* [UPSTREAM] gpflow.training.NatGradOptimizer(gamma) step on layer l's (q_mu, q_sqrt), using the loss gradient left in
  * `grad` by the last dsdgp_model_elbo(with_grad=1) (demos/demo_regression_UCI.ipynb:360-366, tests/test_collapsed.py:100):
  * per output, natural parameters theta <- theta - gamma dL/d eta, then back to (mean, Cholesky factor).
- * info (host, may be NULL): non-zero if the updated covariance is not SPD. */
+ * info (host, may be NULL): non-zero (with DSDGP_ERR_NOT_SPD) if A = S^-1 + 2 gamma dL/dS is not SPD for some output.  Such a
+ * step is refused as a whole, with or without info: theta is not written ([UPSTREAM] tf.cholesky raises, no variable is assigned). */
 int dsdgp_model_natgrad_step(dsdgp_model* m, int32_t l, double gamma, int* info);
 
 /* [UPSTREAM] tf.gradients(loss, var_list) with var_list = the (q_mu, q_sqrt) of the upper layer(s), as
