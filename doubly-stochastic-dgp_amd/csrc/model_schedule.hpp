@@ -328,6 +328,52 @@ extern "C" int dsdgp_model_evaluate(dsdgp_model* m, const double* X, const doubl
                              last.dev.D_out, rows_out, acc, accumulate);
 }
 
+// Calibration of the predictive mixture (calibration.hip) on a model's own predictions: the forward pass exactly as dsdgp_model_evaluate
+// runs it, then the quantile / PIT + CRPS kernel on the workspace's mean and variance, on the same stream.  The Gaussian noise variance is
+// read from the model's device copy.
+int mixture_quantiles_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
+                             int64_t n, int S, int DY, const double* probs, int P, double* q_out);
+int mixture_calibration_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
+                               const double* Y, int64_t n, int S, int DY, const double* probs, int P, double* rows_out, double* acc,
+                               int accumulate);
+static int calibration_refusals(const char* who, dsdgp_model* m, bool needs_gaussian) {
+  if (m->sample_w) {
+    dsdgp_set_error("%s: quadrature sample weights are set (dsdgp_model_set_sample_weights); the mixture is an unweighted mean", who);
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  if (needs_gaussian && m->desc.lik_kind != DSDGP_LIK_GAUSSIAN) {
+    dsdgp_set_error("%s: the predictive y of likelihood kind %d is not a Gaussian mixture; only the latent f (level 0) is covered", who,
+                    m->desc.lik_kind);
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  return DSDGP_OK;
+}
+extern "C" int dsdgp_model_quantiles(dsdgp_model* m, const double* X, int64_t n, int32_t S, const double* const* zs,
+                                     const int64_t* zstride, uint64_t seed, int32_t level, const double* probs, int32_t P,
+                                     double* q_out) {
+  DS_CHECK_ARG(m && X && probs && q_out);
+  DS_CHECK_ARG(!zs || zstride);
+  DS_CHECK_ARG(level == 0 || level == 1);
+  DS_TRY(calibration_refusals("dsdgp_model_quantiles", m, level == 1));
+  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
+  const LayerState& last = m->L[m->desc.L - 1];
+  return mixture_quantiles_launch(m->ctx, last.mean, last.var, 0.0, level == 1 ? m->lik_const : nullptr, n, S, last.dev.D_out, probs, P,
+                                  q_out);
+}
+extern "C" int dsdgp_model_calibration(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                                       const int64_t* zstride, uint64_t seed, const double* probs, int32_t P, double* rows_out,
+                                       double* acc, int accumulate) {
+  DS_CHECK_ARG(m && X && Y && probs && acc);
+  DS_CHECK_ARG(!zs || zstride);
+  DS_TRY(calibration_refusals("dsdgp_model_calibration", m, true));
+  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
+  const LayerState& last = m->L[m->desc.L - 1];
+  return mixture_calibration_launch(m->ctx, last.mean, last.var, 0.0, m->lik_const, Y, n, S, last.dev.D_out, probs, P, rows_out, acc,
+                                    accumulate);
+}
+
 // (re)build the split-K job lists for minibatch shape (n, S); uploaded once, reused by every step of that shape
 static int ensure_plan(dsdgp_model* m, int64_t n, int S) {
   if (m->plan_n == n && m->plan_S == S) return DSDGP_OK;

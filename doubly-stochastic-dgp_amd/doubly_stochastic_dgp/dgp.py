@@ -351,6 +351,115 @@ class DGP_Base(Parameterized):
             out["rows"] = rows.cpu().numpy()
         return out
 
+    # ------------------------------------------------------------------ calibration of the predictive mixture
+    MAX_PROBS = 16
+
+    def _calibration_args(self, what, X, num_samples, probs, batch_size, Y_std, zs, needs_gaussian, Y=None):
+        """Everything predict_quantiles / calibration can refuse without a device: (S, batch_size, Y_std, probs as a float64 array).
+        Called before self.engine() is touched, so a machine without a GPU reports the bad argument and not the missing device."""
+        if needs_gaussian and self.likelihood.needs_broadcasting:
+            raise NotImplementedError(f"{what}: the predictive y of {type(self.likelihood.likelihood).__name__} is not a mixture of "
+                                      "Gaussians; only level=\"f\" (the latent function) is covered")
+        probs = np.atleast_1d(np.asarray(probs, dtype=np.float64))
+        if probs.ndim != 1 or not 1 <= probs.size <= self.MAX_PROBS:
+            raise ValueError(f"probs must hold 1 .. {self.MAX_PROBS} probabilities")
+        if not np.all((probs > 0.0) & (probs < 1.0)):
+            raise ValueError("every probability must lie inside (0, 1)")
+        S, batch_size = int(num_samples), int(batch_size)
+        if batch_size < 1 or S < 1:
+            raise ValueError("batch_size and num_samples must be positive")
+        Y_std = float(Y_std)
+        if not (Y_std > 0.0 and np.isfinite(Y_std)):
+            raise ValueError("Y_std must be positive")
+        shape = lambda a: tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+        if len(shape(X)) != 2 or shape(X)[0] < 1:
+            raise ValueError("X must be a non-empty (N, D_in) array")
+        if Y is not None:
+            want = (shape(X)[0], self.layers[-1].num_outputs)
+            if shape(Y) != want:
+                raise ValueError(f"Ys has shape {shape(Y)}, expected {want} (rows of Xs x outputs of the last layer)")
+        if zs is not None:
+            if len(zs) != len(self.layers):
+                raise ValueError("zs needs one entry (or None) per layer")
+            if any(z is not None and len(shape(z)) != 3 for z in zs):
+                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
+        return S, batch_size, Y_std, np.ascontiguousarray(probs)
+
+    @staticmethod
+    def _device_zs(ctx, zs):
+        if zs is None:
+            return None
+        return [z if z is None or hasattr(z, "data_ptr") else ctx.to_device(np.asarray(z, dtype=np.float64)) for z in zs]
+
+    def predict_quantiles(self, Xnew, num_samples, probs=(0.025, 0.5, 0.975), level="y", batch_size=1000, Y_std=1.0, Y_mean=0.0,
+                          zs=None):
+        """Quantiles of the predictive mixture of `num_samples` Gaussians (dgp.py:116-126), solved on the device: the (N*, D, P) array
+        Y_mean + Y_std q with F(q[i, d, k]) = probs[k] — exact where demos/using_natural_gradients.ipynb cell 9 takes np.percentile of
+        100 draws and demos/demo_step_function.ipynb:83-85 / demos/priors.ipynb:1020 use mean +- 1.96 sqrt(var).  level "y": the
+        observations (Gaussian likelihood only; the noise variance is added), "f": the latent function of any likelihood.  Xnew: numpy
+        or a device tensor, in row batches of `batch_size` (a ragged last one allowed).  zs as in `evaluate`; else one `_draw_seed()`
+        per batch, in batch order."""
+        if level not in ("f", "y"):
+            raise ValueError(f"level must be \"f\" or \"y\", not {level!r}")
+        S, batch_size, Y_std, probs = self._calibration_args("predict_quantiles", Xnew, num_samples, probs, batch_size, Y_std, zs,
+                                                             level == "y")
+        eng = self.engine()
+        ctx = eng.ctx
+        Xd = Xnew.contiguous() if hasattr(Xnew, "data_ptr") else ctx.to_device(Xnew)
+        zs = self._device_zs(ctx, zs)
+        N, D, P = Xd.shape[0], self.layers[-1].num_outputs, probs.size
+        q = ctx.empty(N, D, P)
+        keep = []
+        for a in range(0, N, batch_size):
+            b = min(a + batch_size, N)
+            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
+            keep.append(eng.quantiles_batch(Xd[a:b], S, probs, q[a:b], level=1 if level == "y" else 0, zs=zb, seed=self._draw_seed()))
+        ctx.sync()
+        return float(Y_mean) + Y_std * q.cpu().numpy()
+
+    def calibration(self, Xs, Ys, num_samples, probs=(0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975), batch_size=1000, Y_std=1.0, zs=None,
+                    return_rows=False):
+        """Calibration scores of held-out targets under the predictive mixture (Gaussian likelihood), reduced on the device into one
+        accumulator over the row batches and read back once.  Returns a dict: `crps` = Y_std x the mean over rows and outputs of the
+        closed-form continuous ranked probability score and `crps_per_output`; `pit_le`, (P, D): the fraction of targets whose
+        probability integral transform u = F(y) is <= probs[k] (a calibrated model gives probs[k]); `coverage`: for every pair p, 1 - p
+        both in probs, {1 - 2p: fraction of targets with p < u <= 1 - p}, the coverage of the central interval, over rows and outputs;
+        `n`; with return_rows the (N*, D, 2) array `rows` of [u, CRPS] in model units."""
+        S, batch_size, Y_std, probs = self._calibration_args("calibration", Xs, num_samples, probs, batch_size, Y_std, zs, True, Y=Ys)
+        eng = self.engine()
+        ctx = eng.ctx
+        Xd = Xs.contiguous() if hasattr(Xs, "data_ptr") else ctx.to_device(Xs)
+        Yd = Ys.contiguous() if hasattr(Ys, "data_ptr") else ctx.to_device(Ys)
+        zs = self._device_zs(ctx, zs)
+        N, D, P = Xd.shape[0], self.layers[-1].num_outputs, probs.size
+        acc = ctx.empty(2 + P, D)
+        rows = ctx.empty(N, D, 2) if return_rows else None
+        keep = []
+        for a in range(0, N, batch_size):
+            b = min(a + batch_size, N)
+            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
+            keep.append(eng.calibration_batch(Xd[a:b], Yd[a:b], S, probs, acc, a > 0, zs=zb, seed=self._draw_seed(),
+                                              rows=rows[a:b] if return_rows else None))
+        ctx.sync()
+        out = calibration_scores(acc.cpu().numpy(), probs, Y_std)
+        out["n"] = N
+        if return_rows:
+            out["rows"] = rows.cpu().numpy()
+        return out
+
+
+def calibration_scores(sums, probs, Y_std=1.0):
+    """The dict of DGP_Base.calibration (without `n` and `rows`) from the (2 + P, D) accumulator of dsdgp_mixture_calibration."""
+    cnt = sums[1]
+    out = {"crps": Y_std * float(sums[0].sum() / cnt.sum()), "crps_per_output": Y_std * sums[0] / cnt, "pit_le": sums[2:] / cnt,
+           "coverage": {}}
+    tot = sums[2:].sum(1) / cnt.sum()
+    for k, p in enumerate(probs):
+        for l, r in enumerate(probs):
+            if p < 0.5 and abs(r - (1.0 - p)) <= 1e-12:      # (1 - 0.025 and 0.975 differ in the last bit)
+                out["coverage"][float(1.0 - 2.0 * p)] = float(tot[l] - tot[k])
+    return out
+
 
 class DGP_Quad(DGP_Base):
     """A DGP evaluated with Gauss-Hermite quadrature over the inner layers instead of Monte-Carlo samples (dgp.py:129-166):

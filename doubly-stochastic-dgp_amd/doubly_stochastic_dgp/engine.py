@@ -428,6 +428,32 @@ class Engine:
                                                  int(bool(accumulate))))
         return keep
 
+    def quantiles_batch(self, Xd, S, probs, q, level=1, zs=None, seed=0):
+        """dsdgp_model_quantiles on one batch of device rows: forward pass + the mixture's quantiles at the host array `probs` into the
+        device tensor `q` (n, D_out, P).  level 1: the predictive y (Gaussian likelihood), 0: the latent f.  Asynchronous."""
+        n = Xd.shape[0]
+        probs = np.ascontiguousarray(probs, dtype=np.float64)
+        self._ensure(n, S)
+        self._prepare_checked()
+        zp, zst, keep = self._zs_args(zs, S, n)
+        _lib.check(self.lib.dsdgp_model_quantiles(self.model, ptr(Xd), n, S, zp, zst, C.c_uint64(seed), int(level),
+                                                  probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(q)))
+        return keep
+
+    def calibration_batch(self, Xd, Yd, S, probs, acc, accumulate, zs=None, seed=0, rows=None):
+        """dsdgp_model_calibration on one batch of device rows: forward pass + PIT / CRPS reduction into the device accumulator `acc`
+        ((2 + P) x D_out; added to when `accumulate`), per-row [u, CRPS] into `rows` (n, D_out, 2) if given.  Asynchronous."""
+        n = Xd.shape[0]
+        probs = np.ascontiguousarray(probs, dtype=np.float64)
+        self._check_targets_shape(Yd, n)
+        self._ensure(n, S)
+        self._prepare_checked()
+        zp, zst, keep = self._zs_args(zs, S, n)
+        _lib.check(self.lib.dsdgp_model_calibration(self.model, ptr(Xd), ptr(Yd), n, S, zp, zst, C.c_uint64(seed),
+                                                    probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(rows), ptr(acc),
+                                                    int(bool(accumulate))))
+        return keep
+
     def adam_step(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8):
         # the library refuses a pruned gradient: count the step only once it has been taken
         _lib.check(self.lib.dsdgp_model_adam_step(self.model, lr, beta1, beta2, eps, self.adam_t + 1))

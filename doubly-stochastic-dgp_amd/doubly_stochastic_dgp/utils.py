@@ -106,6 +106,61 @@ class BroadcastingLikelihood:
         ctx.sync()
         return (acc.cpu().numpy(), out.cpu().numpy()) if rows else acc.cpu().numpy()
 
+    def _mixture_noise(self, level, what):
+        if level not in ("f", "y"):
+            raise ValueError(f"level must be \"f\" or \"y\", not {level!r}")
+        if level == "f":
+            return 0.0
+        if self.needs_broadcasting:
+            raise NotImplementedError(f"{what}: the predictive y of {type(self.likelihood).__name__} is not a mixture of Gaussians; "
+                                      "only level=\"f\" is covered")
+        return float(self.likelihood.variance.value)
+
+    @staticmethod
+    def _probs(probs):
+        from . import _lib
+        probs = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)))
+        if probs.ndim != 1 or not 1 <= probs.size <= 16 or not np.all((probs > 0.0) & (probs < 1.0)):
+            raise ValueError("probs must hold 1 .. 16 probabilities inside (0, 1)")
+        return probs, probs.ctypes.data_as(_lib.c_double_p)
+
+    def mixture_quantiles(self, Fmu, Fvar, probs, level="y"):
+        """dsdgp_mixture_quantiles on (S, N, D) component means / variances: the (N, D, P) quantiles of the equally weighted mixture of
+        N(Fmu_s, Fvar_s + noise), noise = the Gaussian likelihood's variance for level "y", 0 for level "f"."""
+        noise = self._mixture_noise(level, "mixture_quantiles")
+        probs, pp = self._probs(probs)
+        from . import _lib
+        from .engine import Context, ptr
+        ctx = Context.get()
+        Fmu = np.asarray(Fmu, dtype=np.float64)
+        S, N, D = Fmu.shape
+        m, v = ctx.to_device(Fmu), ctx.to_device(np.broadcast_to(Fvar, Fmu.shape))
+        q = ctx.empty(N, D, probs.size)
+        _lib.check(ctx.lib.dsdgp_mixture_quantiles(ctx.handle, ptr(m), ptr(v), noise, N, S, D, pp, probs.size, ptr(q)))
+        ctx.sync()
+        return q.cpu().numpy()
+
+    def mixture_calibration(self, Fmu, Fvar, Y, probs, rows=False):
+        """dsdgp_mixture_calibration on (S, N, D) component means / variances and targets Y (N, D), Gaussian likelihood: the accumulator
+        as a (2 + P, D) array [sum of CRPS, rows, #(u <= p_0), ...] summed over N, and with rows=True the (N, D, 2) per-row values
+        [u, CRPS] as well."""
+        noise = self._mixture_noise("y", "mixture_calibration")
+        probs, pp = self._probs(probs)
+        from . import _lib
+        from .engine import Context, ptr
+        ctx = Context.get()
+        Fmu = np.asarray(Fmu, dtype=np.float64)
+        S, N, D = Fmu.shape
+        if np.shape(Y) != (N, D):
+            raise ValueError(f"Y has shape {np.shape(Y)}, expected {(N, D)}")
+        m, v, y = ctx.to_device(Fmu), ctx.to_device(np.broadcast_to(Fvar, Fmu.shape)), ctx.to_device(Y)
+        acc = ctx.empty(2 + probs.size, D)
+        out = ctx.empty(N, D, 2) if rows else None
+        _lib.check(ctx.lib.dsdgp_mixture_calibration(ctx.handle, ptr(m), ptr(v), noise, ptr(y), N, S, D, pp, probs.size, ptr(out),
+                                                     ptr(acc), 0))
+        ctx.sync()
+        return (acc.cpu().numpy(), out.cpu().numpy()) if rows else acc.cpu().numpy()
+
     def check_targets(self, Y):
         """MultiClass: Y must hold integer class labels in [0, num_classes) — the device kernel indexes its per-class
         accumulators with them ([UPSTREAM] tf.one_hot / gather would error or zero-fill; one-hot or NaN targets are a bug)."""

@@ -60,7 +60,7 @@ int dsdgp_ctx_destroy(dsdgp_ctx* ctx);
 int dsdgp_sync(dsdgp_ctx* ctx);
 /* HIP-event timing of the most recent launch of a named kernel class on the ctx stream (bench.py roofline):
  * enable, run, then read the accumulated milliseconds and launch count. name in
- * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate"}. */
+ * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration"}. */
 int dsdgp_prof_enable(dsdgp_ctx* ctx, int on);
 int dsdgp_prof_read(dsdgp_ctx* ctx, const char* name, double* total_ms, int64_t* launches, int reset);
 /* Kernel launches this library has enqueued in this process so far (all contexts; memsets / copies not counted): the difference
@@ -365,6 +365,40 @@ int dsdgp_eval_mixture(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const
  * DSDGP_ERR_UNSUPPORTED while quadrature sample weights are set (dsdgp_model_set_sample_weights). */
 int dsdgp_model_evaluate(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
                          const int64_t* zstride, uint64_t seed, double* rows_out, double* acc, int accumulate);
+
+/* Calibration of the predictive mixture of dgp.py:116-126: S Gaussians N(mean_s, var_s + noise_var) per (i, d), equally weighted, on
+ * caller-supplied mean / var ((S*n) x DY, row s*n + i, as dsdgp_model_propagate writes them).  With sig_s^2 = max(var_s + noise_var,
+ * DBL_MIN) and F(x) = (1/S) sum_s Phi((x - mean_s) / sig_s):
+ *
+ * dsdgp_mixture_quantiles: q_out (device, n x DY x P) = the roots of F(q) = probs[k] — the exact credible-interval ends that
+ * demos/using_natural_gradients.ipynb cell 9 estimates by np.percentile(samples, [10, 50, 90]) of 100 full-covariance draws, and that
+ * demos/demo_step_function.ipynb:83-85 and demos/priors.ipynb:1020 replace by mean +- 1.96 sqrt(var) of a single Gaussian.
+ * probs: HOST array of P probabilities, 0 < p < 1, 1 <= P <= 16, copied into the launch (no upload, no synchronisation).  Safeguarded
+ * Newton inside a bracket that holds the root, at most 128 steps per probability (at the cap: the bracket's midpoint). */
+int dsdgp_mixture_quantiles(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, int64_t n, int32_t S, int32_t DY,
+                            const double* probs, int32_t P, double* q_out);
+/* dsdgp_mixture_calibration: the scores of held-out targets Y (device, n x DY) under the same mixture (dgp.py:116-126; the host route is
+ * predict_y, two (S, N*, D) downloads and numpy).  Per (i, d): the probability integral transform u = F(y) and the continuous ranked
+ * probability score in closed form (Grimit et al. 2006), with A(m, s^2) = m (2 Phi(m/s) - 1) + 2 s phi(m/s):
+ *   CRPS = (1/S) sum_s A(y - mean_s, sig_s^2) - (1/(2 S^2)) sum_s sum_t A(mean_s - mean_t, sig_s^2 + sig_t^2).
+ *   rows_out (device, n x DY x 2, or NULL): [u, CRPS] per (i, d).
+ *   acc (device, (2 + P)*DY doubles): acc[d] = sum_i CRPS, acc[DY + d] = n, acc[(2 + k)*DY + d] = the number of rows with u <= probs[k]
+ *            (exact integers) — overwritten, or added to when accumulate != 0 (batches; data-parallel ranks).
+ * Fixed-order reductions: the same inputs and n give the same bits.  DSDGP_ERR_BAD_ARG for a probability outside (0, 1), P outside
+ * 1..16 or a negative noise_var. */
+int dsdgp_mixture_calibration(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* Y, int64_t n,
+                              int32_t S, int32_t DY, const double* probs, int32_t P, double* rows_out, double* acc, int accumulate);
+/* The same on a model's own predictions: the forward pass exactly as dsdgp_model_evaluate runs it (same kernels, same Philox draws from
+ * `seed`, same `zs` injection, only the last layer's mean and variance kept, in the workspace), then the primitive on the same stream —
+ * one batch of what demos/using_natural_gradients.ipynb cell 9, demos/demo_step_function.ipynb:83-85 and demos/priors.ipynb:1020 do on
+ * the host.  level 0: the latent f (noise 0), every likelihood; level 1: the predictive y, noise = the Gaussian likelihood's variance
+ * read from the model's device copy.  DSDGP_ERR_UNSUPPORTED for level 1 / dsdgp_model_calibration with any other likelihood, and while
+ * quadrature sample weights are set (dsdgp_model_set_sample_weights). */
+int dsdgp_model_quantiles(dsdgp_model* m, const double* X, int64_t n, int32_t S, const double* const* zs, const int64_t* zstride,
+                          uint64_t seed, int32_t level, const double* probs, int32_t P, double* q_out);
+int dsdgp_model_calibration(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                            const int64_t* zstride, uint64_t seed, const double* probs, int32_t P, double* rows_out, double* acc,
+                            int accumulate);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);

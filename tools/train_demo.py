@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Sanity run of the whole training loop on the cfg-2 workload (synthetic kin8nm-shaped data): Adam on everything with
-natural-gradient steps on the last layer interleaved (demo_regression_UCI.ipynb:360-366), ELBO, test log-likelihood and test RMSE
-printed as it goes.  Usage: python tools/train_demo.py [steps]"""
+natural-gradient steps on the last layer interleaved (demo_regression_UCI.ipynb:360-366), ELBO, test log-likelihood, test RMSE,
+CRPS and the coverage of the 95 % predictive interval printed as it goes.  Usage: python tools/train_demo.py [steps]"""
 import os
 import sys
 import time
@@ -31,7 +31,9 @@ def main(steps):
         elbo = model.train_step(0.01, sync=(it % 250 == 0))
         if it % 250 == 0:
             ev = model.evaluate(Xs, Ys, 50)      # held-out scores reduced on the device (run_regression.py:108-123)
-            print(f"step {it:5d}  elbo {elbo:12.3f}  test log-lik {ev['log_density']:8.4f}  test rmse {ev['rmse']:7.4f}  lik var {float(model.likelihood.likelihood.variance.value):.4f}"
+            cal = model.calibration(Xs, Ys, 50, probs=(0.025, 0.5, 0.975))      # CRPS and the 95 % interval's coverage, on the device
+            print(f"step {it:5d}  elbo {elbo:12.3f}  test log-lik {ev['log_density']:8.4f}  test rmse {ev['rmse']:7.4f}  crps {cal['crps']:7.4f}"
+                  f"  cover95 {min(cal['coverage'].values()):6.4f}  lik var {float(model.likelihood.likelihood.variance.value):.4f}"
                   f"  {it / (time.perf_counter() - t0):7.1f} it/s", flush=True)
 
 
