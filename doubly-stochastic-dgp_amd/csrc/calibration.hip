@@ -15,9 +15,8 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "mixture_common.hpp"
 
-#define CAL_T 256         // threads of a workgroup
 #define CAL_CAP 8         // components per lane staged in LDS as (mu, sig); later ones are read from global memory every time
 #define CAL_MAXP 16       // probabilities per call
 #define CAL_MAXIT 128     // root-finder steps per probability: bisection alone takes a bracket of 2^20 sig down to one ulp in ~75
@@ -47,17 +46,7 @@ __device__ __forceinline__ double cal_A(double m, double s) {      // A(m, s^2),
   return m * erf(z * CAL_RSQRT2) + s * CAL_SQRT2_PI * exp(-0.5 * z * z);
 }
 
-// sums / extrema over the SPLIT adjacent lanes that share an item (butterfly; both partners evaluate the same expression, so every
-// lane of the group ends with the same bits)
-template <int SPLIT>
-__device__ __forceinline__ double cal_fold_sum(double x, int sub) {
-#pragma unroll
-  for (int off = 1; off < SPLIT; off <<= 1) {
-    const double o = __shfl_xor(x, off);
-    x = (sub & off) ? o + x : x + o;
-  }
-  return x;
-}
+// fold_sum's butterfly for the extrema
 template <int SPLIT>
 __device__ __forceinline__ double cal_fold_min(double x) {
 #pragma unroll
@@ -72,18 +61,18 @@ __device__ __forceinline__ double cal_fold_max(double x) {
 }
 
 // MODE 0: quantiles.  MODE 1: PIT, CRPS and their sums.
-// Threads map to consecutive flat (i, d) items, SPLIT adjacent lanes per item; lane `sub` owns the components s = sub + c SPLIT,
-// c = 0, 1, ...  The first CAL_CAP of them live in the lane's own LDS column as (mu, sig).
+// Lane `sub` of an item owns the components s = sub + c SPLIT, c = 0, 1, ...  The first CAL_CAP of them live in the lane's own LDS
+// column as (mu, sig).
 template <int MODE, int SPLIT>
-__global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
-  constexpr int JPB = CAL_T / SPLIT;      // items of a workgroup
-  __shared__ double lmu[CAL_CAP * CAL_T];
-  __shared__ double lsg[CAL_CAP * CAL_T];
+__global__ __launch_bounds__(MIX_T) void k_calibration(const CalArgs a) {
+  constexpr int JPB = MixItem<SPLIT>::JPB;
+  __shared__ double lmu[CAL_CAP * MIX_T];
+  __shared__ double lsg[CAL_CAP * MIX_T];
   __shared__ double ent[MODE == 1 ? 3 * JPB : 1];
-  const int tid = threadIdx.x, sub = tid % SPLIT, jl = tid / SPLIT;
-  const int64_t j0 = (int64_t)blockIdx.x * JPB, j = j0 + jl;
-  const bool live = j < a.total;
-  const int64_t jc = live ? j : a.total - 1;      // (every lane takes part in the folds)
+  const MixItem<SPLIT> it(a.total);
+  const int tid = threadIdx.x, sub = it.sub, jl = it.jl;
+  const int64_t j0 = it.j0, jc = it.jc;
+  const bool live = it.live;
   const int S = a.S;
   const int64_t ts = a.total;                     // stride between components
   const double noise = a.noise_dev ? a.noise_dev[0] : a.noise;
@@ -94,16 +83,16 @@ __global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
 
   for (int c = 0; c < nst; ++c) {
     const int64_t s = sub + (int64_t)c * SPLIT;
-    lmu[c * CAL_T + tid] = mp[s * ts];
-    lsg[c * CAL_T + tid] = sqrt(fmax(vp[s * ts] + noise, DBL_MIN));
+    lmu[c * MIX_T + tid] = mp[s * ts];
+    lsg[c * MIX_T + tid] = sqrt(fmax(vp[s * ts] + noise, DBL_MIN));
   }
   __syncthreads();      // (the pair sum reads the other lanes' columns)
 
   // component c of this lane
   auto own = [&](int c, double& mu, double& sg) {
     if (c < CAL_CAP) {
-      mu = lmu[c * CAL_T + tid];
-      sg = lsg[c * CAL_T + tid];
+      mu = lmu[c * MIX_T + tid];
+      sg = lsg[c * MIX_T + tid];
     } else {
       const int64_t s = sub + (int64_t)c * SPLIT;
       mu = mp[s * ts];
@@ -139,8 +128,8 @@ __global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
           F += 0.5 * erfc(-z * CAL_RSQRT2);
           f += CAL_RSQRT2PI * exp(-0.5 * z * z) / sg;
         }
-        F = cal_fold_sum<SPLIT>(F, sub) / (double)S;
-        f = cal_fold_sum<SPLIT>(f, sub) / (double)S;
+        F = fold_sum<SPLIT>(F, sub) / (double)S;
+        f = fold_sum<SPLIT>(f, sub) / (double)S;
         if (!done) {
           const double g = F - p;
           if (g == 0.0) {
@@ -197,8 +186,8 @@ __global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
     {
       const int c = s / SPLIT, o = s % SPLIT;
       if (c < CAL_CAP) {
-        ms = lmu[c * CAL_T + gbase + o];
-        ss = lsg[c * CAL_T + gbase + o];
+        ms = lmu[c * MIX_T + gbase + o];
+        ss = lsg[c * MIX_T + gbase + o];
       } else {
         ms = mp[(int64_t)s * ts];
         ss = sqrt(fmax(vp[(int64_t)s * ts] + noise, DBL_MIN));
@@ -208,8 +197,8 @@ __global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
       double mt, st;
       const int c = t / SPLIT, o = t % SPLIT;
       if (c < CAL_CAP) {
-        mt = lmu[c * CAL_T + gbase + o];
-        st = lsg[c * CAL_T + gbase + o];
+        mt = lmu[c * MIX_T + gbase + o];
+        st = lsg[c * MIX_T + gbase + o];
       } else {
         mt = mp[(int64_t)t * ts];
         st = sqrt(fmax(vp[(int64_t)t * ts] + noise, DBL_MIN));
@@ -217,10 +206,10 @@ __global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
       pr += cal_A(ms - mt, sqrt(ss * ss + st * st));
     }
   }
-  u = cal_fold_sum<SPLIT>(u, sub) * invS;
-  t1 = cal_fold_sum<SPLIT>(t1, sub);
-  diag = cal_fold_sum<SPLIT>(diag, sub);
-  pr = cal_fold_sum<SPLIT>(pr, sub);
+  u = fold_sum<SPLIT>(u, sub) * invS;
+  t1 = fold_sum<SPLIT>(t1, sub);
+  diag = fold_sum<SPLIT>(diag, sub);
+  pr = fold_sum<SPLIT>(pr, sub);
   // diagonal terms A(0, 2 sig^2) = 2 sig / sqrt(pi); off-diagonal pairs counted twice
   const double crps = t1 * invS - 0.5 * invS * invS * (2.0 * pr + 2.0 * CAL_RSQRTPI * diag);
   if (a.rows && live && sub == 0) {
@@ -235,47 +224,26 @@ __global__ __launch_bounds__(CAL_T) void k_calibration(const CalArgs a) {
   }
   __syncthreads();
   const int ND = a.DY, Q = 2 + a.P;
-  for (int p = tid; p < Q * ND; p += CAL_T) {
+  for (int p = tid; p < Q * ND; p += MIX_T) {
     const int d = p % ND, q = p / ND;
     const double pk = q >= 2 ? a.probs[q - 2] : 0.0;
-    double t = 0.0;
-    for (int e = (int)(((int64_t)d + ND - j0 % ND) % ND); e < JPB; e += ND) {
-      if (q == 0) t += ent[e];
-      else if (q == 1) t += ent[JPB + e];
-      else t += (ent[JPB + e] != 0.0 && ent[2 * JPB + e] <= pk) ? 1.0 : 0.0;
-    }
-    a.part[(int64_t)(q * ND + d) * a.nblocks + blockIdx.x] = t;
-  }
-}
-
-// second stage: acc[q DY + d] (+)= sum over the workgroups' partials, one wave per entry: lane-strided partial sums, then the wave sum
-// (both in a fixed order for a given number of workgroups)
-__global__ __launch_bounds__(CAL_T) void k_calibration_finish(const double* __restrict__ part, int nblocks, int entries, int accumulate,
-                                                              double* __restrict__ acc) {
-  const int lane = threadIdx.x & 63, wave = DS_WAVE_ID(threadIdx.x);
-  for (int p = blockIdx.x * (CAL_T / 64) + wave; p < entries; p += gridDim.x * (CAL_T / 64)) {
-    double t = 0.0;
-    for (int b = lane; b < nblocks; b += 64) t += part[(int64_t)p * nblocks + b];
-    t = sum_wave(t);
-    if (lane == 0) acc[p] = accumulate ? acc[p] + t : t;
+    a.part[(int64_t)(q * ND + d) * a.nblocks + blockIdx.x] = sum_output_items(d, ND, j0, 0, JPB, [&](int e) {
+      return q == 0 ? ent[e] : q == 1 ? ent[JPB + e] : (ent[JPB + e] != 0.0 && ent[2 * JPB + e] <= pk) ? 1.0 : 0.0;
+    });
   }
 }
 
 template <int MODE>
-static void cal_launch_split(int split, int nblocks, hipStream_t st, const CalArgs& a) {
-  if (split == 16) DS_LAUNCH((k_calibration<MODE, 16>), dim3(nblocks), dim3(CAL_T), 0, st, a);
-  else if (split == 8) DS_LAUNCH((k_calibration<MODE, 8>), dim3(nblocks), dim3(CAL_T), 0, st, a);
-  else if (split == 4) DS_LAUNCH((k_calibration<MODE, 4>), dim3(nblocks), dim3(CAL_T), 0, st, a);
-  else DS_LAUNCH((k_calibration<MODE, 1>), dim3(nblocks), dim3(CAL_T), 0, st, a);
+static void cal_launch(int split, int nblocks, hipStream_t st, const CalArgs& a) {
+  mix_dispatch_split(split, [&](auto sp) { DS_LAUNCH((k_calibration<MODE, decltype(sp)::value>), dim3(nblocks), dim3(MIX_T), 0, st, a); });
 }
 
-// Lanes per item: by the item count as eval_split of evaluate.hip does (one lane from 32768 items on, else 4 / 8 / 16), raised until
-// the lanes' LDS columns hold every component (S <= CAL_CAP x lanes) where 16 lanes can, and never more lanes than components.
+// Lanes per item: by the item count, raised until the lanes' LDS columns hold every component (S <= CAL_CAP x lanes) where 16 lanes
+// can, and never more lanes than components.
 static int cal_split(int64_t total, int S) {
-  int split = total >= 32768 ? 1 : total >= 8192 ? 4 : total >= 4096 ? 8 : 16;
+  int split = mix_split_by_items(total);
   while (split < 16 && S > CAL_CAP * split) split = (split == 1) ? 4 : split * 2;
-  while (split > 1 && split > S) split = (split == 4) ? 1 : split / 2;
-  return split;
+  return mix_split_clamp(split, S);
 }
 
 static double cal_Phi(double z) { return 0.5 * erfc(-z * CAL_RSQRT2); }
@@ -328,12 +296,10 @@ int mixture_quantiles_launch(dsdgp_ctx* ctx, const double* mean, const double* v
   DS_TRY(cal_fill("dsdgp_mixture_quantiles", ctx, mean, var, noise_var, noise_dev, n, S, DY, probs, P, a));
   DS_CHECK_ARG(q_out != nullptr);
   const int split = cal_split(a.total, S);
-  const int64_t nb64 = (a.total + CAL_T / split - 1) / (CAL_T / split);
-  DS_CHECK_ARG(nb64 <= 0x7fffffff);
+  DS_TRY(mix_nblocks(a.total, split, &a.nblocks));
   a.q_out = q_out;
-  a.nblocks = (int)nb64;
   ProfScope prof(ctx, "calibration");
-  cal_launch_split<0>(split, a.nblocks, ctx->stream, a);
+  cal_launch<0>(split, a.nblocks, ctx->stream, a);
   DS_HIP(hipGetLastError());
   return DSDGP_OK;
 }
@@ -345,16 +311,15 @@ int mixture_calibration_launch(dsdgp_ctx* ctx, const double* mean, const double*
   DS_TRY(cal_fill("dsdgp_mixture_calibration", ctx, mean, var, noise_var, noise_dev, n, S, DY, probs, P, a));
   DS_CHECK_ARG(Y && acc);
   const int split = cal_split(a.total, S);
-  const int64_t nb64 = (a.total + CAL_T / split - 1) / (CAL_T / split);
-  DS_CHECK_ARG(nb64 <= 0x7fffffff);
-  const int nblocks = (int)nb64, entries = (2 + P) * DY;
+  int nblocks;
+  DS_TRY(mix_nblocks(a.total, split, &nblocks));
+  const int entries = (2 + P) * DY;
   void* scr;
   DS_TRY(ctx_scratch(ctx, (size_t)round_up((int64_t)entries * nblocks, 32) * sizeof(double), &scr));
   a.Y = Y; a.rows = rows_out; a.part = (double*)scr; a.nblocks = nblocks;
   ProfScope prof(ctx, "calibration");
-  cal_launch_split<1>(split, nblocks, ctx->stream, a);
-  DS_LAUNCH(k_calibration_finish, dim3(ceil_div(entries, CAL_T / 64)), dim3(CAL_T), 0, ctx->stream, (const double*)scr, nblocks, entries,
-            accumulate, acc);
+  cal_launch<1>(split, nblocks, ctx->stream, a);
+  mixture_finish_launch(ctx->stream, (const double*)scr, nblocks, entries, DY, DY, accumulate, acc);
   DS_HIP(hipGetLastError());
   return DSDGP_OK;
 }

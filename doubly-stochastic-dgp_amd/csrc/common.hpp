@@ -83,6 +83,19 @@ int ctx_scratch(dsdgp_ctx* ctx, size_t bytes, void** out);
 // asynchronous upload of a small host object to device memory `dst` on the ctx stream (the host copy may die on return)
 int ctx_upload(dsdgp_ctx* ctx, void* dst, const void* src, size_t bytes);
 
+// launchers that one translation unit defines and others call
+int multiclass_launch(dsdgp_ctx* ctx, const double* mean, const double* var, const double* Y, int64_t n, int64_t R, int K,
+                      int mode, double wgt, double* out, double* dmean, double* dvar, int y_override);      // multiclass.hip
+bool lik_quad_kind_ok(int kind, double p0, double p1);                                                      // elementwise.hip
+// p0_dev / noise_dev != NULL: the likelihood's positive parameter is read on the device (a model's own copy); p0 / noise_var is ignored
+int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const double* p0_dev, const double* mean, const double* var,
+                        const double* Y, int64_t n, int S, int DY, double* rows_out, double* acc, int accumulate);      // evaluate.hip
+int mixture_quantiles_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
+                             int64_t n, int S, int DY, const double* probs, int P, double* q_out);      // calibration.hip
+int mixture_calibration_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
+                               const double* Y, int64_t n, int S, int DY, const double* probs, int P, double* rows_out, double* acc,
+                               int accumulate);
+
 // RAII-ish profiling bracket: records HIP events on the ctx stream around a launch when profiling is enabled.
 struct ProfScope {
   dsdgp_ctx* ctx;

@@ -6,13 +6,8 @@
 // five quadrature likelihoods) and multiclass_launch (MultiClass); only the Gaussian's closed form is written here.
 // Memory-bound: 2 S n DY doubles read once; nothing but the partial sums is written unless the per-row values are asked for.
 // Every reduction runs in a fixed order: the same inputs and batch size give the same bits.
-#include "common.hpp"
+#include "mixture_common.hpp"
 
-int multiclass_launch(dsdgp_ctx* ctx, const double* mean, const double* var, const double* Y, int64_t n, int64_t R, int K,
-                      int mode, double wgt, double* out, double* dmean, double* dvar, int y_override);
-bool lik_quad_kind_ok(int kind, double p0, double p1);
-
-#define EV_T 256          // threads of a workgroup
 #define EV_NSEG 8         // segments of the in-workgroup sums
 #define EV_DFAST 32       // outputs up to which the in-workgroup sums run in two levels
 
@@ -66,16 +61,7 @@ __device__ __forceinline__ void eval_component(int kind, double mu, double v, do
   }
 }
 
-// the sums of a row's components over the SPLIT adjacent lanes that share it (butterfly; afterwards every lane of the group holds them)
-template <int SPLIT>
-__device__ __forceinline__ double fold_sum(double x, int sub) {
-#pragma unroll
-  for (int off = 1; off < SPLIT; off <<= 1) {
-    const double o = __shfl_xor(x, off);
-    x = (sub & off) ? o + x : x + o;
-  }
-  return x;
-}
+// fold_sum's butterfly for the (maximum, sum) pairs
 template <int SPLIT>
 __device__ __forceinline__ void fold_lse(double& mx, double& sm, int sub) {
 #pragma unroll
@@ -86,17 +72,15 @@ __device__ __forceinline__ void fold_lse(double& mx, double& sm, int sub) {
   }
 }
 
-// Threads map to consecutive flat (i, d) items, SPLIT adjacent lanes per item: lane `sub` of an item takes the components
-// s = sub, sub + SPLIT, ...  (SPLIT = 1: one thread per item, every s one coalesced row of loads).
 template <int LIK, int SPLIT>
-__global__ __launch_bounds__(EV_T) void k_eval_mix(const EvalArgs a) {
-  constexpr int JPB = EV_T / SPLIT;      // items of a workgroup
+__global__ __launch_bounds__(MIX_T) void k_eval_mix(const EvalArgs a) {
+  constexpr int JPB = MixItem<SPLIT>::JPB;
   __shared__ double ent[3 * JPB];
   __shared__ double seg[3 * EV_DFAST * EV_NSEG];
-  const int tid = threadIdx.x, sub = tid % SPLIT, jl = tid / SPLIT;
-  const int64_t j0 = (int64_t)blockIdx.x * JPB, j = j0 + jl;
-  const bool live = j < a.total;
-  const int64_t jc = live ? j : a.total - 1;      // (every lane takes part in the folds)
+  const MixItem<SPLIT> it(a.total);
+  const int tid = threadIdx.x, sub = it.sub, jl = it.jl;
+  const int64_t j0 = it.j0, jc = it.jc;
+  const bool live = it.live;
   const int S = a.S;
   const double invS = 1.0 / (double)S, logS = log((double)S);
   double err, ell;
@@ -184,61 +168,30 @@ __global__ __launch_bounds__(EV_T) void k_eval_mix(const EvalArgs a) {
   const int ND = (LIK == 1) ? 1 : a.DY;      // outputs with sums of their own (MultiClass: one)
   if (ND <= EV_DFAST) {
     constexpr int SL = JPB / EV_NSEG;
-    for (int p = tid; p < 3 * ND * EV_NSEG; p += EV_T) {
+    for (int p = tid; p < 3 * ND * EV_NSEG; p += MIX_T) {
       const int g = p % EV_NSEG, qd = p / EV_NSEG, d = qd % ND, q = qd / ND;
-      const int first = g * SL + (int)(((int64_t)d + ND - (j0 + g * SL) % ND) % ND);
-      double t = 0.0;
-      for (int e = first; e < (g + 1) * SL; e += ND) t += ent[q * JPB + e];
-      seg[p] = t;
+      seg[p] = sum_output_items(d, ND, j0, g * SL, (g + 1) * SL, [&](int e) { return ent[q * JPB + e]; });
     }
     __syncthreads();
-    for (int p = tid; p < 3 * ND; p += EV_T) {
+    for (int p = tid; p < 3 * ND; p += MIX_T) {
       double t = 0.0;
 #pragma unroll
       for (int g = 0; g < EV_NSEG; ++g) t += seg[p * EV_NSEG + g];
       a.part[(int64_t)((p / ND) * a.DY + p % ND) * a.nblocks + blockIdx.x] = t;
     }
   } else {
-    for (int p = tid; p < 3 * ND; p += EV_T) {
+    for (int p = tid; p < 3 * ND; p += MIX_T) {
       const int d = p % ND, q = p / ND;
-      double t = 0.0;
-      for (int e = (int)(((int64_t)d + ND - j0 % ND) % ND); e < JPB; e += ND) t += ent[q * JPB + e];
-      a.part[(int64_t)(q * a.DY + d) * a.nblocks + blockIdx.x] = t;
+      a.part[(int64_t)(q * a.DY + d) * a.nblocks + blockIdx.x] = sum_output_items(d, ND, j0, 0, JPB, [&](int e) { return ent[q * JPB + e]; });
     }
   }
 }
 
-// second stage: acc[q DY + d] (+)= sum over the workgroups' partials, one wave per entry: lane-strided partial sums, then the wave sum
-// (both in a fixed order for a given number of workgroups).  Entries without sums of their own (MultiClass, d > 0) are zeroed.
-__global__ __launch_bounds__(EV_T) void k_eval_finish(const double* __restrict__ part, int nblocks, int DY, int ND, int accumulate,
-                                                      double* __restrict__ acc) {
-  const int lane = threadIdx.x & 63, wave = DS_WAVE_ID(threadIdx.x);
-  for (int p = blockIdx.x * (EV_T / 64) + wave; p < 3 * DY; p += gridDim.x * (EV_T / 64)) {
-    double t = 0.0;
-    if (p % DY < ND)
-      for (int b = lane; b < nblocks; b += 64) t += part[(int64_t)p * nblocks + b];
-    t = sum_wave(t);
-    if (lane == 0) acc[p] = accumulate ? acc[p] + t : t;
-  }
-}
-
 template <int LIK>
-static void eval_launch_split(int split, int nblocks, hipStream_t st, const EvalArgs& a) {
-  if (split == 16) DS_LAUNCH((k_eval_mix<LIK, 16>), dim3(nblocks), dim3(EV_T), 0, st, a);
-  else if (split == 8) DS_LAUNCH((k_eval_mix<LIK, 8>), dim3(nblocks), dim3(EV_T), 0, st, a);
-  else if (split == 4) DS_LAUNCH((k_eval_mix<LIK, 4>), dim3(nblocks), dim3(EV_T), 0, st, a);
-  else DS_LAUNCH((k_eval_mix<LIK, 1>), dim3(nblocks), dim3(EV_T), 0, st, a);
+static void eval_launch(int split, int nblocks, hipStream_t st, const EvalArgs& a) {
+  mix_dispatch_split(split, [&](auto sp) { DS_LAUNCH((k_eval_mix<LIK, decltype(sp)::value>), dim3(nblocks), dim3(MIX_T), 0, st, a); });
 }
 
-// Lanes per item: one while the items alone fill the chip (256 CUs x 2048 threads = 2^19 resident lanes at most; 2^15 items already
-// keep every CU busy), else 4, 8 or 16 so that a batch of ~1000 rows still spreads over the CUs — and never more lanes than components.
-static int eval_split(int64_t total, int S) {
-  int split = total >= 32768 ? 1 : total >= 8192 ? 4 : total >= 4096 ? 8 : 16;
-  while (split > 1 && split > S) split = (split == 4) ? 1 : split / 2;
-  return split;
-}
-
-// p0_dev != NULL: the likelihood's positive parameter is read on the device (a model's own copy); p0 is then ignored
 int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const double* p0_dev, const double* mean, const double* var,
                         const double* Y, int64_t n, int S, int DY, double* rows_out, double* acc, int accumulate) {
   DS_CHECK_ARG(ctx && mean && var && Y && acc && n > 0 && S > 0 && DY > 0);
@@ -254,10 +207,9 @@ int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const do
   }
   const bool mc = kind == DSDGP_LIK_MULTICLASS;
   const int64_t total = mc ? n : n * DY;
-  const int split = eval_split(total, S);
-  const int64_t nb64 = (total + EV_T / split - 1) / (EV_T / split);
-  DS_CHECK_ARG(nb64 <= 0x7fffffff);
-  const int nblocks = (int)nb64;
+  const int split = mix_split_clamp(mix_split_by_items(total), S);
+  int nblocks;
+  DS_TRY(mix_nblocks(total, split, &nblocks));
   const int64_t R = (int64_t)S * n;
   const size_t part_doubles = (size_t)round_up((int64_t)3 * DY * nblocks, 32);
   void* scr;
@@ -272,16 +224,16 @@ int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const do
     DS_TRY(multiclass_launch(ctx, mean, var, Y, n, R, DY, 1, 0.0, T, nullptr, nullptr, -1));
     for (int k = 0; k < DY; ++k) DS_TRY(multiclass_launch(ctx, mean, var, nullptr, R, R, DY, 1, 0.0, T + (int64_t)(1 + k) * R, nullptr, nullptr, k));
     a.T = T;
-    eval_launch_split<1>(split, nblocks, ctx->stream, a);
+    eval_launch<1>(split, nblocks, ctx->stream, a);
   } else if (kind == DSDGP_LIK_GAUSSIAN) {
-    eval_launch_split<0>(split, nblocks, ctx->stream, a);
+    eval_launch<0>(split, nblocks, ctx->stream, a);
   } else if (kind == DSDGP_LIK_BERNOULLI) {
-    eval_launch_split<2>(split, nblocks, ctx->stream, a);
+    eval_launch<2>(split, nblocks, ctx->stream, a);
   } else {
-    eval_launch_split<3>(split, nblocks, ctx->stream, a);
+    eval_launch<3>(split, nblocks, ctx->stream, a);
   }
-  DS_LAUNCH(k_eval_finish, dim3(ceil_div(3 * DY, EV_T / 64)), dim3(EV_T), 0, ctx->stream, (const double*)scr, nblocks, DY, mc ? 1 : DY,
-            accumulate, acc);
+  // (MultiClass: one output has sums of its own)
+  mixture_finish_launch(ctx->stream, (const double*)scr, nblocks, 3 * DY, DY, mc ? 1 : DY, accumulate, acc);
   DS_HIP(hipGetLastError());
   return DSDGP_OK;
 }

@@ -6,8 +6,6 @@
 #include <stdlib.h>
 #include <hip/hip_ext.h>
 
-int multiclass_launch(dsdgp_ctx* ctx, const double* mean, const double* var, const double* Y, int64_t n, int64_t R, int K,
-                      int mode, double wgt, double* out, double* dmean, double* dvar, int y_override);
 int gram_launch(dsdgp_ctx* ctx, int kind, const double* X, int64_t n, const double* X2, int64_t n2, int D,
                 const double* hyp_dev, double diag_add, int symmetric, double* out, int64_t ld);
 

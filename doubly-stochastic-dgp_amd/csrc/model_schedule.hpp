@@ -306,37 +306,12 @@ extern "C" int dsdgp_model_propagate(dsdgp_model* m, const double* X, int64_t n,
   return forward_layers(m, X, n, S, zs, zstride, seed, false, true, Fs, Fmeans, Fvars);
 }
 
-// Held-out evaluation (demos/run_regression.py:108-123 on dgp.py:116-126): the forward pass of dsdgp_model_propagate with only the last
-// layer's mean and variance wanted (they stay in the workspace), then the mixture reduction of evaluate.hip on them, on the same stream.
-// The likelihood's positive parameter is read from the model's own device copy: nothing goes through the host.
-int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const double* p0_dev, const double* mean, const double* var,
-                        const double* Y, int64_t n, int S, int DY, double* rows_out, double* acc, int accumulate);
-extern "C" int dsdgp_model_evaluate(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
-                                    const int64_t* zstride, uint64_t seed, double* rows_out, double* acc, int accumulate) {
-  DS_CHECK_ARG(m && X && Y && acc);
+// The front that the three mixture entries below share: their refusals, then the forward pass of dsdgp_model_propagate with only the
+// last layer's mean and variance wanted (they stay in the workspace; *last is that layer).  The reduction follows on the same stream and
+// reads the likelihood's positive parameter from the model's own device copy: nothing goes through the host.
+static int mixture_forward(const char* who, dsdgp_model* m, const double* X, int64_t n, int S, const double* const* zs,
+                           const int64_t* zstride, uint64_t seed, bool needs_gaussian, const LayerState** last) {
   DS_CHECK_ARG(!zs || zstride);
-  if (m->sample_w) {
-    dsdgp_set_error("dsdgp_model_evaluate: quadrature sample weights are set (dsdgp_model_set_sample_weights); the mixture is an unweighted mean");
-    return DSDGP_ERR_UNSUPPORTED;
-  }
-  if (!m->prepared) DS_TRY(prepare_async(m));
-  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
-  const LayerState& last = m->L[m->desc.L - 1];
-  const int kind = m->desc.lik_kind;
-  DS_CHECK_ARG(kind != DSDGP_LIK_MULTICLASS || last.dev.D_out == m->desc.num_classes);
-  return eval_mixture_launch(m->ctx, kind, 1.0, m->desc.lik_aux, lik_has_param(kind) ? m->lik_const : nullptr, last.mean, last.var, Y, n, S,
-                             last.dev.D_out, rows_out, acc, accumulate);
-}
-
-// Calibration of the predictive mixture (calibration.hip) on a model's own predictions: the forward pass exactly as dsdgp_model_evaluate
-// runs it, then the quantile / PIT + CRPS kernel on the workspace's mean and variance, on the same stream.  The Gaussian noise variance is
-// read from the model's device copy.
-int mixture_quantiles_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
-                             int64_t n, int S, int DY, const double* probs, int P, double* q_out);
-int mixture_calibration_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
-                               const double* Y, int64_t n, int S, int DY, const double* probs, int P, double* rows_out, double* acc,
-                               int accumulate);
-static int calibration_refusals(const char* who, dsdgp_model* m, bool needs_gaussian) {
   if (m->sample_w) {
     dsdgp_set_error("%s: quadrature sample weights are set (dsdgp_model_set_sample_weights); the mixture is an unweighted mean", who);
     return DSDGP_ERR_UNSUPPORTED;
@@ -346,31 +321,43 @@ static int calibration_refusals(const char* who, dsdgp_model* m, bool needs_gaus
                     m->desc.lik_kind);
     return DSDGP_ERR_UNSUPPORTED;
   }
+  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
+  *last = &m->L[m->desc.L - 1];
   return DSDGP_OK;
 }
+
+// Held-out evaluation (demos/run_regression.py:108-123 on dgp.py:116-126): the mixture reduction of evaluate.hip
+extern "C" int dsdgp_model_evaluate(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                                    const int64_t* zstride, uint64_t seed, double* rows_out, double* acc, int accumulate) {
+  DS_CHECK_ARG(m && X && Y && acc);
+  const LayerState* last;
+  DS_TRY(mixture_forward("dsdgp_model_evaluate", m, X, n, S, zs, zstride, seed, false, &last));
+  const int kind = m->desc.lik_kind;
+  DS_CHECK_ARG(kind != DSDGP_LIK_MULTICLASS || last->dev.D_out == m->desc.num_classes);
+  return eval_mixture_launch(m->ctx, kind, 1.0, m->desc.lik_aux, lik_has_param(kind) ? m->lik_const : nullptr, last->mean, last->var, Y, n,
+                             S, last->dev.D_out, rows_out, acc, accumulate);
+}
+
+// Calibration of the predictive mixture: the quantile / PIT + CRPS kernel of calibration.hip
 extern "C" int dsdgp_model_quantiles(dsdgp_model* m, const double* X, int64_t n, int32_t S, const double* const* zs,
                                      const int64_t* zstride, uint64_t seed, int32_t level, const double* probs, int32_t P,
                                      double* q_out) {
   DS_CHECK_ARG(m && X && probs && q_out);
-  DS_CHECK_ARG(!zs || zstride);
+  DS_CHECK_ARG(!zs || zstride);      // (here as well: a bad call keeps meeting this check before the one on level)
   DS_CHECK_ARG(level == 0 || level == 1);
-  DS_TRY(calibration_refusals("dsdgp_model_quantiles", m, level == 1));
-  if (!m->prepared) DS_TRY(prepare_async(m));
-  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
-  const LayerState& last = m->L[m->desc.L - 1];
-  return mixture_quantiles_launch(m->ctx, last.mean, last.var, 0.0, level == 1 ? m->lik_const : nullptr, n, S, last.dev.D_out, probs, P,
+  const LayerState* last;
+  DS_TRY(mixture_forward("dsdgp_model_quantiles", m, X, n, S, zs, zstride, seed, level == 1, &last));
+  return mixture_quantiles_launch(m->ctx, last->mean, last->var, 0.0, level == 1 ? m->lik_const : nullptr, n, S, last->dev.D_out, probs, P,
                                   q_out);
 }
 extern "C" int dsdgp_model_calibration(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
                                        const int64_t* zstride, uint64_t seed, const double* probs, int32_t P, double* rows_out,
                                        double* acc, int accumulate) {
   DS_CHECK_ARG(m && X && Y && probs && acc);
-  DS_CHECK_ARG(!zs || zstride);
-  DS_TRY(calibration_refusals("dsdgp_model_calibration", m, true));
-  if (!m->prepared) DS_TRY(prepare_async(m));
-  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
-  const LayerState& last = m->L[m->desc.L - 1];
-  return mixture_calibration_launch(m->ctx, last.mean, last.var, 0.0, m->lik_const, Y, n, S, last.dev.D_out, probs, P, rows_out, acc,
+  const LayerState* last;
+  DS_TRY(mixture_forward("dsdgp_model_calibration", m, X, n, S, zs, zstride, seed, true, &last));
+  return mixture_calibration_launch(m->ctx, last->mean, last->var, 0.0, m->lik_const, Y, n, S, last->dev.D_out, probs, P, rows_out, acc,
                                     accumulate);
 }
 

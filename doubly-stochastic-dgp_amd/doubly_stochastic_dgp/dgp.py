@@ -320,20 +320,13 @@ class DGP_Base(Parameterized):
         if zs is not None:
             if len(zs) != len(self.layers):
                 raise ValueError("zs needs one entry (or None) per layer")
-            zs = [z if z is None or hasattr(z, "data_ptr") else ctx.to_device(np.asarray(z, dtype=np.float64)) for z in zs]
+            zs = self._device_zs(ctx, zs)
             if any(z is not None and z.dim() != 3 for z in zs):
                 raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
         acc = ctx.empty(3, D)
         rows = ctx.empty(N, D, 3) if return_rows else None
-        keep = []
-        for a in range(0, N, batch_size):
-            b = min(a + batch_size, N)
-            zb = None
-            if zs is not None:      # the batch's rows of every draw that is not broadcast over rows
-                zb = [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
-            keep.append(eng.evaluate_batch(Xd[a:b], Yd[a:b], S, acc, a > 0, zs=zb, seed=self._draw_seed(),
-                                           rows=rows[a:b] if return_rows else None))
-        ctx.sync()
+        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.evaluate_batch(
+            Xd[a:b], Yd[a:b], S, acc, a > 0, zs=zb, seed=seed, rows=rows[a:b] if return_rows else None))
         sums = acc.cpu().numpy()
         cnt = float(sums[2].sum()) if not isinstance(self.likelihood.likelihood, MultiClass) else float(sums[2, 0])
         out = {"n": N}
@@ -391,6 +384,17 @@ class DGP_Base(Parameterized):
             return None
         return [z if z is None or hasattr(z, "data_ptr") else ctx.to_device(np.asarray(z, dtype=np.float64)) for z in zs]
 
+    def _over_row_batches(self, ctx, N, batch_size, zs, call):
+        """call(a, b, zb, seed) on the row batches [a, b) of N rows in order, then one synchronisation: zb = the batch's rows of every
+        draw of the device list `zs` that is not broadcast over rows, seed = one `_draw_seed()` per batch.  What the calls return (the
+        arrays their asynchronous launches read) is kept alive until the synchronisation."""
+        keep = []
+        for a in range(0, N, batch_size):
+            b = min(a + batch_size, N)
+            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
+            keep.append(call(a, b, zb, self._draw_seed()))
+        ctx.sync()
+
     def predict_quantiles(self, Xnew, num_samples, probs=(0.025, 0.5, 0.975), level="y", batch_size=1000, Y_std=1.0, Y_mean=0.0,
                           zs=None):
         """Quantiles of the predictive mixture of `num_samples` Gaussians (dgp.py:116-126), solved on the device: the (N*, D, P) array
@@ -409,12 +413,8 @@ class DGP_Base(Parameterized):
         zs = self._device_zs(ctx, zs)
         N, D, P = Xd.shape[0], self.layers[-1].num_outputs, probs.size
         q = ctx.empty(N, D, P)
-        keep = []
-        for a in range(0, N, batch_size):
-            b = min(a + batch_size, N)
-            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
-            keep.append(eng.quantiles_batch(Xd[a:b], S, probs, q[a:b], level=1 if level == "y" else 0, zs=zb, seed=self._draw_seed()))
-        ctx.sync()
+        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.quantiles_batch(
+            Xd[a:b], S, probs, q[a:b], level=1 if level == "y" else 0, zs=zb, seed=seed))
         return float(Y_mean) + Y_std * q.cpu().numpy()
 
     def calibration(self, Xs, Ys, num_samples, probs=(0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975), batch_size=1000, Y_std=1.0, zs=None,
@@ -434,13 +434,8 @@ class DGP_Base(Parameterized):
         N, D, P = Xd.shape[0], self.layers[-1].num_outputs, probs.size
         acc = ctx.empty(2 + P, D)
         rows = ctx.empty(N, D, 2) if return_rows else None
-        keep = []
-        for a in range(0, N, batch_size):
-            b = min(a + batch_size, N)
-            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
-            keep.append(eng.calibration_batch(Xd[a:b], Yd[a:b], S, probs, acc, a > 0, zs=zb, seed=self._draw_seed(),
-                                              rows=rows[a:b] if return_rows else None))
-        ctx.sync()
+        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.calibration_batch(
+            Xd[a:b], Yd[a:b], S, probs, acc, a > 0, zs=zb, seed=seed, rows=rows[a:b] if return_rows else None))
         out = calibration_scores(acc.cpu().numpy(), probs, Y_std)
         out["n"] = N
         if return_rows:

@@ -416,14 +416,19 @@ class Engine:
             raise _lib.CholeskyError(f"Cholesky decomposition was not successful (Kuu pivot {int(out[3])})")
         return out
 
+    def _mixture_batch_args(self, Xd, S, zs, Yd=None):
+        """What evaluate_batch, quantiles_batch and calibration_batch do ahead of their library call -> (n, zp, zst, keep)"""
+        n = Xd.shape[0]
+        if Yd is not None:
+            self._check_targets_shape(Yd, n)
+        self._ensure(n, S)
+        self._prepare_checked()
+        return (n, *self._zs_args(zs, S, n))
+
     def evaluate_batch(self, Xd, Yd, S, acc, accumulate, zs=None, seed=0, rows=None):
         """dsdgp_model_evaluate on one batch of device rows: forward pass + mixture reduction into the device accumulator `acc`
         (3 x D_out of the last layer; added to when `accumulate`), per-row values into `rows` (n, D_out, 3) if given.  Asynchronous."""
-        n = Xd.shape[0]
-        self._check_targets_shape(Yd, n)
-        self._ensure(n, S)
-        self._prepare_checked()
-        zp, zst, keep = self._zs_args(zs, S, n)
+        n, zp, zst, keep = self._mixture_batch_args(Xd, S, zs, Yd)
         _lib.check(self.lib.dsdgp_model_evaluate(self.model, ptr(Xd), ptr(Yd), n, S, zp, zst, C.c_uint64(seed), ptr(rows), ptr(acc),
                                                  int(bool(accumulate))))
         return keep
@@ -431,11 +436,8 @@ class Engine:
     def quantiles_batch(self, Xd, S, probs, q, level=1, zs=None, seed=0):
         """dsdgp_model_quantiles on one batch of device rows: forward pass + the mixture's quantiles at the host array `probs` into the
         device tensor `q` (n, D_out, P).  level 1: the predictive y (Gaussian likelihood), 0: the latent f.  Asynchronous."""
-        n = Xd.shape[0]
         probs = np.ascontiguousarray(probs, dtype=np.float64)
-        self._ensure(n, S)
-        self._prepare_checked()
-        zp, zst, keep = self._zs_args(zs, S, n)
+        n, zp, zst, keep = self._mixture_batch_args(Xd, S, zs)
         _lib.check(self.lib.dsdgp_model_quantiles(self.model, ptr(Xd), n, S, zp, zst, C.c_uint64(seed), int(level),
                                                   probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(q)))
         return keep
@@ -443,12 +445,8 @@ class Engine:
     def calibration_batch(self, Xd, Yd, S, probs, acc, accumulate, zs=None, seed=0, rows=None):
         """dsdgp_model_calibration on one batch of device rows: forward pass + PIT / CRPS reduction into the device accumulator `acc`
         ((2 + P) x D_out; added to when `accumulate`), per-row [u, CRPS] into `rows` (n, D_out, 2) if given.  Asynchronous."""
-        n = Xd.shape[0]
         probs = np.ascontiguousarray(probs, dtype=np.float64)
-        self._check_targets_shape(Yd, n)
-        self._ensure(n, S)
-        self._prepare_checked()
-        zp, zst, keep = self._zs_args(zs, S, n)
+        n, zp, zst, keep = self._mixture_batch_args(Xd, S, zs, Yd)
         _lib.check(self.lib.dsdgp_model_calibration(self.model, ptr(Xd), ptr(Yd), n, S, zp, zst, C.c_uint64(seed),
                                                     probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(rows), ptr(acc),
                                                     int(bool(accumulate))))

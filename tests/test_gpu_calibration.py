@@ -18,10 +18,7 @@ by S at 4, 8 and 16, raised by S past 8 components per lane at 8 | 9, 32 | 33, 6
 memory (16 lanes x 8: 128 | 129), one vs several workgroups (16 lanes: 16 | 17 items), P = 1 and P = 16.  The kernel has no unrolled
 component loop, hence no unroll remainder."""
 import ctypes as C
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -29,9 +26,9 @@ from numpy.testing import assert_allclose
 
 from tests import calibration_reference as R
 from tests.helpers import kern_spec, make_case
+from tests.mixture_cases import NS, _build_case, _case, run_child
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TOL = dict(rtol=1e-10, atol=1e-13)
 PROBS = (1e-6, 0.025, 0.25, 0.5, 0.75, 0.975, 1.0 - 1e-6)
@@ -375,39 +372,7 @@ def test_primitive_rejects_bad_arguments(ctx):
 
 
 # ---------------------------------------------------------------- model level
-NS, S_MAX = 37, 37
-_cases, _refs = {}, {}
-
-
-def _build_case(name):
-    """the small two-layer cases of tests/test_gpu_evaluate.py: D_in = 2, M = 16, inner width 2; (model, Xs, Ys, zs for S_MAX samples)"""
-    rng = np.random.RandomState(5)
-    N, D, M = 40, 2, 16
-    X = rng.randn(N, D)
-    Z = X[:M] + 0.01 * rng.randn(M, D)
-    kw, DY = {}, 2
-    if name == "rbf":
-        specs, Y, Ys = [kern_spec("rbf", D, 1.2, 0.9)] * 2, rng.randn(N, DY), rng.randn(NS, DY)
-    elif name == "matern_white":
-        DY = 1
-        specs, Y, Ys, kw = [kern_spec("matern52", D, 0.9, 1.1)] * 2, rng.randn(N, DY), rng.randn(NS, DY), dict(white=True)
-    elif name == "bernoulli":
-        specs, kw = [kern_spec("rbf", D, 1.2, 0.9)] * 2, dict(bernoulli=True)
-        Y, Ys = rng.choice([-1.0, 1.0], N * DY).reshape(N, DY), rng.choice([-1.0, 1.0], NS * DY).reshape(NS, DY)
-    else:
-        DY = 3
-        specs, kw = [kern_spec("rbf", D, 1.2, 0.9)] * 2, dict(num_classes=3)
-        Y, Ys = rng.randint(0, 3, size=(N, 1)).astype(np.float64), rng.randint(0, 3, size=(NS, 1)).astype(np.float64)
-    _, _, model = make_case(X, Y, Z, specs, lik_var=0.1, S=3, **kw)
-    Xs = rng.randn(NS, D)
-    zs = [rng.randn(S_MAX, NS, 2), rng.randn(S_MAX, NS, DY)]
-    return model, Xs, Ys, zs
-
-
-def _case(name):
-    if name not in _cases:
-        _cases[name] = _build_case(name)
-    return _cases[name]
+_refs = {}
 
 
 def _noise(model, level="y"):
@@ -621,17 +586,6 @@ def _bits_of_one_run():
             "pit_le": dig(out["pit_le"]), "same_as_primitive": same}
 
 
-def _child(env_extra):
-    env = dict(os.environ)
-    env.pop("DSDGP_FORCE", None)
-    env.pop("DSDGP_NO_OVERLAP", None)
-    env.update(env_extra)
-    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, os.path.join(ROOT, "doubly-stochastic-dgp_amd")], env=env, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
-
-
 def test_model_equals_the_primitive_bit_for_bit():
     """the default configuration, in this process"""
     got = _bits_of_one_run()
@@ -645,7 +599,7 @@ def test_model_bits_do_not_depend_on_the_forward_path(env):
     the same bits.  The GEMM-formulated chains sum in another order (tests/test_gpu_gemm_path.py), so their score is held to that file's
     chain-against-GEMM bound instead, rtol 1e-8."""
     base = _bits_of_one_run()
-    got = _child(env)
+    got = run_child(_CHILD, env)
     print("default", base, "\n", env, got)
     assert base["same_as_primitive"] and got["same_as_primitive"]
     if "DSDGP_NO_OVERLAP" in env:

@@ -12,20 +12,15 @@ Model level: DGP_Base.evaluate against the reference applied to the outputs of t
 numpy), with explicit draws and with device draws at the per-batch seeds of DGP_Base._draw_seed."""
 import ctypes as C
 import hashlib
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 from numpy.testing import assert_allclose
 
 from tests import evaluate_reference as R
-from tests.helpers import kern_spec, make_case
+from tests.mixture_cases import NS, _build_case, _case, run_child
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TOL = dict(rtol=1e-10, atol=1e-13)
 TOL_QUAD_DENSITY = dict(rtol=1e-11, atol=1e-13)      # tests/test_gpu_likelihoods.py, predict_density_logmeanexp of the primitives
@@ -211,40 +206,8 @@ def test_primitive_rejects_what_it_does_not_cover(ctx):
 
 
 # ---------------------------------------------------------------- model level
-NS, S_MAX = 37, 37
 MODELS = ["rbf", "matern_white", "bernoulli", "multiclass"]
-_cases, _refs = {}, {}
-
-
-def _build_case(name):
-    """two layers, D_in = 2, M = 16, inner width 2; (model, Xs, Ys, zs for S_MAX samples)"""
-    rng = np.random.RandomState(5)
-    N, D, M = 40, 2, 16
-    X = rng.randn(N, D)
-    Z = X[:M] + 0.01 * rng.randn(M, D)
-    kw, DY = {}, 2
-    if name == "rbf":
-        specs, Y, Ys = [kern_spec("rbf", D, 1.2, 0.9)] * 2, rng.randn(N, DY), rng.randn(NS, DY)
-    elif name == "matern_white":
-        DY = 1
-        specs, Y, Ys, kw = [kern_spec("matern52", D, 0.9, 1.1)] * 2, rng.randn(N, DY), rng.randn(NS, DY), dict(white=True)
-    elif name == "bernoulli":
-        specs, kw = [kern_spec("rbf", D, 1.2, 0.9)] * 2, dict(bernoulli=True)
-        Y, Ys = rng.choice([-1.0, 1.0], N * DY).reshape(N, DY), rng.choice([-1.0, 1.0], NS * DY).reshape(NS, DY)
-    else:
-        DY = 3
-        specs, kw = [kern_spec("rbf", D, 1.2, 0.9)] * 2, dict(num_classes=3)
-        Y, Ys = rng.randint(0, 3, size=(N, 1)).astype(np.float64), rng.randint(0, 3, size=(NS, 1)).astype(np.float64)
-    _, _, model = make_case(X, Y, Z, specs, lik_var=0.1, S=3, **kw)
-    Xs = rng.randn(NS, D)
-    zs = [rng.randn(S_MAX, NS, 2), rng.randn(S_MAX, NS, DY)]
-    return model, Xs, Ys, zs
-
-
-def _case(name):
-    if name not in _cases:
-        _cases[name] = _build_case(name)
-    return _cases[name]
+_refs = {}
 
 
 def _reference_from(model, Fm, Fv, Ys):
@@ -362,20 +325,9 @@ def _bits_of_one_run():
             "launches": int(Context.get().lib.dsdgp_launch_count())}
 
 
-def _child(env_extra):
-    env = dict(os.environ)
-    env.pop("DSDGP_FORCE", None)
-    env.pop("DSDGP_NO_OVERLAP", None)
-    env.update(env_extra)
-    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, os.path.join(ROOT, "doubly-stochastic-dgp_amd")], env=env, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
-
-
 @pytest.fixture(scope="module")
 def default_bits():
-    return _child({})
+    return run_child(_CHILD, {})
 
 
 @pytest.mark.parametrize("env", [{"DSDGP_NO_OVERLAP": "1"}, {"DSDGP_FORCE": "gemm_mp=16"}], ids=["no_overlap", "gemm"])
@@ -386,7 +338,7 @@ def test_evaluate_bits_do_not_depend_on_the_forward_path(default_bits, env):
     the default, so there the bits must agree outright; the GEMM-formulated chains sum in another order
     (tests/test_gpu_gemm_path.py asserts that their predictions differ from the chains' in the last bits), so their scores are held to
     that file's chain-against-GEMM bound instead, rtol 1e-8."""
-    got = _child(env)
+    got = run_child(_CHILD, env)
     print("default", default_bits, "\n", env, got)
     assert default_bits["same_as_primitive"] and got["same_as_primitive"]
     if "DSDGP_NO_OVERLAP" in env:
