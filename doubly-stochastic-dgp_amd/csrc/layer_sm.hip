@@ -26,7 +26,8 @@ static inline bool sm_small(int Mp, int64_t nblk, int D_in, bool bwd) {
   // launch with more runs in two rounds, the second one latency-bound on a third of the chip (config 2: 1250 blocks, 482 late
   // starters, 139 us).  The 4-wave instance with the paired d-loop (96 VGPRs, five workgroups per CU) keeps 1280 blocks resident with
   // the MFMA pipe saturated in the d-loop: 124 us.  (DSDGP_SM_BWD_LIM128: A/B aid.)
-  // tests/test_gpu_large_launch_m128.py runs both sides of both M = 128 thresholds (161 / 769 row blocks) against the oracle
+  // tests/test_gpu_large_launch_m128.py runs both sides of both M = 128 thresholds (161 / 769 row blocks) against the oracle;
+  // tests/test_gpu_wide_input.py both sides of D_in <= XCH (64 | 65 at Mp = 128: the 8-wave and the 4-wave instance of the same launch)
   static const int64_t bwd_lim128 = getenv("DSDGP_SM_BWD_LIM128") ? atoll(getenv("DSDGP_SM_BWD_LIM128")) : SM_BWD_RESIDENT_8W;
   const int64_t lim = Mp > 128 ? ((int64_t)1 << 40) : (bwd ? bwd_lim128 : SM_SMALL_BLOCKS);
   return Mp >= 128 && Mp <= 256 && nblk <= lim && D_in <= XCH;
