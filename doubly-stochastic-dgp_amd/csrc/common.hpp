@@ -95,6 +95,8 @@ int mixture_quantiles_launch(dsdgp_ctx* ctx, const double* mean, const double* v
 int mixture_calibration_launch(dsdgp_ctx* ctx, const double* mean, const double* var, double noise_var, const double* noise_dev,
                                const double* Y, int64_t n, int S, int DY, const double* probs, int P, double* rows_out, double* acc,
                                int accumulate);
+int mixture_classification_launch(dsdgp_ctx* ctx, int kind, const double* mean, const double* var, const double* Y, int64_t n, int S,
+                                  int DY, int bins, double* probs_out, double* rows_out, double* acc, int accumulate);      // classification.hip
 
 // RAII-ish profiling bracket: records HIP events on the ctx stream around a launch when profiling is enabled.
 struct ProfScope {

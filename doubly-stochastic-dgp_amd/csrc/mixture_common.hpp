@@ -1,4 +1,5 @@
-// What the reductions over the S mixture components of the (S, n, DY) last-layer means and variances share (evaluate.hip, calibration.hip):
+// What the reductions over the S mixture components of the (S, n, DY) last-layer means and variances share (evaluate.hip, calibration.hip,
+// classification.hip):
 // items -> threads, the sums over an item's lanes and per output, the second-stage kernel, the launch geometry.  Their math stays with them.
 #pragma once
 #include <type_traits>

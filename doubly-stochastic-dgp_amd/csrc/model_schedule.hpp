@@ -361,6 +361,23 @@ extern "C" int dsdgp_model_calibration(dsdgp_model* m, const double* X, const do
                                     accumulate);
 }
 
+// Classification report of the predictive mixture (MultiClass / Bernoulli): the probability and report kernels of classification.hip
+extern "C" int dsdgp_model_classification(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                                          const int64_t* zstride, uint64_t seed, int32_t bins, double* probs_out, double* rows_out,
+                                          double* acc, int accumulate) {
+  DS_CHECK_ARG(m && X && Y && acc);
+  const int kind = m->desc.lik_kind;
+  if (kind != DSDGP_LIK_MULTICLASS && kind != DSDGP_LIK_BERNOULLI) {
+    dsdgp_set_error("dsdgp_model_classification: likelihood kind %d has no classes; MultiClass and Bernoulli are covered", kind);
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  const LayerState* last;
+  DS_TRY(mixture_forward("dsdgp_model_classification", m, X, n, S, zs, zstride, seed, false, &last));
+  DS_CHECK_ARG(kind != DSDGP_LIK_MULTICLASS || last->dev.D_out == m->desc.num_classes);
+  return mixture_classification_launch(m->ctx, kind, last->mean, last->var, Y, n, S, last->dev.D_out, bins, probs_out, rows_out, acc,
+                                       accumulate);
+}
+
 // (re)build the split-K job lists for minibatch shape (n, S); uploaded once, reused by every step of that shape
 static int ensure_plan(dsdgp_model* m, int64_t n, int S) {
   if (m->plan_n == n && m->plan_S == S) return DSDGP_OK;

@@ -5,8 +5,9 @@
 // Four lanes per (sample,row), five quadrature nodes each; the 20 x K erf evaluations are ALU-bound; per-class gradient accumulators
 // sit in LDS.
 #include "common.hpp"
+#include "gauss_hermite.hpp"
 
-#define MC_H 20
+#define MC_H GH20_H
 #define MC_KMAX 32
 #define MC_T 64
 
@@ -16,20 +17,8 @@ static bool g_gh_ready = false;
 
 static int ensure_gh(hipStream_t st) {
   if (g_gh_ready) return DSDGP_OK;
-  // Gauss–Hermite nodes/weights, n = 20 (numpy.polynomial.hermite.hermgauss(20)); symmetric, listed once
-  static const double xpos[10] = {0.2453407083009012499, 0.7374737285453943587, 1.2340762153953230079, 1.7385377121165862068,
-                                  2.2549740020892756723, 2.7888060584281304806, 3.3478545673832163269, 3.9447640401156252104,
-                                  4.6036824495507442731, 5.3874808900112328620};
-  static const double wpos[10] = {4.6224366960061008965e-1, 2.8667550536283412972e-1, 1.0901720602002331250e-1,
-                                  2.4810520887463643070e-2, 3.2437733422378566463e-3, 2.2833863601635308670e-4,
-                                  7.8025564785320636941e-6, 1.0860693707692815356e-7, 4.3993409922731805536e-10,
-                                  2.2293936455341516100e-13};
   double x[MC_H], w[MC_H];
-  const double isp = 0.56418958354775628695;   // 1/sqrt(pi)
-  for (int i = 0; i < 10; ++i) {
-    x[10 + i] = xpos[i];  w[10 + i] = wpos[i] * isp;
-    x[9 - i] = -xpos[i];  w[9 - i] = wpos[i] * isp;
-  }
+  gh20_nodes(x, w);
   DS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_gh_x), x, sizeof(x), 0, hipMemcpyHostToDevice, st));
   DS_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(c_gh_w), w, sizeof(w), 0, hipMemcpyHostToDevice, st));
   DS_HIP(hipStreamSynchronize(st));

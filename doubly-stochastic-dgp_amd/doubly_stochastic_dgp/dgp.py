@@ -442,6 +442,107 @@ class DGP_Base(Parameterized):
             out["rows"] = rows.cpu().numpy()
         return out
 
+    # ------------------------------------------------------------------ classification report (MultiClass / Bernoulli)
+    MAX_BINS = 32
+
+    def _classification_args(self, X, Y, num_samples, bins, batch_size, zs):
+        """Everything classification_report can refuse without a device -> (kind, C, ND, S, bins, batch_size); called before
+        self.engine() is touched."""
+        kind, Cn = self.likelihood.classification_args("classification_report")
+        bins = int(bins)
+        if not 1 <= bins <= self.MAX_BINS:
+            raise ValueError(f"bins must lie in 1 .. {self.MAX_BINS}")
+        S, batch_size = int(num_samples), int(batch_size)
+        if batch_size < 1 or S < 1:
+            raise ValueError("batch_size and num_samples must be positive")
+        shape = lambda a: tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+        if len(shape(X)) != 2 or shape(X)[0] < 1:
+            raise ValueError("X must be a non-empty (N, D_in) array")
+        ND = self.layers[-1].num_outputs if self.likelihood.bernoulli else 1
+        want = (shape(X)[0], ND)
+        if shape(Y) != want:
+            raise ValueError(f"Ys has shape {shape(Y)}, expected {want}")
+        if zs is not None:
+            if len(zs) != len(self.layers):
+                raise ValueError("zs needs one entry (or None) per layer")
+            if any(z is not None and len(shape(z)) != 3 for z in zs):
+                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
+        if not hasattr(Y, "data_ptr"):
+            self.likelihood.check_targets(Y)
+        return kind, Cn, ND, S, bins, batch_size
+
+    def classification_report(self, Xs, Ys, num_samples, bins=10, batch_size=1000, zs=None, return_rows=False):
+        """Is the classifier calibrated, and which classes does it confuse?  Held-out labels scored under the mixture class probabilities
+        pi = mean over the `num_samples` components of the likelihood's predictive probabilities (MultiClass: C = K classes, Ys (N*, 1)
+        labels; Bernoulli: C = 2 per output, Ys (N*, D), class 1 where Ys == 1), on the device: over row batches of `batch_size` one
+        launch forms the probabilities of all classes and components, a second the report, added into one accumulator that is read
+        back once.  Xs / Ys: numpy arrays or device tensors.  zs as in `evaluate`; else one `_draw_seed()` per batch, in batch order.
+        Returns a dict: `n`; `error_rate` of argmax_c pi_c (ties: the lowest c); `log_density` = mean log pi_y (evaluate's);
+        `brier` = mean sum_c (pi_c - [c = y])^2 (the multi-class definition: a binary problem gives 2 (p - t)^2, twice the usual binary
+        score); `ece` = sum_b (n_b / n) |accuracy_b - confidence_b| over the non-empty ones of `bins` equal-width bins of the
+        confidence max_c pi_c, `mce` the largest such gap; `reliability` = {"edges" (B + 1,), "count", "confidence", "accuracy" (B,)},
+        nan in the last two where a bin is empty; `top_k_accuracy` (C,): the fraction of rows whose label is among the k + 1 most
+        probable classes; `confusion` (C, C) int64, [true, predicted]; `per_class` = {"recall", "precision", "support"}.  Bernoulli
+        with D > 1 outputs: the scalars pooled over outputs, `error_rate_per_output`, `log_density_per_output`, `brier_per_output`,
+        `ece_per_output`, `confusion` (D, 2, 2), the reliability and per_class arrays with a leading D.  With return_rows: `probs`
+        (N*, K) (Bernoulli: (N*, D), p(y = 1)) and `rows` (N*, ND, 4) = [predicted class, confidence, log pi_y, brier]."""
+        kind, Cn, ND, S, bins, batch_size = self._classification_args(Xs, Ys, num_samples, bins, batch_size, zs)
+        eng = self.engine()
+        ctx = eng.ctx
+        Xd = Xs.contiguous() if hasattr(Xs, "data_ptr") else ctx.to_device(Xs)
+        Yd = Ys.contiguous() if hasattr(Ys, "data_ptr") else ctx.to_device(Ys)
+        zs = self._device_zs(ctx, zs)
+        N, D = Xd.shape[0], self.layers[-1].num_outputs
+        acc = ctx.empty(4 + 3 * bins + Cn + Cn * Cn, ND)
+        probs = ctx.empty(N, D) if return_rows else None
+        rows = ctx.empty(N, ND, 4) if return_rows else None
+        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.classification_batch(
+            Xd[a:b], Yd[a:b], S, bins, acc, a > 0, zs=zb, seed=seed, probs=probs[a:b] if return_rows else None,
+            rows=rows[a:b] if return_rows else None))
+        out = classification_scores(acc.cpu().numpy(), bins, Cn)
+        out["n"] = N
+        if return_rows:
+            out["probs"] = probs.cpu().numpy()
+            out["rows"] = rows.cpu().numpy()
+        return out
+
+
+def classification_scores(sums, bins, C):
+    """The dict of DGP_Base.classification_report (without `n`, `probs` and `rows`) from the (4 + 3 bins + C + C^2, ND) accumulator of
+    dsdgp_mixture_classification."""
+    B, C = int(bins), int(C)
+    sums = np.asarray(sums, dtype=np.float64).reshape(4 + 3 * B + C + C * C, -1)
+    ND = sums.shape[1]
+    cnt = sums[3]
+    bc, bcf, bok = sums[4:4 + B], sums[4 + B:4 + 2 * B], sums[4 + 2 * B:4 + 3 * B]
+    rank = sums[4 + 3 * B:4 + 3 * B + C]
+    conf = np.rint(sums[4 + 3 * B + C:]).astype(np.int64).reshape(C, C, ND)
+
+    def reliability(bc, bcf, bok):      # bins on the leading axis
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cf, ok = np.where(bc > 0, bcf / bc, np.nan), np.where(bc > 0, bok / bc, np.nan)
+        gap = np.where(bc > 0, np.abs(ok - cf), 0.0)
+        return cf, ok, (bc / bc.sum(0) * gap).sum(0), gap.max(0)
+
+    cf, ok, ece, mce = reliability(bc.sum(1), bcf.sum(1), bok.sum(1))
+    out = {"error_rate": float(sums[0].sum() / cnt.sum()), "log_density": float(sums[1].sum() / cnt.sum()),
+           "brier": float(sums[2].sum() / cnt.sum()), "ece": float(ece), "mce": float(mce),
+           "top_k_accuracy": np.cumsum(rank.sum(1)) / cnt.sum()}
+    edges = np.arange(B + 1) / B
+    with np.errstate(divide="ignore", invalid="ignore"):
+        per_class = {"recall": np.einsum("ttd->dt", conf) / conf.sum(1).T, "precision": np.einsum("ttd->dt", conf) / conf.sum(0).T,
+                     "support": conf.sum(1).T}
+    if ND == 1:
+        out["reliability"] = {"edges": edges, "count": np.rint(bc[:, 0]).astype(np.int64), "confidence": cf, "accuracy": ok}
+        out["confusion"] = conf[..., 0]
+        out["per_class"] = {k: v[0] for k, v in per_class.items()}
+        return out
+    cfo, oko, eceo, _ = reliability(bc, bcf, bok)
+    out.update(error_rate_per_output=sums[0] / cnt, log_density_per_output=sums[1] / cnt, brier_per_output=sums[2] / cnt,
+               ece_per_output=eceo, confusion=np.ascontiguousarray(conf.transpose(2, 0, 1)), per_class=per_class,
+               reliability={"edges": edges, "count": np.rint(bc.T).astype(np.int64), "confidence": cfo.T, "accuracy": oko.T})
+    return out
+
 
 def calibration_scores(sums, probs, Y_std=1.0):
     """The dict of DGP_Base.calibration (without `n` and `rows`) from the (2 + P, D) accumulator of dsdgp_mixture_calibration."""

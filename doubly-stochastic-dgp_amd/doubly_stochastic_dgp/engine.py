@@ -417,7 +417,7 @@ class Engine:
         return out
 
     def _mixture_batch_args(self, Xd, S, zs, Yd=None):
-        """What evaluate_batch, quantiles_batch and calibration_batch do ahead of their library call -> (n, zp, zst, keep)"""
+        """What evaluate_batch, quantiles_batch, calibration_batch and classification_batch do ahead of their library call -> (n, zp, zst, keep)"""
         n = Xd.shape[0]
         if Yd is not None:
             self._check_targets_shape(Yd, n)
@@ -450,6 +450,16 @@ class Engine:
         _lib.check(self.lib.dsdgp_model_calibration(self.model, ptr(Xd), ptr(Yd), n, S, zp, zst, C.c_uint64(seed),
                                                     probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(rows), ptr(acc),
                                                     int(bool(accumulate))))
+        return keep
+
+    def classification_batch(self, Xd, Yd, S, bins, acc, accumulate, zs=None, seed=0, probs=None, rows=None):
+        """dsdgp_model_classification on one batch of device rows (MultiClass / Bernoulli): forward pass + class probabilities + report
+        reduction into the device accumulator `acc` ((4 + 3 bins + C + C^2) x ND; added to when `accumulate`), the mixture class
+        probabilities into `probs` (n, D_out) and per-row [predicted class, conf, l, brier] into `rows` (n, ND, 4) if given.
+        Asynchronous."""
+        n, zp, zst, keep = self._mixture_batch_args(Xd, S, zs, Yd)
+        _lib.check(self.lib.dsdgp_model_classification(self.model, ptr(Xd), ptr(Yd), n, S, zp, zst, C.c_uint64(seed), int(bins),
+                                                       ptr(probs), ptr(rows), ptr(acc), int(bool(accumulate))))
         return keep
 
     def adam_step(self, lr=0.01, beta1=0.9, beta2=0.999, eps=1e-8):

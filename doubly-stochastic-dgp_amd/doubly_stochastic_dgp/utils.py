@@ -161,6 +161,48 @@ class BroadcastingLikelihood:
         ctx.sync()
         return (acc.cpu().numpy(), out.cpu().numpy()) if rows else acc.cpu().numpy()
 
+    def classification_args(self, what):
+        """(kind, C) of dsdgp_mixture_classification for the wrapped likelihood: MultiClass (C = num_classes) or Bernoulli (C = 2, one
+        two-class problem per output); every other likelihood has no classes."""
+        from . import _lib
+        from .gpflow_compat import MultiClass
+        if self.bernoulli:
+            return _lib.LIK_BERNOULLI, 2
+        if isinstance(self.likelihood, MultiClass):
+            return _lib.LIK_MULTICLASS, int(self.likelihood.num_classes)
+        raise NotImplementedError(f"{what}: {type(self.likelihood).__name__} has no classes; MultiClass and Bernoulli are covered")
+
+    def mixture_classification(self, Fmu, Fvar, Y, bins=10, rows=False):
+        """dsdgp_mixture_classification on (S, N, D) component means / variances and targets Y (MultiClass: (N, 1) labels, D = K;
+        Bernoulli: (N, D), every output its own two-class problem): the accumulator as an (E, ND) array, E = 4 + 3 bins + C + C^2 and
+        ND = 1 (MultiClass, C = K) or D (Bernoulli, C = 2), laid out as include/dsdgp.h documents (`dgp.classification_scores` turns it
+        into the report), and with rows=True also the mixture class probabilities (N, D) (Bernoulli: p(y = 1)) and the (N, ND, 4)
+        per-row values [predicted class, conf, l = log pi_y, brier].  brier is the multi-class sum_c (pi_c - [c = y])^2: a binary
+        problem gives 2 (p - t)^2, twice the usual binary score."""
+        kind, Cn = self.classification_args("mixture_classification")
+        bins = int(bins)
+        if not 1 <= bins <= 32:
+            raise ValueError("bins must lie in 1 .. 32")
+        self.check_targets(Y)
+        from . import _lib
+        from .engine import Context, ptr
+        Fmu = np.asarray(Fmu, dtype=np.float64)
+        S, N, D = Fmu.shape
+        ND = D if self.bernoulli else 1
+        if np.shape(Y) != (N, ND):
+            raise ValueError(f"Y has shape {np.shape(Y)}, expected {(N, ND)}")
+        if not self.bernoulli and D != Cn:
+            raise ValueError(f"Fmu has {D} outputs, the likelihood {Cn} classes")
+        ctx = Context.get()
+        m, v, y = ctx.to_device(Fmu), ctx.to_device(np.broadcast_to(Fvar, Fmu.shape)), ctx.to_device(Y)
+        acc = ctx.empty(4 + 3 * bins + Cn + Cn * Cn, ND)
+        probs = ctx.empty(N, D) if rows else None
+        out = ctx.empty(N, ND, 4) if rows else None
+        _lib.check(ctx.lib.dsdgp_mixture_classification(ctx.handle, kind, ptr(m), ptr(v), ptr(y), N, S, D, bins, ptr(probs), ptr(out),
+                                                        ptr(acc), 0))
+        ctx.sync()
+        return (acc.cpu().numpy(), probs.cpu().numpy(), out.cpu().numpy()) if rows else acc.cpu().numpy()
+
     def check_targets(self, Y):
         """MultiClass: Y must hold integer class labels in [0, num_classes) — the device kernel indexes its per-class
         accumulators with them ([UPSTREAM] tf.one_hot / gather would error or zero-fill; one-hot or NaN targets are a bug)."""

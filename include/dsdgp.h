@@ -400,6 +400,37 @@ int dsdgp_model_calibration(dsdgp_model* m, const double* X, const double* Y, in
                             const int64_t* zstride, uint64_t seed, const double* probs, int32_t P, double* rows_out, double* acc,
                             int accumulate);
 
+/* Classification report of the predictive mixture of dgp.py:116-126 for the two likelihoods with classes, on caller-supplied mean / var
+ * ((S*n) x DY, row s*n + i, as dsdgp_model_propagate writes them): is the classifier calibrated, and which classes does it confuse?
+ *   kind = DSDGP_LIK_MULTICLASS: Y (device, n x 1) labels, DY = K classes, 2 <= K <= 32, C = K, ND = 1.  pi[i, k] = (1/S) sum_s p_{s,i,k},
+ *          p_{s,i,k} the RobustMax predictive probability of class k by the arithmetic of dsdgp_multiclass_predict, all K classes of all S
+ *          components in ONE launch (no (S n)-sized intermediate goes through memory).
+ *   kind = DSDGP_LIK_BERNOULLI: Y (device, n x DY), every output d its own two-class problem (class 1: Y == 1, class 0: any other target),
+ *          C = 2, ND = DY.  p[i, d] = (1/S) sum_s probit(mean_s / sqrt(1 + var_s)), pi = (1 - p, p).
+ * Per row i (Bernoulli: per (i, d)), with the label y clamped into 0 .. C-1: predicted class c^ = argmax_c pi_c (ties: the lowest c, so a
+ * Bernoulli p of exactly 0.5 predicts class 0), conf = pi_c^, l = log pi_y (the log density of dsdgp_eval_mixture),
+ * brier = sum_c (pi_c - [c = y])^2 (the multi-class definition: a binary problem gives 2 (p - t)^2, twice the usual binary Brier score),
+ * rank = #{c : pi_c > pi_y} + #{c < y : pi_c == pi_y}, bin = min(bins - 1, floor(conf * bins)): `bins` equal-width bins on [0, 1].
+ *   bins: 1 .. 32.
+ *   probs_out (device, n x DY, or NULL): pi (MultiClass), p(y = 1) (Bernoulli).
+ *   rows_out (device, n x ND x 4, or NULL): [c^, conf, l, brier].
+ *   acc (device, E*ND doubles, E = 4 + 3*bins + C + C*C), entry acc[q*ND + d]:
+ *            q = 0 sum [c^ != y], 1 sum l, 2 sum brier, 3 rows; 4 + b rows in bin b; 4 + bins + b sum of conf over bin b;
+ *            4 + 2*bins + b sum of [c^ = y] over bin b; 4 + 3*bins + r rows whose label has rank r;
+ *            4 + 3*bins + C + t*C + c rows with label t predicted as c
+ *            — the counts exact integers; overwritten, or added to when accumulate != 0 (batches; data-parallel ranks).
+ * Fixed-order reductions: the same inputs and n give the same bits.  DSDGP_ERR_UNSUPPORTED for any other kind or K outside 2..32,
+ * DSDGP_ERR_BAD_ARG for bins outside 1..32. */
+int dsdgp_mixture_classification(dsdgp_ctx* ctx, int32_t kind, const double* mean, const double* var, const double* Y, int64_t n,
+                                 int32_t S, int32_t DY, int32_t bins, double* probs_out, double* rows_out, double* acc, int accumulate);
+/* The same on a model's own predictions: the forward pass exactly as dsdgp_model_evaluate runs it (same kernels, same Philox draws from
+ * `seed`, same `zs` injection, only the last layer's mean and variance kept, in the workspace), then the primitive on the same stream with
+ * the model's likelihood.  DSDGP_ERR_UNSUPPORTED for a model whose likelihood is neither MultiClass nor Bernoulli, and while quadrature
+ * sample weights are set (dsdgp_model_set_sample_weights). */
+int dsdgp_model_classification(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                               const int64_t* zstride, uint64_t seed, int32_t bins, double* probs_out, double* rows_out, double* acc,
+                               int accumulate);
+
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
 
