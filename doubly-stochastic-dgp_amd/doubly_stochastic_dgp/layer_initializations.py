@@ -1,10 +1,96 @@
 """Layer construction for DGP (host-side, one-off).  Same two entry points and argument meaning as the reference's
 layer_initializations.py:16-52 / :55-79, organised differently: the inter-layer width maps are PLANNED first (one
 `_width_map` per boundary) and the layers are then built from the plan."""
+import ctypes as C
+
 import numpy as np
 
 from .gpflow_compat import Identity, Linear, Zero
 from .layers import SVGP_Layer
+
+KMEANS_MAX_M, KMEANS_MAX_D = 2048, 1024          # KM_MAX_M, KM_MAX_D of csrc/kmeans.hip
+
+
+def _kmeans_args(X, M, iter, init):
+    """Everything kmeans_inducing can refuse without a device -> (n, D, M, iters, index array or None, centre array or None); called
+    before the engine's context is touched, so a machine without a GPU reports the bad argument and not the missing device."""
+    on_device = hasattr(X, "data_ptr")
+    if not on_device:
+        X = np.asarray(X)
+    if len(X.shape) != 2:
+        raise ValueError(f"X must be a 2-D (n, D) array, not one of shape {tuple(X.shape)}")
+    n, D = int(X.shape[0]), int(X.shape[1])
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)):
+        raise ValueError(f"M must be an integer, not {M!r}")
+    M, iters = int(M), int(iter)
+    if not 2 <= M <= KMEANS_MAX_M:
+        raise ValueError(f"M = {M} outside 2 .. {KMEANS_MAX_M}")
+    if not 1 <= D <= KMEANS_MAX_D:
+        raise ValueError(f"D = {D} outside 1 .. {KMEANS_MAX_D}")
+    if iters < 1:
+        raise ValueError(f"iter = {iters}: at least one iteration")
+    if M > n:
+        raise ValueError(f"M = {M} centres from n = {n} rows")
+    if not on_device and not np.all(np.isfinite(np.asarray(X, dtype=np.float64))):
+        raise ValueError("X holds a non-finite value")
+    idx = centres = None
+    if init is not None:
+        if hasattr(init, "data_ptr"):
+            init = init.cpu().numpy()
+        init = np.asarray(init)
+        if init.ndim == 1:
+            if init.shape != (M,) or not np.issubdtype(init.dtype, np.integer):
+                raise ValueError(f"init as row indices must be an integer array of shape ({M},)")
+            if init.min() < 0 or init.max() >= n:
+                raise ValueError(f"init holds a row index outside 0 .. {n - 1}")
+            idx = init.astype(np.int64)
+        elif init.shape == (M, D):
+            centres = np.ascontiguousarray(init, dtype=np.float64)
+            if not np.all(np.isfinite(centres)):
+                raise ValueError("init holds a non-finite value")
+        else:
+            raise ValueError(f"init must be ({M},) row indices or ({M}, {D}) centres, not shape {init.shape}")
+    return n, D, M, iters, idx, centres
+
+
+def kmeans_inducing(X, M, iter=10, seed=0, init=None, return_info=False):
+    """Inducing inputs by k-means on the device: what demos/run_regression.py:57 does with scipy's kmeans2(X, M, minit='points')[0].
+    X: numpy array or device tensor (n, D).  init None: the start centres are the rows np.random.default_rng(seed).choice(n, M,
+    replace=False) — the minit='points' rule, M distinct rows, but numpy's Generator stream and not the RandomState draw scipy makes,
+    so the same seed does not reproduce scipy's Z.  init may instead be M row indices, shape (M,), or the centres themselves, (M, D).
+    `iter` Lloyd iterations (kmeans2's default 10): ties go to the lowest centre, a centre without rows keeps its value; the same
+    X, M, iter and start give the same bits on every call and every rank.  Returns Z (M, D) as numpy; with return_info also a dict:
+    `labels` (n,) int32 and `counts` (M,) int64 of the assignment Z was averaged from (kmeans2's second result), `inertia` = that
+    assignment's sum of squared distances to its centres.
+    ValueError, before any device is looked for: X not 2-D, M outside 2 .. 2048, D outside 1 .. 1024, iter < 1, M > n, an init of the
+    wrong shape or with an index out of range, a non-finite value in a numpy X or init."""
+    n, D, M, iters, idx, centres = _kmeans_args(X, M, iter, init)
+    if idx is None and centres is None:
+        idx = np.random.default_rng(seed).choice(n, M, replace=False).astype(np.int64)
+    from . import _lib
+    from .engine import Context
+    ctx = Context.get()
+    torch = ctx.torch
+    dev = f"cuda:{ctx.device}"
+    with torch.cuda.stream(ctx.tstream):
+        if hasattr(X, "data_ptr"):
+            Xd = X.to(device=dev, dtype=torch.float64).contiguous()
+            Z0 = Xd[torch.as_tensor(idx).to(dev)].contiguous() if centres is None else ctx.to_device(centres)
+        else:
+            Xh = np.ascontiguousarray(X, dtype=np.float64)
+            Xd = ctx.to_device(Xh)
+            Z0 = ctx.to_device(Xh[idx] if centres is None else centres)
+        Z = ctx.empty(M, D)
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        counts = torch.empty(M, dtype=torch.int64, device=dev)
+        inertia = ctx.empty(1)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(ctx.lib.dsdgp_kmeans(ctx.handle, p(Xd), n, D, M, p(Z0), iters, p(Z), p(labels), p(counts), p(inertia)))
+    ctx.sync()
+    Zh = Z.cpu().numpy()
+    if not return_info:
+        return Zh
+    return Zh, {"labels": labels.cpu().numpy(), "counts": counts.cpu().numpy(), "inertia": float(inertia.cpu().numpy()[0])}
 
 
 def _width_map(d_from, d_to, cloud):

@@ -431,6 +431,23 @@ int dsdgp_model_classification(dsdgp_model* m, const double* X, const double* Y,
                                const int64_t* zstride, uint64_t seed, int32_t bins, double* probs_out, double* rows_out, double* acc,
                                int accumulate);
 
+/* dsdgp_kmeans: Lloyd's k-means for the inducing points, Z = kmeans2(X, M, minit='points')[0] of demos/run_regression.py:57 (scipy, one
+ * host thread) on the device.  X (device, n x D, row-major), Z0 (device, M x D): the initial centres (with minit='points', M rows of X).
+ * `iters` iterations of  assign: label_i = argmin_m |x_i - z_m|^2 (ties: the lowest m; a NaN never wins, so 0 <= label < M whatever X
+ * holds),  update: z_m = the mean of the rows labelled m; a centre without rows keeps its value bit for bit (kmeans2's missing='warn',
+ * without the warning).  All of them are enqueued on the context's stream; the host does not wait.
+ *   Z (device, M x D): the centres after the last update; may alias Z0.
+ *   labels (device, n x int32, or NULL), counts (device, M x int64, or NULL), inertia (device, 1 double, or NULL): the last assignment —
+ *            the one Z was averaged from, what kmeans2 returns as its labels — its cluster sizes and its sum_i min_m |x_i - z_m|^2.
+ * The arithmetic runs on X minus its column means (k-means is translation-invariant; |x|^2 + |z|^2 - 2 x.z on uncentred data is not),
+ * the cross products on the fp64 MFMA pipe with the argmin fused behind them: nothing of size n x M reaches memory.  Every reduction runs
+ * in a fixed order and the update sorts the rows by label instead of adding with floating-point atomics: the same X, Z0 and iters give
+ * the same bits, on every rank of a data-parallel run.
+ * DSDGP_ERR_BAD_ARG (nothing launched, Z untouched) for n < M, n >= 2^31, M outside 2..2048, D outside 1..1024, iters < 1 or a NULL
+ * X / Z0 / Z. */
+int dsdgp_kmeans(dsdgp_ctx* ctx, const double* X, int64_t n, int32_t D, int32_t M, const double* Z0, int32_t iters, double* Z,
+                 int32_t* labels, int64_t* counts, double* inertia);
+
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
 
