@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "gauss_hermite.hpp"
+#include "likelihood.hpp"
 #include "mixture_common.hpp"
 
 #define CLS_KMAX 32       // MC_KMAX of multiclass.hip

@@ -86,7 +86,6 @@ int ctx_upload(dsdgp_ctx* ctx, void* dst, const void* src, size_t bytes);
 // launchers that one translation unit defines and others call
 int multiclass_launch(dsdgp_ctx* ctx, const double* mean, const double* var, const double* Y, int64_t n, int64_t R, int K,
                       int mode, double wgt, double* out, double* dmean, double* dvar, int y_override);      // multiclass.hip
-bool lik_quad_kind_ok(int kind, double p0, double p1);                                                      // elementwise.hip
 // p0_dev / noise_dev != NULL: the likelihood's positive parameter is read on the device (a model's own copy); p0 / noise_var is ignored
 int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const double* p0_dev, const double* mean, const double* var,
                         const double* Y, int64_t n, int S, int DY, double* rows_out, double* acc, int accumulate);      // evaluate.hip
@@ -177,180 +176,6 @@ typedef double __attribute__((address_space(3)))* lptr;
 // what lets the layer chain feed one GEMM's result straight into the next without touching LDS.
 __device__ __forceinline__ d4 mfma_f64(double a, double b, d4 c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
-// ---- [UPSTREAM] Bernoulli likelihood, probit link (/root/reference/tests/test_dgp.py:48-54 builds it; its variational
-// expectations are the base Likelihood's 20-point Gauss-Hermite rule, its predictions the probit closed form)
-// probit(x) = Phi(x) (1 - 2e-3) + 1e-3
-__device__ __forceinline__ double bern_probit(double x) { return 0.5 * (1.0 + erf(x * 0.70710678118654752440)) * (1.0 - 2e-3) + 1e-3; }
-// log Bernoulli(y | p): y == 1 selects p, every other target 1 - p
-__device__ __forceinline__ double bern_logp(double p, double y) { return log(y == 1.0 ? p : 1.0 - p); }
-// variational expectation int log p(y | f) N(f | mu, v) df with np.polynomial.hermite.hermgauss(20) (weights / sqrt(pi));
-// dmu / dv = its derivatives.  No clamp on v: a negative variance gives NaN, as upstream's sqrt does.
-__device__ __forceinline__ double bern_var_exp(double mu, double v, double y, double* dmu, double* dv) {
-  constexpr double GX[10] = {0.24534070830090124, 0.7374737285453944, 1.234076215395323, 1.7385377121165861, 2.2549740020892757,
-                             2.7888060584281305, 3.3478545673832163, 3.944764040115625, 4.603682449550744, 5.387480890011233};
-  constexpr double GW[10] = {0.2607930634495549, 0.16173933398399998, 0.0615063720639769, 0.013997837447101022,
-                             0.00183010313108049, 0.00012882627996192928, 4.402121090230851e-06, 6.127490259982928e-08,
-                             2.4820623623151755e-10, 1.2578006724379234e-13};
-  const double sd = sqrt(2.0 * v);
-  const double sgn = (y == 1.0) ? 1.0 : -1.0;
-  double ve = 0.0, gm = 0.0, gv = 0.0;
-#pragma unroll
-  for (int k = 0; k < 20; ++k) {
-    const double x = (k < 10) ? -GX[9 - k] : GX[k - 10];
-    const double w = (k < 10) ? GW[9 - k] : GW[k - 10];
-    const double f = mu + sd * x;
-    const double p = bern_probit(f);
-    const double q = (y == 1.0) ? p : 1.0 - p;
-    ve += w * log(q);
-    const double dl = sgn * (1.0 - 2e-3) * 0.39894228040143267794 * exp(-0.5 * f * f) / q;      // d log q / d f
-    gm += w * dl;
-    gv += w * dl * x;
-  }
-  *dmu = gm;
-  *dv = gv / sd;
-  return ve;
-}
-
-// ---- [UPSTREAM] further GPflow 1.1.1 likelihoods behind BroadcastingLikelihood (utils.py:54-121 wraps ANY likelihood): Poisson and
-// Exponential / Gamma with the exp link, StudentT, Beta.  kind = DSDGP_LIK_*; p0 = StudentT.scale / Gamma.shape / Beta.scale,
-// p1 = Poisson.binsize / StudentT.deg_free.
-// digamma(x), x > 0: recurrence up to x >= 8, then the asymptotic series (error < 1e-15 there)
-__device__ __forceinline__ double digamma_d(double x) {
-  double r = 0.0;
-  while (x < 8.0) {
-    r -= 1.0 / x;
-    x += 1.0;
-  }
-  const double i = 1.0 / x, i2 = i * i;
-  return r + log(x) - 0.5 * i -
-         i2 * (1.0 / 12.0 - i2 * (1.0 / 120.0 - i2 * (1.0 / 252.0 - i2 * (1.0 / 240.0 - i2 * (1.0 / 132.0 - i2 * (691.0 / 32760.0 - i2 / 12.0))))));
-}
-// log p(y | f).  Gamma (kind 6, exp link): p0 = shape.  Beta (kind 7, the Bernoulli's probit link): p0 = scale, y clipped to [1e-6, 1 - 1e-6].
-__device__ __forceinline__ double lik_logp(int kind, double f, double y, double p0, double p1) {
-  if (kind == 6) return -p0 * f - lgamma(p0) + (p0 - 1.0) * log(y) - y * exp(-f);
-  if (kind == 7) {
-    const double mean = bern_probit(f), al = mean * p0, be = p0 - al, yc = fmin(fmax(y, 1e-6), 1.0 - 1e-6);
-    return (al - 1.0) * log(yc) + (be - 1.0) * log(1.0 - yc) + lgamma(al + be) - lgamma(al) - lgamma(be);
-  }
-  if (kind == 3) return y * (f + log(p1)) - exp(f) * p1 - lgamma(y + 1.0);      // Poisson: y log(lam) - lam - lgamma(y + 1), lam = exp(f) binsize
-  if (kind == 4) return -y * exp(-f) - f;                                       // Exponential: -y / scale - log(scale), scale = exp(f)
-  const double nu = p1, z = (y - f) / p0;                                       // StudentT
-  return lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * (log(nu) + 1.1447298858494001741) - log(p0) -
-         0.5 * (nu + 1.0) * log(1.0 + z * z / nu);
-}
-// conditional mean / variance of y given f
-__device__ __forceinline__ void lik_cond(int kind, double f, double p0, double p1, double* cm, double* cv) {
-  if (kind == 3) { *cm = *cv = exp(f) * p1; return; }
-  if (kind == 4) { const double e = exp(f); *cm = e; *cv = e * e; return; }
-  if (kind == 6) { const double e = exp(f); *cm = p0 * e; *cv = p0 * e * e; return; }
-  if (kind == 7) { const double m = bern_probit(f); *cm = m; *cv = (m - m * m) / (p0 + 1.0); return; }
-  *cm = f;
-  *cv = p0 * p0 * (p1 / (p1 - 2.0));
-}
-#define DSDGP_GH20_X {0.24534070830090124, 0.7374737285453944, 1.234076215395323, 1.7385377121165861, 2.2549740020892757, \
-                      2.7888060584281305, 3.3478545673832163, 3.944764040115625, 4.603682449550744, 5.387480890011233}
-#define DSDGP_GH20_W {0.2607930634495549, 0.16173933398399998, 0.0615063720639769, 0.013997837447101022, 0.00183010313108049, \
-                      0.00012882627996192928, 4.402121090230851e-06, 6.127490259982928e-08, 2.4820623623151755e-10, 1.2578006724379234e-13}
-// variational expectation int log p(y | f) N(f | mu, v) df and its derivatives w.r.t. mu, v and p0: the closed forms GPflow uses with
-// the exp link (Poisson, Exponential), the base Likelihood's 20-point Gauss-Hermite rule (weights / sqrt(pi)) for StudentT
-__device__ __forceinline__ double lik_var_exp(int kind, double mu, double v, double y, double p0, double p1, double* dmu, double* dv,
-                                              double* dp0) {
-  *dp0 = 0.0;
-  if (kind == 3) {
-    const double e = exp(mu + 0.5 * v) * p1;
-    *dmu = y - e;
-    *dv = -0.5 * e;
-    return y * mu - e - lgamma(y + 1.0) + y * log(p1);
-  }
-  if (kind == 4) {
-    const double e = exp(-mu + 0.5 * v) * y;
-    *dmu = e - 1.0;
-    *dv = -0.5 * e;
-    return -e - mu;
-  }
-  if (kind == 6) {      // Gamma, exp link: -shape mu - lgamma(shape) + (shape - 1) log y - y exp(-mu + v / 2)
-    const double e = exp(-mu + 0.5 * v) * y;
-    *dmu = e - p0;
-    *dv = -0.5 * e;
-    *dp0 = -mu - digamma_d(p0) + log(y);
-    return -p0 * mu - lgamma(p0) + (p0 - 1.0) * log(y) - e;
-  }
-  constexpr double GX[10] = DSDGP_GH20_X;
-  constexpr double GW[10] = DSDGP_GH20_W;
-  if (kind == 7) {      // Beta: quadrature of the log density, its derivatives through alpha = probit(f) scale, beta = scale - alpha
-    const double sd = sqrt(2.0 * v), yc = fmin(fmax(y, 1e-6), 1.0 - 1e-6), ly = log(yc), l1y = log(1.0 - yc);
-    const double lgs = lgamma(p0), dgs = digamma_d(p0);
-    double ve = 0.0, gm = 0.0, gv = 0.0, gp = 0.0;
-#pragma unroll 1
-    for (int k = 0; k < 20; ++k) {
-      const double x = (k < 10) ? -GX[9 - k] : GX[k - 10];
-      const double w = (k < 10) ? GW[9 - k] : GW[k - 10];
-      const double f = mu + sd * x;
-      const double mean = bern_probit(f), al = mean * p0, be = p0 - al;
-      ve += w * ((al - 1.0) * ly + (be - 1.0) * l1y + lgs - lgamma(al) - lgamma(be));
-      const double da = digamma_d(al), db = digamma_d(be);
-      const double dl = (1.0 - 2e-3) * 0.39894228040143267794 * exp(-0.5 * f * f) * p0 * (ly - l1y - da + db);      // d log p / d f
-      gm += w * dl;
-      gv += w * dl * x;
-      gp += w * (mean * ly + (1.0 - mean) * l1y + dgs - mean * da - (1.0 - mean) * db);
-    }
-    *dmu = gm;
-    *dv = gv / sd;
-    *dp0 = gp;
-    return ve;
-  }
-  const double sd = sqrt(2.0 * v), nu = p1;
-  const double c0 = lgamma(0.5 * (nu + 1.0)) - lgamma(0.5 * nu) - 0.5 * (log(nu) + 1.1447298858494001741) - log(p0);
-  double ve = 0.0, gm = 0.0, gv = 0.0, gp = 0.0;
-#pragma unroll
-  for (int k = 0; k < 20; ++k) {
-    const double x = (k < 10) ? -GX[9 - k] : GX[k - 10];
-    const double w = (k < 10) ? GW[9 - k] : GW[k - 10];
-    const double r = y - (mu + sd * x), den = nu * p0 * p0 + r * r;
-    ve += w * (c0 - 0.5 * (nu + 1.0) * log(den / (nu * p0 * p0)));
-    const double dl = (nu + 1.0) * r / den;                       // d log p / d f
-    gm += w * dl;
-    gv += w * dl * x;
-    gp += w * (-1.0 / p0 + (nu + 1.0) * r * r / (p0 * den));      // d log p / d scale
-  }
-  *dmu = gm;
-  *dv = gv / sd;
-  *dp0 = gp;
-  return ve;
-}
-// log int p(y | f) N(f | mu, v) df (predict_density) by the same rule
-__device__ __forceinline__ double lik_log_density(int kind, double mu, double v, double y, double p0, double p1) {
-  constexpr double GX[10] = DSDGP_GH20_X;
-  constexpr double GW[10] = DSDGP_GH20_W;
-  const double sd = sqrt(2.0 * v);
-  double s = 0.0;
-#pragma unroll 1
-  for (int k = 0; k < 20; ++k) {
-    const double x = (k < 10) ? -GX[9 - k] : GX[k - 10];
-    const double w = (k < 10) ? GW[9 - k] : GW[k - 10];
-    s += w * exp(lik_logp(kind, mu + sd * x, y, p0, p1));
-  }
-  return log(s);
-}
-// predict_mean_and_var: E_y = sum w cm(f_k), V_y = sum w (cv(f_k) + cm(f_k)^2) - E_y^2
-__device__ __forceinline__ void lik_predict(int kind, double mu, double v, double p0, double p1, double* ey, double* vy) {
-  constexpr double GX[10] = DSDGP_GH20_X;
-  constexpr double GW[10] = DSDGP_GH20_W;
-  const double sd = sqrt(2.0 * v);
-  double e = 0.0, q = 0.0;
-#pragma unroll 1
-  for (int k = 0; k < 20; ++k) {
-    const double x = (k < 10) ? -GX[9 - k] : GX[k - 10];
-    const double w = (k < 10) ? GW[9 - k] : GW[k - 10];
-    double cm, cv;
-    lik_cond(kind, mu + sd * x, p0, p1, &cm, &cv);
-    e += w * cm;
-    q += w * (cv + cm * cm);
-  }
-  *ey = e;
-  *vy = q - e * e;
 }
 
 // Cross-lane sums WITHOUT the LDS: __shfl_xor compiles to ds_bpermute_b32 pairs (an LDS round trip of 100-200 cycles per step when

@@ -2,10 +2,11 @@
 // on the host (demos/run_regression.py:108-123 on predict_y outputs; dgp.py:116-126 predict_y / predict_density), and its three sums.
 //   per (i, d):  mhat = mean_s E_s ;  mixture variance = mean_s (V_s + E_s^2) - mhat^2 ;  l = logsumexp_s log p(y | mean_s, var_s) - log S
 //   per output:  sum_i (y - mhat)^2 (MultiClass: sum_i [argmax_k mhat_k != y]),  sum_i l,  the row count
-// (E_s, V_s) = predict_mean_and_var of component s.  The component formulas are the device functions of common.hpp (Bernoulli, the
-// five quadrature likelihoods) and multiclass_launch (MultiClass); only the Gaussian's closed form is written here.
+// (E_s, V_s) = predict_mean_and_var of component s.  The component formulas are lik_density / lik_moments of likelihood.hpp (the
+// element-wise likelihoods) and multiclass_launch (MultiClass).
 // Memory-bound: 2 S n DY doubles read once; nothing but the partial sums is written unless the per-row values are asked for.
 // Every reduction runs in a fixed order: the same inputs and batch size give the same bits.
+#include "likelihood.hpp"
 #include "mixture_common.hpp"
 
 #define EV_NSEG 8         // segments of the in-workgroup sums
@@ -41,24 +42,12 @@ __device__ __forceinline__ void lse_merge(double am, double as, double bm, doubl
   sm = as * ea + bs * eb;
 }
 
-// LIK: 0 Gaussian (closed form), 2 Bernoulli, 3 the quadrature likelihoods (runtime kind)
+// LIK: the family of an element-wise likelihood (LIKF_QUAD: runtime kind), LIKF_NONE = MultiClass
 template <int LIK>
 __device__ __forceinline__ void eval_component(int kind, double mu, double v, double y, double p0, double p1, double& lp, double& E,
                                                double& V) {
-  if (LIK == 0) {
-    const double vv = v + p0, r = y - mu;
-    lp = -0.91893853320467274178 - 0.5 * log(vv) - 0.5 * r * r / vv;
-    E = mu;
-    V = vv;
-  } else if (LIK == 2) {
-    const double p = bern_probit(mu / sqrt(1.0 + v));
-    lp = bern_logp(p, y);
-    E = p;
-    V = p - p * p;
-  } else {
-    lik_predict(kind, mu, v, p0, p1, &E, &V);
-    lp = lik_log_density(kind, mu, v, y, p0, p1);
-  }
+  lik_moments<LIK>(kind, mu, v, p0, p1, E, V);
+  lp = lik_density<LIK>(kind, mu, v, y, p0, p1);
 }
 
 // fold_sum's butterfly for the (maximum, sum) pairs
@@ -84,7 +73,7 @@ __global__ __launch_bounds__(MIX_T) void k_eval_mix(const EvalArgs a) {
   const int S = a.S;
   const double invS = 1.0 / (double)S, logS = log((double)S);
   double err, ell;
-  if (LIK == 1) {
+  if (LIK == LIKF_NONE) {
     // MultiClass: item = row i.  l from the label's log densities, then class by class the mixture probability and its argmax
     const int K = a.DY;
     const int64_t R = (int64_t)S * a.n;
@@ -165,7 +154,7 @@ __global__ __launch_bounds__(MIX_T) void k_eval_mix(const EvalArgs a) {
     ent[2 * JPB + jl] = live ? 1.0 : 0.0;
   }
   __syncthreads();
-  const int ND = (LIK == 1) ? 1 : a.DY;      // outputs with sums of their own (MultiClass: one)
+  const int ND = (LIK == LIKF_NONE) ? 1 : a.DY;      // outputs with sums of their own (MultiClass: one)
   if (ND <= EV_DFAST) {
     constexpr int SL = JPB / EV_NSEG;
     for (int p = tid; p < 3 * ND * EV_NSEG; p += MIX_T) {
@@ -195,17 +184,12 @@ static void eval_launch(int split, int nblocks, hipStream_t st, const EvalArgs& 
 int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const double* p0_dev, const double* mean, const double* var,
                         const double* Y, int64_t n, int S, int DY, double* rows_out, double* acc, int accumulate) {
   DS_CHECK_ARG(ctx && mean && var && Y && acc && n > 0 && S > 0 && DY > 0);
-  const bool generic = kind == DSDGP_LIK_POISSON || kind == DSDGP_LIK_EXPONENTIAL || kind == DSDGP_LIK_STUDENT_T ||
-                       kind == DSDGP_LIK_GAMMA || kind == DSDGP_LIK_BETA;
-  if (!(kind == DSDGP_LIK_GAUSSIAN || kind == DSDGP_LIK_MULTICLASS || kind == DSDGP_LIK_BERNOULLI || generic)) {
+  const bool mc = kind == DSDGP_LIK_MULTICLASS;
+  if (!mc && lik_family(kind) == LIKF_NONE) {
     dsdgp_set_error("dsdgp_eval_mixture: likelihood kind %d is not covered", kind);
     return DSDGP_ERR_UNSUPPORTED;
   }
-  if (!p0_dev) {
-    if (kind == DSDGP_LIK_GAUSSIAN) DS_CHECK_ARG(p0 > 0.0);
-    if (generic) DS_CHECK_ARG(lik_quad_kind_ok(kind, p0, p1));
-  }
-  const bool mc = kind == DSDGP_LIK_MULTICLASS;
+  if (!mc) DS_CHECK_ARG(lik_params_ok(kind, p0_dev ? 1.0 : p0, p1));
   const int64_t total = mc ? n : n * DY;
   const int split = mix_split_clamp(mix_split_by_items(total), S);
   int nblocks;
@@ -224,13 +208,9 @@ int eval_mixture_launch(dsdgp_ctx* ctx, int kind, double p0, double p1, const do
     DS_TRY(multiclass_launch(ctx, mean, var, Y, n, R, DY, 1, 0.0, T, nullptr, nullptr, -1));
     for (int k = 0; k < DY; ++k) DS_TRY(multiclass_launch(ctx, mean, var, nullptr, R, R, DY, 1, 0.0, T + (int64_t)(1 + k) * R, nullptr, nullptr, k));
     a.T = T;
-    eval_launch<1>(split, nblocks, ctx->stream, a);
-  } else if (kind == DSDGP_LIK_GAUSSIAN) {
-    eval_launch<0>(split, nblocks, ctx->stream, a);
-  } else if (kind == DSDGP_LIK_BERNOULLI) {
-    eval_launch<2>(split, nblocks, ctx->stream, a);
+    eval_launch<LIKF_NONE>(split, nblocks, ctx->stream, a);
   } else {
-    eval_launch<3>(split, nblocks, ctx->stream, a);
+    lik_dispatch(kind, [&](auto fam) { eval_launch<decltype(fam)::value>(split, nblocks, ctx->stream, a); });
   }
   // (MultiClass: one output has sums of its own)
   mixture_finish_launch(ctx->stream, (const double*)scr, nblocks, 3 * DY, DY, mc ? 1 : DY, accumulate, acc);

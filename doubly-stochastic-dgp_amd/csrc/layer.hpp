@@ -35,7 +35,7 @@ struct LayerFwdArgs {
   double* XT1;          // split-M kernels, training: (DinP16 x ldA) [X^T ; 1] for the Z-gradient product, or NULL
   unsigned long long* phase_clk;   // debug aid (DSDGP_FWD_TIMING): [workgroup][8] s_memrealtime (100 MHz) stamps of the forward chain's phases, or NULL
   // last layer of a training step with the Gaussian likelihood: [UPSTREAM] Gaussian.variational_expectations (dgp.py:89-90) and its
-  // adjoints in this chain's epilogue (k_lik_gauss's job: one launch less between the forward and the reverse pass).  lik_Y NULL: off.
+  // adjoints in this chain's epilogue (k_lik_elbo<LIKF_GAUSS>'s job: one launch less between the forward and the reverse pass).  lik_Y NULL: off.
   const double* lik_Y;             // (n_inner x D_out) targets
   const double* lik_const;         // [0] = likelihood variance
   double lik_w;                    // data_scale / S
@@ -70,7 +70,7 @@ struct LayerBwdArgs {
   //   XT1       [X^T;1]: 0 for r >= Rin — the forward chain's XT1 store, k_xt1 (GEMM pass), k_adj_prep
   //   VB, MB    whoever produces the adjoints: the next layer's backward chain (MBp / VBp: zeros for Rin <= row < ldA), the adjoint
   //             prologue of this chain (MBw / VBw, same), k_adj_prep (every r < ld, 0 where r >= Rin or d >= D_out), the likelihood
-  //             epilogue of the last forward chain (lik_MB / lik_VB) and the k_lik_* kernels (MBt / VBt)
+  //             epilogue of the last forward chain (lik_MB / lik_VB) and k_lik_elbo (MBt / VBt)
   //   GW        this chain, all ldA columns: 0 where r >= Rin or m >= M
   //   E         this chain, all ldA columns; the pad holds whatever the chain computed for the clamped rows — its only consumer, the
   //             product E A^T, meets Asave's zero pad there

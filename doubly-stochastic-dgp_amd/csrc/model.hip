@@ -2,6 +2,7 @@
 // One C call enqueues a whole ELBO evaluation (+ reverse-mode gradient) on the ctx stream; nothing here touches the host
 // between kernels except reading the final scalars when the caller asks for them.
 #include "layer.hpp"
+#include "likelihood.hpp"
 #include "linalg.hpp"
 #include <stdlib.h>
 #include <hip/hip_ext.h>
@@ -20,8 +21,7 @@ int gram_launch(dsdgp_ctx* ctx, int kind, const double* X, int64_t n, const doub
 // ------------------------------------------------------------------------------------------------------
 static int validate_desc(const dsdgp_model_desc* d) {
   DS_CHECK_ARG(d && d->L >= 1 && d->L <= DSDGP_MAX_LAYERS && d->n_theta > 0);
-  DS_CHECK_ARG(d->lik_kind == DSDGP_LIK_GAUSSIAN || d->lik_kind == DSDGP_LIK_MULTICLASS || d->lik_kind == DSDGP_LIK_BERNOULLI ||
-               lik_is_generic(d->lik_kind));
+  DS_CHECK_ARG(d->lik_kind == DSDGP_LIK_MULTICLASS || lik_family(d->lik_kind) != LIKF_NONE);
   DS_CHECK_ARG((d->lik_kind != DSDGP_LIK_POISSON && d->lik_kind != DSDGP_LIK_STUDENT_T) || d->lik_aux > 0.0);      // binsize / deg_free
   DS_CHECK_ARG(!lik_has_param(d->lik_kind) || (d->off_lik_var >= 0 && d->off_lik_var < d->n_theta));
   for (int l = 0; l < d->L; ++l) {

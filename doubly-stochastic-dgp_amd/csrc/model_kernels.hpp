@@ -304,97 +304,20 @@ __global__ __launch_bounds__(256) void k_kl_final(const LayerDev* __restrict__ l
   layers_kl_value(layers, L, sh);
 }
 
-// [UPSTREAM] Gaussian.variational_expectations (dgp.py:89-90) and its adjoints w.r.t. the last layer's mean/var.
-__global__ __launch_bounds__(256) void k_lik_gauss(const double* __restrict__ mean, const double* __restrict__ var,
-                                                   const double* __restrict__ Y, int64_t n, int S, int DY,
-                                                   const double* __restrict__ lik_const, double w,
-                                                   const double* __restrict__ sw, double* __restrict__ part,
-                                                   double* __restrict__ dmean, double* __restrict__ dvar,
-                                                   double* __restrict__ MBt, double* __restrict__ VBt, int64_t ldt) {
-  // MBt / VBt (DY x ldt, or NULL): the adjoints stored transposed and zero-padded, i.e. already in the form the last layer's
-  // backward chain reads (k_adj_prep's job when that layer has one output row per input row)
-  __shared__ double sh[4];
-  const double s2 = lik_const[0];
-  const int64_t total = (int64_t)S * n * DY;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double ve = 0.0, dl = 0.0;
-  if (idx < total) {
-    const int64_t row = idx / DY;
-    const int dd = (int)(idx % DY);
-    const double y = Y[(row % n) * DY + dd];
-    const double mu = mean[idx], v = var[idx];
-    const double q = (y - mu) * (y - mu) + v;
-    const double f = sw ? sw[row / n] * S : 1.0;     // quadrature weight relative to the MC mean's 1/S (dgp.py:166)
-    ve = f * (-0.91893853320467274178 - 0.5 * log(s2) - 0.5 * q / s2);
-    dl = f * (-0.5 / s2 + 0.5 * q / (s2 * s2));
-    if (dmean) {
-      dmean[idx] = -w * f * (y - mu) / s2;
-      dvar[idx] = 0.5 * w * f / s2;
-    }
-    if (MBt) {
-      MBt[(int64_t)dd * ldt + row] = -w * f * (y - mu) / s2;
-      VBt[(int64_t)dd * ldt + row] = 0.5 * w * f / s2;
-    }
-  } else if (MBt && idx < ldt * DY) {      // rows of the 16-row padding
-    MBt[(idx % DY) * ldt + idx / DY] = 0.0;
-    VBt[(idx % DY) * ldt + idx / DY] = 0.0;
-  }
-  const double a = block_sum_256(ve, sh);
-  const double b = block_sum_256(dl, sh);
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = a;
-    part[2 * blockIdx.x + 1] = b;
-  }
-}
-
-// [UPSTREAM] Bernoulli (probit) variational expectations and their adjoints w.r.t. the last layer's mean / var; same outputs as
-// k_lik_gauss (the likelihood has no parameter: the second partial is zero)
-__global__ __launch_bounds__(256) void k_lik_bern(const double* __restrict__ mean, const double* __restrict__ var,
+// [UPSTREAM] variational expectations of an element-wise likelihood (family F, likelihood.hpp: lik_ve) and their adjoints w.r.t. the
+// last layer's mean / var.  part[block] = {sum of ve, sum of d ve / d p0}: the second is the derivative w.r.t. the likelihood's positive
+// parameter (lik_const[0]: Gaussian.variance, StudentT.scale, Gamma.shape, Beta.scale), zero for the kinds without one.
+template <int F>
+__global__ __launch_bounds__(256) void k_lik_elbo(int kind, const double* __restrict__ lik_const, double aux,
+                                                  const double* __restrict__ mean, const double* __restrict__ var,
                                                   const double* __restrict__ Y, int64_t n, int S, int DY, double w,
                                                   const double* __restrict__ sw, double* __restrict__ part,
                                                   double* __restrict__ dmean, double* __restrict__ dvar,
                                                   double* __restrict__ MBt, double* __restrict__ VBt, int64_t ldt) {
+  // MBt / VBt (DY x ldt, or NULL): the adjoints stored transposed and zero-padded, i.e. already in the form the last layer's
+  // backward chain reads (k_adj_prep's job when that layer has one output row per input row)
   __shared__ double sh[4];
-  const int64_t total = (int64_t)S * n * DY;
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  double ve = 0.0;
-  if (idx < total) {
-    const int64_t row = idx / DY;
-    const int dd = (int)(idx % DY);
-    const double y = Y[(row % n) * DY + dd];
-    const double f = sw ? sw[row / n] * S : 1.0;
-    double dm, dv;
-    ve = f * bern_var_exp(mean[idx], var[idx], y, &dm, &dv);
-    if (dmean) {
-      dmean[idx] = -w * f * dm;
-      dvar[idx] = -w * f * dv;
-    }
-    if (MBt) {
-      MBt[(int64_t)dd * ldt + row] = -w * f * dm;
-      VBt[(int64_t)dd * ldt + row] = -w * f * dv;
-    }
-  } else if (MBt && idx < ldt * DY) {      // rows of the 16-row padding
-    MBt[(idx % DY) * ldt + idx / DY] = 0.0;
-    VBt[(idx % DY) * ldt + idx / DY] = 0.0;
-  }
-  const double a = block_sum_256(ve, sh);
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = a;
-    part[2 * blockIdx.x + 1] = 0.0;
-  }
-}
-
-// [UPSTREAM] Poisson / Exponential / Gamma (exp link), StudentT and Beta variational expectations (common.hpp: lik_var_exp) and their
-// adjoints; same outputs as k_lik_gauss — the second partial is the derivative w.r.t. the likelihood's positive parameter
-// (lik_const[0]: StudentT.scale, Gamma.shape, Beta.scale), zero for Poisson / Exponential
-__global__ __launch_bounds__(256) void k_lik_gen(int kind, const double* __restrict__ lik_const, double aux,
-                                                 const double* __restrict__ mean, const double* __restrict__ var,
-                                                 const double* __restrict__ Y, int64_t n, int S, int DY, double w,
-                                                 const double* __restrict__ sw, double* __restrict__ part,
-                                                 double* __restrict__ dmean, double* __restrict__ dvar,
-                                                 double* __restrict__ MBt, double* __restrict__ VBt, int64_t ldt) {
-  __shared__ double sh[4];
-  const double p0 = (kind == DSDGP_LIK_STUDENT_T || kind == DSDGP_LIK_GAMMA || kind == DSDGP_LIK_BETA) ? lik_const[0] : 1.0;
+  const double p0 = (F == LIKF_GAUSS || (F == LIKF_QUAD && lik_has_param(kind))) ? lik_const[0] : 1.0;
   const int64_t total = (int64_t)S * n * DY;
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   double ve = 0.0, dl = 0.0;
@@ -402,24 +325,25 @@ __global__ __launch_bounds__(256) void k_lik_gen(int kind, const double* __restr
     const int64_t row = idx / DY;
     const int dd = (int)(idx % DY);
     const double y = Y[(row % n) * DY + dd];
-    const double f = sw ? sw[row / n] * S : 1.0;
-    double dm, dv, dp;
-    ve = f * lik_var_exp(kind, mean[idx], var[idx], y, p0, aux, &dm, &dv, &dp);
+    const double f = sw ? sw[row / n] * S : 1.0;     // quadrature weight relative to the MC mean's 1/S (dgp.py:166)
+    double am, av, dp;
+    lik_ve<F>(kind, mean[idx], var[idx], y, p0, aux, -w * f, ve, am, av, dp);
+    ve = f * ve;
     dl = f * dp;
     if (dmean) {
-      dmean[idx] = -w * f * dm;
-      dvar[idx] = -w * f * dv;
+      dmean[idx] = am;
+      dvar[idx] = av;
     }
     if (MBt) {
-      MBt[(int64_t)dd * ldt + row] = -w * f * dm;
-      VBt[(int64_t)dd * ldt + row] = -w * f * dv;
+      MBt[(int64_t)dd * ldt + row] = am;
+      VBt[(int64_t)dd * ldt + row] = av;
     }
   } else if (MBt && idx < ldt * DY) {      // rows of the 16-row padding
     MBt[(idx % DY) * ldt + idx / DY] = 0.0;
     VBt[(idx % DY) * ldt + idx / DY] = 0.0;
   }
   const double a = block_sum_256(ve, sh);
-  const double b = block_sum_256(dl, sh);
+  const double b = (F == LIKF_BERN) ? 0.0 : block_sum_256(dl, sh);
   if (threadIdx.x == 0) {
     part[2 * blockIdx.x] = a;
     part[2 * blockIdx.x + 1] = b;
@@ -440,7 +364,7 @@ __global__ void k_scale_by_sample(const double* __restrict__ sw, int64_t n, int 
   }
 }
 
-// block partial sums of a vector (MultiClass variational expectations), same [blocks][2] layout as k_lik_gauss
+// block partial sums of a vector (MultiClass variational expectations), same [blocks][2] layout as k_lik_elbo
 __global__ __launch_bounds__(256) void k_partial_sum(const double* __restrict__ x, int64_t count, double* __restrict__ part) {
   __shared__ double sh[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;

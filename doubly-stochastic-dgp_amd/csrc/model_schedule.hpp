@@ -863,7 +863,7 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
   // the last layer of a deep model has one output row per input row: its transposed adjoints come straight from the
   // likelihood kernel (no k_adj_prep launch on the critical path) — or, Gaussian likelihood without quadrature weights, from the
   // last forward chain's own epilogue (no likelihood launch either)
-  const bool elementwise = m->desc.lik_kind == DSDGP_LIK_GAUSSIAN || m->desc.lik_kind == DSDGP_LIK_BERNOULLI || lik_is_generic(m->desc.lik_kind);
+  const bool elementwise = lik_family(m->desc.lik_kind) != LIKF_NONE;
   m->fused_last = with_grad && L > 1 && elementwise;
   const bool lik_in_chain = m->fused_last && m->desc.lik_kind == DSDGP_LIK_GAUSSIAN && !m->sample_w && m->force.lik_fuse != 0;
   int lik_nb = 0;
@@ -878,15 +878,10 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
     double* dv = (with_grad && !m->fused_last) ? m->lik_dvar : nullptr;
     double* mbt = m->fused_last ? last.MB : nullptr;
     double* vbt = m->fused_last ? last.VB : nullptr;
-    if (m->desc.lik_kind == DSDGP_LIK_GAUSSIAN)
-      DS_LAUNCH(k_lik_gauss, dim3(nblocks), dim3(256), 0, ctx->stream, last.mean, last.var, Y, n, S, DY, m->lik_const,
-                         w, m->sample_w, m->lik_part, dm, dv, mbt, vbt, ldt);
-    else if (m->desc.lik_kind == DSDGP_LIK_BERNOULLI)
-      DS_LAUNCH(k_lik_bern, dim3(nblocks), dim3(256), 0, ctx->stream, last.mean, last.var, Y, n, S, DY, w, m->sample_w,
-                         m->lik_part, dm, dv, mbt, vbt, ldt);
-    else
-      DS_LAUNCH(k_lik_gen, dim3(nblocks), dim3(256), 0, ctx->stream, (int)m->desc.lik_kind, (const double*)m->lik_const, m->desc.lik_aux,
-                         last.mean, last.var, Y, n, S, DY, w, m->sample_w, m->lik_part, dm, dv, mbt, vbt, ldt);
+    lik_dispatch(m->desc.lik_kind, [&](auto fam) {
+      DS_LAUNCH(k_lik_elbo<decltype(fam)::value>, dim3(nblocks), dim3(256), 0, ctx->stream, (int)m->desc.lik_kind, (const double*)m->lik_const,
+                m->desc.lik_aux, last.mean, last.var, Y, n, S, DY, w, m->sample_w, m->lik_part, dm, dv, mbt, vbt, ldt);
+    });
   } else {
     // MultiClass: Y is (n x 1) labels, the last layer has K = num_classes outputs; ve per (s, i) row -> last.F scratch
     DS_CHECK_ARG(DY == m->desc.num_classes);

@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib, settings
-from .gpflow_compat import (Bernoulli, Beta, Exponential, Gamma, Gaussian, MultiClass, Parameter, Poisson, StudentT, positive_backward, positive_forward, split_kernel)
+from .gpflow_compat import MultiClass, Parameter, likelihood_entry, positive_backward, positive_forward, split_kernel
 
 _KIND = {"rbf": _lib.KERN_RBF, "matern52": _lib.KERN_MATERN52}
 _MEAN = {"zero": _lib.MEAN_ZERO, "identity": _lib.MEAN_IDENTITY, "linear": _lib.MEAN_LINEAR}
@@ -165,45 +165,19 @@ class Engine:
             if mf_in_theta:
                 ld.trainable_mean_A = int(add(layer.mean_function.A, "id", "mean_A"))
                 ld.trainable_mean_b = int(add(layer.mean_function.b, "id", "mean_b"))
-        if isinstance(self.likelihood, Gaussian):
-            d.lik_kind = _lib.LIK_GAUSSIAN
-            p = self.likelihood.variance
+        d.lik_kind, p, const = likelihood_entry(self.likelihood)
+        if d.lik_kind == _lib.LIK_MULTICLASS:
+            d.num_classes = const
+        elif const is not None:
+            d.lik_aux = const
+        d.off_lik_var = -1
+        if p is not None:      # the likelihood's one positive parameter (Gaussian.variance, StudentT.scale, Gamma.shape, Beta.scale)
             self.entries.append((p, off, 1, "pos"))
             if self not in p._owners:
                 p._owners.append(self)
             d.off_lik_var = off
             d.trainable_lik_var = int(p.trainable)
             off += 1
-        elif isinstance(self.likelihood, MultiClass):
-            d.lik_kind = _lib.LIK_MULTICLASS
-            d.num_classes = self.likelihood.num_classes
-            d.off_lik_var = -1
-        elif isinstance(self.likelihood, Bernoulli):
-            d.lik_kind = _lib.LIK_BERNOULLI
-            d.off_lik_var = -1
-        elif isinstance(self.likelihood, Poisson):
-            d.lik_kind = _lib.LIK_POISSON
-            d.lik_aux = self.likelihood.binsize
-            d.off_lik_var = -1
-        elif isinstance(self.likelihood, Exponential):
-            d.lik_kind = _lib.LIK_EXPONENTIAL
-            d.off_lik_var = -1
-        elif isinstance(self.likelihood, (StudentT, Gamma, Beta)):
-            if isinstance(self.likelihood, StudentT):
-                d.lik_kind = _lib.LIK_STUDENT_T
-                d.lik_aux = self.likelihood.deg_free
-            else:
-                d.lik_kind = _lib.LIK_GAMMA if isinstance(self.likelihood, Gamma) else _lib.LIK_BETA
-            # the likelihood's one positive parameter (StudentT.scale, Gamma.shape, Beta.scale): the slot Gaussian.variance takes
-            p = self.likelihood.shape if isinstance(self.likelihood, Gamma) else self.likelihood.scale
-            self.entries.append((p, off, 1, "pos"))
-            if self not in p._owners:
-                p._owners.append(self)
-            d.off_lik_var = off
-            d.trainable_lik_var = int(p.trainable)
-            off += 1
-        else:
-            raise NotImplementedError(type(self.likelihood).__name__)
         d.n_theta = off
         self.n_theta = off
 
@@ -605,12 +579,9 @@ class Engine:
             if layer.mean_function.kind == "linear":
                 names[id(layer.mean_function.A)] = f"l{l}.mean_A"
                 names[id(layer.mean_function.b)] = f"l{l}.mean_b"
-        if isinstance(self.likelihood, Gaussian):
-            names[id(self.likelihood.variance)] = "lik_variance_raw"
-        if isinstance(self.likelihood, (StudentT, Beta)):
-            names[id(self.likelihood.scale)] = "lik_variance_raw"
-        if isinstance(self.likelihood, Gamma):
-            names[id(self.likelihood.shape)] = "lik_variance_raw"
+        p = likelihood_entry(self.likelihood)[1]
+        if p is not None:
+            names[id(p)] = "lik_variance_raw"
         for p, off, cnt, kind in self.entries:
             out[names[id(p)]] = g[off:off + cnt].reshape(p.shape).copy()
         return out

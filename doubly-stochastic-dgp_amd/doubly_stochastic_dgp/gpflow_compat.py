@@ -8,7 +8,7 @@ in libdsdgp (HIP).  [UPSTREAM] = behaviour of GPflow 1.1.1 that the reference re
 """
 import numpy as np
 
-from . import settings
+from . import _lib, settings
 
 SOFTPLUS_LOWER = 1e-6     # [UPSTREAM] transforms.positive = Log1pe(lower=1e-6)
 
@@ -297,6 +297,39 @@ class Beta(Likelihood):
         if invlink is not None:
             raise NotImplementedError("only the default probit link is on the built path")
         self.scale = Parameter(scale, transform="positive")
+
+
+# likelihood class -> (DSDGP_LIK_* kind, name of its positive Parameter or None, name of its constant attribute or None): the one place
+# that maps a likelihood to what the library is given.  The Parameter is the model's likelihood slot in theta and p0 of the primitives,
+# the constant lik_aux / p1 (MultiClass: num_classes of the model descriptor).
+LIKELIHOODS = {
+    Gaussian: (_lib.LIK_GAUSSIAN, "variance", None),
+    MultiClass: (_lib.LIK_MULTICLASS, None, "num_classes"),
+    Bernoulli: (_lib.LIK_BERNOULLI, None, None),
+    Poisson: (_lib.LIK_POISSON, None, "binsize"),
+    Exponential: (_lib.LIK_EXPONENTIAL, None, None),
+    StudentT: (_lib.LIK_STUDENT_T, "scale", "deg_free"),
+    Gamma: (_lib.LIK_GAMMA, "shape", None),
+    Beta: (_lib.LIK_BETA, "scale", None),
+}
+
+
+def likelihood_entry(lik):
+    """(kind, its positive Parameter or None, its constant or None) of a likelihood object; NotImplementedError for a class outside
+    LIKELIHOODS."""
+    for cls, (kind, par, const) in LIKELIHOODS.items():
+        if isinstance(lik, cls):
+            return kind, (getattr(lik, par) if par else None), (getattr(lik, const) if const else None)
+    raise NotImplementedError(f"likelihood {type(lik).__name__} is not on the built path "
+                              f"({', '.join(c.__name__ for c in LIKELIHOODS)} are)")
+
+
+def likelihood_args(lik):
+    """(kind, p0, p1) of the library's primitives: p0 = the positive Parameter's value, p1 = the constant; 1.0 where there is none
+    (MultiClass's class count is no p1)."""
+    kind, par, const = likelihood_entry(lik)
+    p1 = 1.0 if const is None or kind == _lib.LIK_MULTICLASS else const
+    return kind, (float(par.value) if par is not None else 1.0), p1
 
 
 class InducingPoints(Parameterized):

@@ -49,44 +49,24 @@ class BroadcastingLikelihood:
 
     def __init__(self, likelihood):
         self.likelihood = likelihood
-        from .gpflow_compat import Bernoulli, Beta, Exponential, Gamma, Gaussian, MultiClass, Poisson, StudentT
-        self.needs_broadcasting = not isinstance(likelihood, Gaussian)
-        self.bernoulli = isinstance(likelihood, Bernoulli)
+        from . import _lib
+        from .gpflow_compat import likelihood_entry
+        kind = likelihood_entry(likelihood)[0]      # (a class outside gpflow_compat.LIKELIHOODS raises here)
+        self.needs_broadcasting = kind != _lib.LIK_GAUSSIAN
+        self.bernoulli = kind == _lib.LIK_BERNOULLI
         # Poisson / Exponential / Gamma (exp link), StudentT, Beta: elementwise like Bernoulli, evaluated by dsdgp_lik_var_exp / dsdgp_lik_predict
-        self.generic = isinstance(likelihood, (Poisson, Exponential, StudentT, Gamma, Beta))
-        if not isinstance(likelihood, (Gaussian, MultiClass, Bernoulli, Poisson, Exponential, StudentT, Gamma, Beta)):
-            raise NotImplementedError(f"likelihood {type(likelihood).__name__} is not on the built path "
-                                      "(Gaussian, MultiClass, Bernoulli, Poisson, Exponential, StudentT, Gamma, Beta are)")
+        self.generic = kind not in (_lib.LIK_GAUSSIAN, _lib.LIK_MULTICLASS, _lib.LIK_BERNOULLI)
 
     def generic_args(self):
         """(kind, p0, p1) of dsdgp_lik_var_exp / dsdgp_lik_predict: p0 = StudentT.scale / Gamma.shape / Beta.scale, p1 = Poisson.binsize /
         StudentT.deg_free."""
-        from . import _lib
-        from .gpflow_compat import Beta, Exponential, Gamma, Poisson
-        lik = self.likelihood
-        if isinstance(lik, Poisson):
-            return _lib.LIK_POISSON, 1.0, lik.binsize
-        if isinstance(lik, Exponential):
-            return _lib.LIK_EXPONENTIAL, 1.0, 1.0
-        if isinstance(lik, Gamma):
-            return _lib.LIK_GAMMA, float(lik.shape.value), 1.0
-        if isinstance(lik, Beta):
-            return _lib.LIK_BETA, float(lik.scale.value), 1.0
-        return _lib.LIK_STUDENT_T, float(lik.scale.value), lik.deg_free
+        return self.mixture_args()
 
     def mixture_args(self):
-        """(kind, p0, p1) of dsdgp_eval_mixture for the wrapped likelihood: generic_args for the quadrature likelihoods, p0 = the noise
-        variance for the Gaussian, nothing for Bernoulli / MultiClass."""
-        from . import _lib
-        from .gpflow_compat import MultiClass
-        if not self.needs_broadcasting:
-            return _lib.LIK_GAUSSIAN, float(self.likelihood.variance.value), 1.0
-        if self.bernoulli:
-            return _lib.LIK_BERNOULLI, 1.0, 1.0
-        if self.generic:
-            return self.generic_args()
-        assert isinstance(self.likelihood, MultiClass)
-        return _lib.LIK_MULTICLASS, 1.0, 1.0
+        """(kind, p0, p1) of dsdgp_eval_mixture for the wrapped likelihood (gpflow_compat.likelihood_args): p0 = the noise variance for
+        the Gaussian, nothing for Bernoulli / MultiClass."""
+        from .gpflow_compat import likelihood_args
+        return likelihood_args(self.likelihood)
 
     def evaluate_mixture(self, Fmu, Fvar, Y, rows=False):
         """dsdgp_eval_mixture on (S, N, D) component means / variances and targets Y: the accumulator as a (3, D) array [squared error
@@ -165,11 +145,12 @@ class BroadcastingLikelihood:
         """(kind, C) of dsdgp_mixture_classification for the wrapped likelihood: MultiClass (C = num_classes) or Bernoulli (C = 2, one
         two-class problem per output); every other likelihood has no classes."""
         from . import _lib
-        from .gpflow_compat import MultiClass
-        if self.bernoulli:
-            return _lib.LIK_BERNOULLI, 2
-        if isinstance(self.likelihood, MultiClass):
-            return _lib.LIK_MULTICLASS, int(self.likelihood.num_classes)
+        from .gpflow_compat import likelihood_entry
+        kind, _, const = likelihood_entry(self.likelihood)
+        if kind == _lib.LIK_BERNOULLI:
+            return kind, 2
+        if kind == _lib.LIK_MULTICLASS:
+            return kind, int(const)
         raise NotImplementedError(f"{what}: {type(self.likelihood).__name__} has no classes; MultiClass and Bernoulli are covered")
 
     def mixture_classification(self, Fmu, Fvar, Y, bins=10, rows=False):

@@ -88,6 +88,36 @@ def test_var_exp_and_predict_primitives(name):
         assert np.isnan(out[5, 2]) and np.isfinite(np.delete(out.ravel(), 5 * D + 2)).all()
 
 
+@pytest.mark.parametrize("name", ["bernoulli", "student_t"])
+def test_dgp_quad_weighted_adjoints_match_oracle(name):
+    """DGP_Quad over a two-layer model: the likelihood kernel's quadrature-weight factor (sw[s] S) on the transposed adjoints that the
+    last layer's backward chain reads, for a likelihood without and one with a parameter of its own — ELBO and every gradient block
+    against the oracle's weighted restatement (tolerances of test_gpu_parity.test_dgp_quad_matches_oracle).  S N = 270 is no multiple of
+    16 (padding rows), S N DY = 270 leaves a ragged second workgroup."""
+    from doubly_stochastic_dgp.dgp import DGP_Quad
+    rng = np.random.RandomState(23)
+    N, D, M, H = 30, 2, 10, 3
+    X = rng.randn(N, D)
+    Y = np.where(rng.uniform(size=(N, 1)) < 0.5, -1.0, 1.0) if name == "bernoulli" else _targets(name, rng, N, 1)
+    Z = X[:M] + 0.01 * rng.randn(M, D)
+    specs = [kern_spec("rbf", D, 1.0, 0.8), kern_spec("matern52", D, 1.2, 1.1)]
+    if name == "bernoulli":
+        spec, state, model = make_case(X, Y, Z, specs, S=1, num_data=90, bernoulli=True)
+    else:
+        spec, state, model = make_case(X, Y, Z, specs, S=1, num_data=90, likelihood=name, lik_aux=4.5, lik_var=0.7)
+    quad = DGP_Quad(X, Y, model.likelihood.likelihood, model.layers, H=H, num_data=90)
+    assert quad.D_quad == 2 and quad.num_samples == H ** 2
+    zs, w = O.quad_points(H, [2])
+    ref, g = OM.elbo_and_grad(spec, state, X, Y, zs, H ** 2, num_data=90, sample_weights=w)
+    got = quad._build_likelihood(X, Y, with_grad=True)
+    assert_allclose(got, ref, rtol=1e-9)
+    grads = quad.engine().gradient_dict()
+    assert ("lik_variance_raw" in g) == (name == "student_t") and set(g) <= set(grads)
+    for k in g:
+        err = np.max(np.abs(-g[k] - grads[k])) / (np.max(np.abs(g[k])) + 1e-12)
+        assert err <= 1e-7, (k, err)
+
+
 def test_c_abi_rejects_bad_kinds_and_parameters():
     import ctypes as C
     from doubly_stochastic_dgp import _lib
