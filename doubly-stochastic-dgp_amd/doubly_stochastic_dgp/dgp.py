@@ -7,7 +7,7 @@ import numpy as np
 
 from . import _lib
 from .gpflow_compat import Gaussian, Parameterized, Zero
-from .layer_initializations import init_layers_linear, kmeans_inducing
+from .layer_initializations import greedy_inducing, init_layers_linear, kmeans_inducing
 from .distributed import shard_terms
 from .utils import BroadcastingLikelihood
 
@@ -600,11 +600,22 @@ class DGP_Quad(DGP_Base):
 
 class DGP(DGP_Base):
     """The doubly-stochastic DGP with linear/identity mean functions (dgp.py:169-192).  Z: the (M, D) inducing inputs, or an integer M
-    for kmeans_inducing(X, M, seed=0) — the kmeans2 call of demos/run_regression.py:57, on the device."""
+    for kmeans_inducing(X, M, seed=0) — the kmeans2 call of demos/run_regression.py:57, on the device.  inducing (read only when Z is
+    an integer): "kmeans", or "greedy" for greedy_inducing(X, M, kernels[0]) — the conditional-variance rule under the first layer's
+    kernel; ValueError if fewer than M rows pass its threshold (settings.jitter)."""
 
-    def __init__(self, X, Y, Z, kernels, likelihood, num_outputs=None, mean_function=None, white=False, **kwargs):
+    def __init__(self, X, Y, Z, kernels, likelihood, num_outputs=None, mean_function=None, white=False, inducing="kmeans", **kwargs):
         if isinstance(Z, (int, np.integer)) and not isinstance(Z, bool):
-            Z = kmeans_inducing(X, int(Z), seed=0)
+            if inducing not in ("kmeans", "greedy"):
+                raise ValueError(f"inducing = {inducing!r}: 'kmeans' or 'greedy'")
+            if inducing == "greedy":
+                M = int(Z)
+                Z = greedy_inducing(X, M, kernels[0])
+                if Z.shape[0] < M:
+                    raise ValueError(f"inducing='greedy': only {Z.shape[0]} of the M = {M} rows asked for have a conditional variance "
+                                     "above the threshold (settings.jitter); ask for fewer")
+            else:
+                Z = kmeans_inducing(X, int(Z), seed=0)
         layers = init_layers_linear(X, Y, Z, kernels, num_outputs=num_outputs,
                                     mean_function=Zero() if mean_function is None else mean_function, white=white)
         DGP_Base.__init__(self, X, Y, likelihood, layers, **kwargs)

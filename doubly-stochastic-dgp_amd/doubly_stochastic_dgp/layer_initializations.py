@@ -5,10 +5,13 @@ import ctypes as C
 
 import numpy as np
 
-from .gpflow_compat import Identity, Linear, Zero
+from . import settings
+from .gpflow_compat import Identity, Linear, Stationary, Zero, split_kernel
 from .layers import SVGP_Layer
 
 KMEANS_MAX_M, KMEANS_MAX_D = 2048, 1024          # KM_MAX_M, KM_MAX_D of csrc/kmeans.hip
+GREEDY_MAX_M, GREEDY_MAX_D = 2048, 1024          # GR_MAX_M, GR_MAX_D of csrc/greedy.hip
+_GREEDY_KIND = {"rbf": 0, "matern52": 1}         # DSDGP_KERN_*
 
 
 def _kmeans_args(X, M, iter, init):
@@ -91,6 +94,90 @@ def kmeans_inducing(X, M, iter=10, seed=0, init=None, return_info=False):
     if not return_info:
         return Zh
     return Zh, {"labels": labels.cpu().numpy(), "counts": counts.cpu().numpy(), "inertia": float(inertia.cpu().numpy()[0])}
+
+
+def _greedy_args(X, M, kernel, first, threshold):
+    """Everything greedy_inducing can refuse without a device -> (n, D, M, first or -1, threshold, kind, ard, variance, white variance
+    or None, lengthscales); called before the engine's context is touched, as _kmeans_args is."""
+    on_device = hasattr(X, "data_ptr")
+    if not on_device:
+        X = np.asarray(X)
+    if len(X.shape) != 2:
+        raise ValueError(f"X must be a 2-D (n, D) array, not one of shape {tuple(X.shape)}")
+    n, D = int(X.shape[0]), int(X.shape[1])
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)):
+        raise ValueError(f"M must be an integer, not {M!r}")
+    M = int(M)
+    if not 2 <= M <= GREEDY_MAX_M:
+        raise ValueError(f"M = {M} outside 2 .. {GREEDY_MAX_M}")
+    if not 1 <= D <= GREEDY_MAX_D:
+        raise ValueError(f"D = {D} outside 1 .. {GREEDY_MAX_D}")
+    if M > n:
+        raise ValueError(f"M = {M} points from n = {n} rows")
+    if n >= 2 ** 31:
+        raise ValueError(f"n = {n}: at most 2^31 - 1 rows")
+    if first is None:
+        first = -1
+    else:
+        if isinstance(first, bool) or not isinstance(first, (int, np.integer)):
+            raise ValueError(f"first must be a row index, not {first!r}")
+        first = int(first)
+        if not 0 <= first < n:
+            raise ValueError(f"first = {first} outside 0 .. {n - 1}")
+    threshold = float(settings.jitter if threshold is None else threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"threshold = {threshold}: a non-negative number")
+    try:
+        stat, white = split_kernel(kernel)
+    except NotImplementedError as e:
+        raise ValueError(str(e))
+    if not isinstance(stat, Stationary) or stat.kind not in _GREEDY_KIND:
+        raise ValueError(f"kernel {type(stat).__name__} is neither RBF nor Matern52")
+    if int(stat.input_dim) != D:
+        raise ValueError(f"the kernel's input_dim = {stat.input_dim} is not D = {D}")
+    if not on_device and not np.all(np.isfinite(np.asarray(X, dtype=np.float64))):
+        raise ValueError("X holds a non-finite value")
+    ls = np.ascontiguousarray(np.asarray(stat.lengthscales.value, dtype=np.float64).reshape(-1))
+    return (n, D, M, first, threshold, _GREEDY_KIND[stat.kind], int(stat.ARD), float(stat.variance.value),
+            None if white is None else float(white.variance.value), ls)
+
+
+def greedy_inducing(X, M, kernel, first=None, threshold=None, return_info=False):
+    """Inducing inputs by the greedy conditional-variance rule on the device (the pivoted Cholesky factorisation of K(X, X);
+    "ConditionalVariance" of Burt, Rasmussen and van der Wilk 2020): each step takes the row of X whose variance under `kernel`,
+    conditioned on the rows already chosen, is largest (ties: the lowest row).  X: numpy array or device tensor (n, D).  kernel: a
+    gpflow_compat RBF or Matern52 (scalar or ARD lengthscales), alone or in a sum with White, mapped as the engine maps a layer's kernel.
+    first: the row to start from (default: row 0, every row having the same prior variance).  The selection stops early at the first
+    row whose conditional variance is <= threshold; None means settings.jitter — a pivot below what Ku gets added to its diagonal is
+    one the jitter dominates.  Returns Z (m, D) as numpy, m <= M, its rows bit copies of rows of X; with return_info also a dict:
+    `indices` (m,) int32, `m`, `residual` (m,): the conditional variance of each row when it was chosen, `trace` (m,): tr(Kff - Qff)
+    after 1 .. m points — the quantity that bounds the gap of the sparse approximation, so the answer to "is M large enough?" — and
+    `L` (m, m): the lower Cholesky factor of k(Z, Z) (+ White) in pivot order.  The same arguments give the same bits on every call.
+    ValueError, before any device is looked for: X not 2-D, M outside 2 .. 2048, D outside 1 .. 1024, M > n, first outside 0 .. n-1, a
+    negative or NaN threshold, a non-finite value in a numpy X, a kernel whose input_dim is not D or that is not RBF / Matern52 (+ White)."""
+    n, D, M, first, threshold, kind, ard, variance, wvar, ls = _greedy_args(X, M, kernel, first, threshold)
+    from . import _lib
+    from .engine import Context
+    ctx = Context.get()
+    torch = ctx.torch
+    dev = f"cuda:{ctx.device}"
+    spec = _lib.KernelSpec(kind=kind, input_dim=D, ard=ard, has_white=int(wvar is not None), variance=variance,
+                           white_variance=0.0 if wvar is None else wvar, lengthscales=ls.ctypes.data_as(_lib.c_double_p))
+    with torch.cuda.stream(ctx.tstream):
+        Xd = X.to(device=dev, dtype=torch.float64).contiguous() if hasattr(X, "data_ptr") else ctx.to_device(X)
+        idx = torch.empty(M, dtype=torch.int32, device=dev)
+        m_out = torch.empty(1, dtype=torch.int32, device=dev)
+        Z, res, tr, L = ctx.empty(M, D), ctx.empty(M), ctx.empty(M), ctx.empty(M, M)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(ctx.lib.dsdgp_greedy_inducing(ctx.handle, C.byref(spec), p(Xd), n, M, first, threshold, p(idx), p(m_out), p(Z), p(res),
+                                             p(tr), p(L), M))
+    ctx.sync()
+    m = int(m_out.cpu().numpy()[0])
+    Zh = Z.cpu().numpy()[:m].copy()
+    if not return_info:
+        return Zh
+    return Zh, {"indices": idx.cpu().numpy()[:m].copy(), "m": m, "residual": res.cpu().numpy()[:m].copy(),
+                "trace": tr.cpu().numpy()[:m].copy(), "L": L.cpu().numpy()[:m, :m].copy()}
 
 
 def _width_map(d_from, d_to, cloud):

@@ -448,6 +448,29 @@ int dsdgp_model_classification(dsdgp_model* m, const double* X, const double* Y,
 int dsdgp_kmeans(dsdgp_ctx* ctx, const double* X, int64_t n, int32_t D, int32_t M, const double* Z0, int32_t iters, double* Z,
                  int32_t* labels, int64_t* counts, double* inertia);
 
+/* dsdgp_greedy_inducing: greedy conditional-variance selection of the inducing points — the pivoted Cholesky factorisation of
+ * K(X, X) ("ConditionalVariance" of Burt, Rasmussen and van der Wilk 2020) on the device.  X (device, n x D, row-major, D =
+ * kern->input_dim); kern as for dsdgp_gram (RBF or Matern52, scalar or ARD lengthscales, optional White part).
+ *   d_i = kern.Kdiag (variance + white_variance);  for j = 0 .. M-1:  p_j = `first` if j == 0 and first >= 0, else argmax_i d_i over the
+ *   rows not yet chosen (ties: the lowest i; a NaN never wins);  stop if d_p <= threshold (m = j points);  c_j[i] = (k(x_i, x_p) -
+ *   sum_{t<j} c_t[i] c_t[p]) / sqrt(d_p);  d_i = max(d_i - c_j[i]^2, 0), d_p = 0;  trace_j = sum_i d_i = tr(Kff - Qff) of the first j + 1 points.
+ * All M steps are enqueued on the context's stream; the host does not wait and the chosen row never visits it.
+ *   idx (device, M x int32): p_0 .. p_{m-1};  m_out (device, 1 x int32): m.
+ *   Z (device, M x D, or NULL): the chosen rows, bit copies of rows of X;  residual (device, M, or NULL): d_p at the time row p was
+ *   chosen;  trace (device, M, or NULL): trace_j;  L (device, M x ldl, or NULL): L[j][t] = c_t[p_j] (t < j), L[j][j] = sqrt(residual_j),
+ *   zero above — the lower Cholesky factor of k(Z, Z) (+ white_variance I) in pivot order; the columns M .. ldl of L are not written.
+ *   Entries j >= m after an early stop: idx -1, residual 0, trace = trace_{m-1} (tr K(X, X) if m = 0), zero rows of Z and L.
+ * r^2 is formed from differences of rows, never from |x|^2 + |z|^2 - 2 x.z.  Every sum runs in a fixed order (sum_t ascending in t, no
+ * floating-point atomics) and a row's arithmetic does not depend on where the row sits: the same arguments give the same bits on every
+ * call and every rank, and two bit-identical rows of X tie exactly (the lower index wins).  Step j moves 8 n (D + j + 3) bytes.
+ * DSDGP_ERR_BAD_ARG (nothing launched, no output touched) for n < M, n >= 2^31, M outside 2..2048, kern->input_dim outside 1..1024, a
+ * kind other than RBF / Matern52, first outside -1 .. n-1, a negative or NaN threshold, a NULL X / idx / m_out, or L with ldl < M.
+ * DSDGP_ERR_UNSUPPORTED when the M x n column store (or the D x n transposed copy of X) would exceed 2^30 doubles (8 GB of scratch):
+ * pass a subset of the rows. */
+int dsdgp_greedy_inducing(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* X, int64_t n, int32_t M, int64_t first,
+                          double threshold, int32_t* idx, int32_t* m_out, double* Z, double* residual, double* trace, double* L,
+                          int64_t ldl);
+
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
 
