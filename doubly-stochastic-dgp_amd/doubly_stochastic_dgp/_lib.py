@@ -141,6 +141,8 @@ _PROTOS = {
                                C.c_void_p, C.c_void_p]),
     "dsdgp_greedy_inducing": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_double,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "dsdgp_pca": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsdgp_model_set_grad_first_layer": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),

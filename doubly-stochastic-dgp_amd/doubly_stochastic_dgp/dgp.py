@@ -602,9 +602,13 @@ class DGP(DGP_Base):
     """The doubly-stochastic DGP with linear/identity mean functions (dgp.py:169-192).  Z: the (M, D) inducing inputs, or an integer M
     for kmeans_inducing(X, M, seed=0) — the kmeans2 call of demos/run_regression.py:57, on the device.  inducing (read only when Z is
     an integer): "kmeans", or "greedy" for greedy_inducing(X, M, kernels[0]) — the conditional-variance rule under the first layer's
-    kernel; ValueError if fewer than M rows pass its threshold (settings.jitter)."""
+    kernel; ValueError if fewer than M rows pass its threshold (settings.jitter).  pca: "host" (np.linalg.svd, as the reference) or
+    "device" (layer_initializations.pca_map) for the step-down mean functions of init_layers_linear."""
 
-    def __init__(self, X, Y, Z, kernels, likelihood, num_outputs=None, mean_function=None, white=False, inducing="kmeans", **kwargs):
+    def __init__(self, X, Y, Z, kernels, likelihood, num_outputs=None, mean_function=None, white=False, inducing="kmeans", pca="host",
+                 **kwargs):
+        if pca not in ("host", "device"):
+            raise ValueError(f"pca = {pca!r}: 'host' or 'device'")
         if isinstance(Z, (int, np.integer)) and not isinstance(Z, bool):
             if inducing not in ("kmeans", "greedy"):
                 raise ValueError(f"inducing = {inducing!r}: 'kmeans' or 'greedy'")
@@ -617,5 +621,5 @@ class DGP(DGP_Base):
             else:
                 Z = kmeans_inducing(X, int(Z), seed=0)
         layers = init_layers_linear(X, Y, Z, kernels, num_outputs=num_outputs,
-                                    mean_function=Zero() if mean_function is None else mean_function, white=white)
+                                    mean_function=Zero() if mean_function is None else mean_function, white=white, pca=pca)
         DGP_Base.__init__(self, X, Y, likelihood, layers, **kwargs)

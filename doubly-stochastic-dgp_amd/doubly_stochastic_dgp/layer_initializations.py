@@ -12,6 +12,7 @@ from .layers import SVGP_Layer
 KMEANS_MAX_M, KMEANS_MAX_D = 2048, 1024          # KM_MAX_M, KM_MAX_D of csrc/kmeans.hip
 GREEDY_MAX_M, GREEDY_MAX_D = 2048, 1024          # GR_MAX_M, GR_MAX_D of csrc/greedy.hip
 _GREEDY_KIND = {"rbf": 0, "matern52": 1}         # DSDGP_KERN_*
+PCA_MAX_D, PCA_MAX_SWEEPS = 1024, 64             # PCA_MAX_D, PCA_MAX_SWEEPS of csrc/pca.hip
 
 
 def _kmeans_args(X, M, iter, init):
@@ -180,13 +181,93 @@ def greedy_inducing(X, M, kernel, first=None, threshold=None, return_info=False)
                 "trace": tr.cpu().numpy()[:m].copy(), "L": L.cpu().numpy()[:m, :m].copy()}
 
 
-def _width_map(d_from, d_to, cloud):
+def _pca_args(X, k, max_sweeps):
+    """Everything pca_map can refuse without a device -> (n, D, k, max_sweeps); called before the engine's context is touched, as
+    _kmeans_args is."""
+    on_device = hasattr(X, "data_ptr")
+    if not on_device:
+        X = np.asarray(X)
+    if len(X.shape) != 2:
+        raise ValueError(f"X must be a 2-D (n, D) array, not one of shape {tuple(X.shape)}")
+    n, D = int(X.shape[0]), int(X.shape[1])
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k must be an integer, not {k!r}")
+    if isinstance(max_sweeps, bool) or not isinstance(max_sweeps, (int, np.integer)):
+        raise ValueError(f"max_sweeps must be an integer, not {max_sweeps!r}")
+    k, max_sweeps = int(k), int(max_sweeps)
+    if not 1 <= D <= PCA_MAX_D:
+        raise ValueError(f"D = {D} outside 1 .. {PCA_MAX_D}")
+    if not 1 <= k <= D:
+        raise ValueError(f"k = {k} outside 1 .. D = {D}")
+    if n < 1:
+        raise ValueError("X has no rows")
+    if n >= 2 ** 31:
+        raise ValueError(f"n = {n}: at most 2^31 - 1 rows")
+    if not 1 <= max_sweeps <= PCA_MAX_SWEEPS:
+        raise ValueError(f"max_sweeps = {max_sweeps} outside 1 .. {PCA_MAX_SWEEPS}")
+    if not on_device and not np.all(np.isfinite(np.asarray(X, dtype=np.float64))):
+        raise ValueError("X holds a non-finite value")
+    return n, D, k, max_sweeps
+
+
+def pca_map(X, k, center=False, max_sweeps=30, return_info=False):
+    """The step-down map of init_layers_linear on the device: the top k right singular vectors of X, which the reference takes from
+    np.linalg.svd(X, full_matrices=False) (layer_initializations.py:35), as the top k eigenvectors of C = X^T X (center=False, what
+    svd(X) diagonalises) or of the centred (X - mean)^T (X - mean) (center=True).  X: numpy array or device tensor (n, D).  C is formed
+    on the fp64 MFMA pipe and diagonalised by a round-robin two-sided Jacobi iteration, at most max_sweeps sweeps, all on the device.
+    Returns T (D, k) as numpy: column j is the unit eigenvector of the j-th largest eigenvalue, its entry of largest magnitude positive
+    (ties: the lowest row) — np.linalg.svd's rows up to that sign.  The same arguments give the same bits on every call and every rank.
+    With return_info also a dict: `eigenvalues` (D,), non-increasing; `singular_values` (D,) = sqrt(max(eigenvalues, 0)); `explained`
+    (D,) = cumsum(max(eigenvalues, 0)) / sum(max(eigenvalues, 0)) (zeros if the sum is zero): the share of tr(C) the first 1 .. D
+    directions carry, so explained[k - 1] answers "is the narrower width wide enough?"; `mean` (D,): the column means (zeros when
+    center=False); `gram` (D, D): C as the device formed it; `sweeps`; `converged`.
+    RuntimeError if the iteration has not converged after max_sweeps sweeps — unless return_info is set: then the caller reads the flag.
+    ValueError, before any device is looked for: X not 2-D, k not an integer or outside 1 .. D, D outside 1 .. 1024, no rows,
+    max_sweeps outside 1 .. 64, a non-finite value in a numpy X."""
+    n, D, k, max_sweeps = _pca_args(X, k, max_sweeps)
+    from . import _lib
+    from .engine import Context
+    ctx = Context.get()
+    torch = ctx.torch
+    dev = f"cuda:{ctx.device}"
+    with torch.cuda.stream(ctx.tstream):
+        Xd = X.to(device=dev, dtype=torch.float64).contiguous() if hasattr(X, "data_ptr") else ctx.to_device(X)
+        W, evals, mean, gram = ctx.empty(D, k), ctx.empty(D), ctx.empty(D), ctx.empty(D, D)
+        info = torch.empty(4, dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _lib.check(ctx.lib.dsdgp_pca(ctx.handle, p(Xd), n, D, k, int(bool(center)), max_sweeps, p(W), k, p(evals), p(mean), p(gram), p(info)))
+    ctx.sync()
+    T = W.cpu().numpy()
+    flags = info.cpu().numpy()
+    converged, sweeps = bool(flags[0]), int(flags[1])
+    if not return_info:
+        if not converged:
+            raise RuntimeError(f"pca_map: the Jacobi iteration has not converged after {sweeps} sweeps ({int(flags[2])} rotations in "
+                               "the last one); raise max_sweeps")
+        return T
+    lam = evals.cpu().numpy()
+    pos = np.maximum(lam, 0.0)
+    total = pos.sum()
+    return T, {"eigenvalues": lam, "singular_values": np.sqrt(pos), "explained": np.cumsum(pos) / total if total > 0 else np.zeros(D),
+               "mean": mean.cpu().numpy(), "gram": gram.cpu().numpy(), "sweeps": sweeps, "converged": converged}
+
+
+def _check_pca(pca):
+    if pca not in ("host", "device"):
+        raise ValueError(f"pca = {pca!r}: 'host' or 'device'")
+
+
+def _width_map(d_from, d_to, cloud, pca="host"):
     """The fixed linear map between two layer widths, or None when they agree (identity mean function).
-    narrower: the top `d_to` right singular vectors of `cloud` (the data as seen at this depth) — a PCA projection;
+    narrower: the top `d_to` right singular vectors of `cloud` (the data as seen at this depth) — a PCA projection; pca="host":
+              numpy's SVD of the whole cloud, pca="device": pca_map(cloud, d_to);
     wider:    [I | 0], the extra coordinates start at zero."""
+    _check_pca(pca)
     if d_from == d_to:
         return None
     if d_from > d_to:
+        if pca == "device":
+            return pca_map(cloud, d_to)
         right = np.linalg.svd(cloud, full_matrices=False)[2]
         return right[:d_to].T.copy()
     out = np.zeros((d_from, d_to))
@@ -194,13 +275,13 @@ def _width_map(d_from, d_to, cloud):
     return out
 
 
-def _plan_widths(X, Z, widths):
+def _plan_widths(X, Z, widths, pca="host"):
     """[(inducing inputs, output width, map-or-None)] for every inner boundary, plus the inducing inputs of the last layer.
     Data and inducing inputs are carried through the maps together so that each layer's Z lives in that layer's input space."""
     cloud, ind = np.array(X, dtype=np.float64), np.array(Z, dtype=np.float64)
     plan = []
     for d_from, d_to in zip(widths[:-1], widths[1:]):
-        T = _width_map(d_from, d_to, cloud)
+        T = _width_map(d_from, d_to, cloud, pca)
         plan.append((ind, d_to, T))
         if T is not None:
             cloud, ind = cloud @ T, ind @ T
@@ -213,12 +294,14 @@ def _frozen_linear(T):
     return mf
 
 
-def init_layers_linear(X, Y, Z, kernels, num_outputs=None, mean_function=None, Layer=SVGP_Layer, white=False):
+def init_layers_linear(X, Y, Z, kernels, num_outputs=None, mean_function=None, Layer=SVGP_Layer, white=False, pca="host"):
     """Inner layers get an identity mean where consecutive kernels share their input width and a fixed linear map where they do
-    not (see `_width_map`); the last layer gets `mean_function` (default Zero) and `num_outputs` (default: columns of Y)."""
+    not (see `_width_map`); the last layer gets `mean_function` (default Zero) and `num_outputs` (default: columns of Y).
+    pca: where the step-down maps are computed, "host" (np.linalg.svd, as the reference) or "device" (pca_map)."""
+    _check_pca(pca)
     final_mean = Zero() if mean_function is None else mean_function
     n_out = num_outputs or Y.shape[1]
-    plan, Z_last = _plan_widths(X, Z, [k.input_dim for k in kernels])
+    plan, Z_last = _plan_widths(X, Z, [k.input_dim for k in kernels], pca)
     layers = [Layer(k, Zl, width, Identity() if T is None else _frozen_linear(T), white=white)
               for k, (Zl, width, T) in zip(kernels[:-1], plan)]
     layers.append(Layer(kernels[-1], Z_last, n_out, final_mean, white=white))

@@ -60,7 +60,7 @@ int dsdgp_ctx_destroy(dsdgp_ctx* ctx);
 int dsdgp_sync(dsdgp_ctx* ctx);
 /* HIP-event timing of the most recent launch of a named kernel class on the ctx stream (bench.py roofline):
  * enable, run, then read the accumulated milliseconds and launch count. name in
- * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration"}. */
+ * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig"}. */
 int dsdgp_prof_enable(dsdgp_ctx* ctx, int on);
 int dsdgp_prof_read(dsdgp_ctx* ctx, const char* name, double* total_ms, int64_t* launches, int reset);
 /* Kernel launches this library has enqueued in this process so far (all contexts; memsets / copies not counted): the difference
@@ -470,6 +470,33 @@ int dsdgp_kmeans(dsdgp_ctx* ctx, const double* X, int64_t n, int32_t D, int32_t 
 int dsdgp_greedy_inducing(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* X, int64_t n, int32_t M, int64_t first,
                           double threshold, int32_t* idx, int32_t* m_out, double* Z, double* residual, double* trace, double* L,
                           int64_t ldl);
+
+/* dsdgp_pca: the PCA behind the step-down mean functions — the top k right singular vectors of X, which the reference's
+ * init_layers_linear takes from np.linalg.svd(X, full_matrices=False) (layer_initializations.py:35) — as the top k eigenvectors of
+ * the D x D matrix C on the device.  X (device, n x D, row-major).
+ *   center = 0: C = X^T X (what svd(X) diagonalises; the reference does not centre);  center = 1: C = (X - 1 mean^T)^T (X - 1 mean^T),
+ *   mean = the column means, subtracted from the rows as they are staged (X^T X - n mean mean^T is never formed).
+ *   C = V diag(lambda) V^T by two-sided Jacobi in the round-robin ordering (D padded to even, D - 1 or D steps of disjoint pairs per sweep):
+ *   pair (p, q) is skipped when |a_pq| <= 2^-53 sqrt(|a_pp a_qq|), else theta = (a_qq - a_pp) / (2 a_pq), t = sgn(theta) / (|theta| +
+ *   sqrt(theta^2 + 1)), sgn(0) = 1.  After each sweep off = sqrt(sum_{i != j} a_ij^2) is measured from the entries themselves; the
+ *   iteration has converged when off <= D 2^-52 |C|_F or a sweep rotated nothing.  max_sweeps sweeps are enqueued; the steps after
+ *   convergence return at once.
+ *   W (device, D x ldw): column j < k = the unit eigenvector of the j-th largest eigenvalue, its entry of largest magnitude positive (ties:
+ *            the lowest row); the columns k .. ldw are not written.
+ *   evals (device, D, or NULL): all D eigenvalues, non-increasing; equal eigenvalues keep the order of their index in the solver's diagonal.
+ *   mean (device, D, or NULL): the column means (center = 1) or zeros (center = 0).
+ *   gram (device, D x D, or NULL): C as the device formed it, exactly symmetric.
+ *   info (device, 4 x int32, or NULL): {converged, sweeps run, rotations applied in the last sweep, 0}.
+ * Everything is enqueued on the context's stream; the host does not wait.  C is formed on the fp64 MFMA pipe from the 64 x 64 tiles on or
+ * below its diagonal, the rows of X split over workgroups and the partial tiles added in ascending split order; no floating-point atomics
+ * anywhere and no kernel waits for another workgroup: the same X, k, center and max_sweeps give the same bits on every call and every
+ * rank.  The Gram launch reads 8 n 128 bytes of X per off-diagonal tile (8 n 64 per diagonal one, mostly from L2) and writes 32 KB per
+ * (tile, split); a Jacobi step reads and writes the two Dp x Dp matrices A and V once: 32 Dp^2 bytes.
+ * DSDGP_ERR_BAD_ARG (nothing launched, no output touched) for n < 1, n >= 2^31, D outside 1..1024, k outside 1..D, center outside {0, 1},
+ * max_sweeps outside 1..64, ldw < k or a NULL X / W.  DSDGP_ERR_UNSUPPORTED if the partial tiles of one row split exceeded 256 MB of
+ * scratch (they are 4.5 MB at D = 1024; the number of splits is chosen so that all of them stay below that cap). */
+int dsdgp_pca(dsdgp_ctx* ctx, const double* X, int64_t n, int32_t D, int32_t k, int32_t center, int32_t max_sweeps, double* W, int64_t ldw,
+              double* evals, double* mean, double* gram, int32_t* info);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
