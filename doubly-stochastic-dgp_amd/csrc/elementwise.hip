@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_lik_over_samples(int kind, double p0, d
       double acc = 0.0;
       for (int s = 0; s < S; ++s) {
         const double l = lik_density<F>(kind, mean[(int64_t)s * total + i], var[(int64_t)s * total + i], y, p0, p1);
-        acc += exp(l - mx);
+        acc += (l == mx) ? 1.0 : exp(l - mx);      // (every component -inf: no NaN, the result stays -inf — evaluate.hip's lse_add)
       }
       out[i] = mx + log(acc) - log((double)S);
     }

@@ -437,6 +437,48 @@ extern "C" int dsdgp_model_layer_matrix(dsdgp_model* m, int32_t l, int32_t which
   return DSDGP_OK;
 }
 
+// Read-out of the training step's element-wise likelihood launch (verification aid: nothing on the evaluation path calls it): the
+// SAME k_lik_elbo<F> instance on the grid elbo_impl gives it, on the caller's device arrays.  Row-major adjoints (dmean / dvar), the
+// transposed zero-padded ones (MBt / VBt, DY x ldt), or the values alone; part = the raw [blocks][2] partial sums.
+extern "C" int dsdgp_lik_elbo_readout(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const double* mean, const double* var,
+                                      const double* Y, int64_t n, int32_t S, int32_t DY, double w, const double* sample_w,
+                                      double* part, double* dmean, double* dvar, double* MBt, double* VBt, int64_t ldt) {
+  DS_CHECK_ARG(ctx && mean && var && Y && part && n > 0 && S > 0 && DY > 0);
+  DS_CHECK_ARG(lik_params_ok(kind, p0, p1));
+  DS_CHECK_ARG(!dmean == !dvar && !MBt == !VBt && !(dmean && MBt));
+  const int64_t R = (int64_t)S * n, total = R * DY;
+  DS_CHECK_ARG(!MBt || ldt >= R);
+  const int64_t cover = MBt ? ldt * DY : total;      // elbo_impl: fused_last launches over the padded rows as well
+  DS_CHECK_ARG((cover + 255) / 256 <= 0x7fffffff);
+  const int nblocks = ceil_div(cover, 256);
+  void* scr;
+  DS_TRY(ctx_scratch(ctx, 2 * sizeof(double), &scr));
+  const double lc[2] = {p0, 0.0};
+  DS_TRY(ctx_upload(ctx, scr, lc, sizeof(lc)));
+  lik_dispatch(kind, [&](auto fam) {
+    DS_LAUNCH(k_lik_elbo<decltype(fam)::value>, dim3(nblocks), dim3(256), 0, ctx->stream, (int)kind, (const double*)scr, p1, mean, var, Y, n,
+              (int)S, (int)DY, w, sample_w, part, dmean, dvar, MBt, VBt, ldt);
+  });
+  DS_HIP(hipGetLastError());
+  return DSDGP_OK;
+}
+
+// The same for MultiClass: multiclass_launch in mode 0 with adjoints, then k_scale_by_sample when quadrature weights are given, as
+// elbo_impl runs them.  ve: (S n) per-row values, dmean / dvar: (S n x K).  Y holds labels in [0, K): the kernel indexes with them.
+extern "C" int dsdgp_multiclass_readout(dsdgp_ctx* ctx, const double* mean, const double* var, const double* Y, int64_t n, int32_t S,
+                                        int32_t K, double w, const double* sample_w, double* ve, double* dmean, double* dvar) {
+  DS_CHECK_ARG(ctx && mean && var && Y && ve && dmean && dvar && n > 0 && S > 0);
+  const int64_t R = (int64_t)S * n;
+  DS_TRY(multiclass_launch(ctx, mean, var, Y, n, R, K, 0, w, ve, dmean, dvar, -1));
+  if (sample_w) {
+    const int64_t cnt = R * K;
+    DS_LAUNCH(k_scale_by_sample, dim3((int)std::min<int64_t>(2048, ceil_div(cnt, 256))), dim3(256), 0, ctx->stream, sample_w, n, (int)S,
+              (int)K, R, ve, dmean, dvar);
+  }
+  DS_HIP(hipGetLastError());
+  return DSDGP_OK;
+}
+
 extern "C" int dsdgp_model_layer_conditional(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean,
                                              double* var) {
   DS_CHECK_ARG(m && X && mean && var && l >= 0 && l < m->desc.L && n > 0);

@@ -132,7 +132,10 @@ __global__ void k_over_samples(const double* __restrict__ tmp, int64_t n, int S,
       double mx = -1.0 / 0.0;
       for (int s = 0; s < S; ++s) mx = fmax(mx, tmp[(int64_t)s * n + i]);
       double a = 0.0;
-      for (int s = 0; s < S; ++s) a += exp(tmp[(int64_t)s * n + i] - mx);
+      for (int s = 0; s < S; ++s) {      // (every component -inf: no NaN, the result stays -inf — evaluate.hip's lse_add)
+        const double l = tmp[(int64_t)s * n + i];
+        a += (l == mx) ? 1.0 : exp(l - mx);
+      }
       out[i] = mx + log(a) - log((double)S);
     }
   }

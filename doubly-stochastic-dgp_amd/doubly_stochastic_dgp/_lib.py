@@ -121,6 +121,11 @@ _PROTOS = {
                                     C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]),
     "dsdgp_lik_predict": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_void_p]),
+    "dsdgp_lik_elbo_readout": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int64]),
+    "dsdgp_multiclass_readout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsdgp_eval_mixture": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]),
     "dsdgp_model_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),

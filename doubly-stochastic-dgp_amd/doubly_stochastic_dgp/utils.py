@@ -41,6 +41,91 @@ def mvhermgauss(H, D):
     return x.reshape(int(H) ** int(D), int(D)), w
 
 
+GUARD_SENTINEL = -7.25e77      # what the read-outs below fill their guard elements with
+
+
+def _guarded(ctx, count, guard):
+    buf = ctx.empty(count + guard)
+    buf.fill_(GUARD_SENTINEL)
+    return buf
+
+
+def lik_elbo_readout(kind, p0, p1, mean, var, Y, w=1.0, weights=None, transposed=False, adjoints=True, ldt=None, guard=0):
+    """dsdgp_lik_elbo_readout (verification aid): the training step's element-wise likelihood launch on (S, N, D) mean / var and (N, D)
+    targets.  -> dict: part (blocks, 2); row-major form dmean, dvar (S, N, D); transposed form MBt, VBt (D, ldt), ldt = S N rounded up
+    to 16 unless given.  guard > 0: every output buffer gets that many sentinel-filled elements behind it, returned as part_guard,
+    dmean_guard, ... — untouched memory still reads GUARD_SENTINEL."""
+    from . import _lib
+    from .engine import Context, ptr
+    ctx = Context.get()
+    mean = np.asarray(mean, dtype=np.float64)
+    S, N, D = mean.shape
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.shape != (N, D) or np.shape(var) != mean.shape:
+        raise ValueError("mean, var must be (S, N, D) and Y (N, D)")
+    m, v, y = ctx.to_device(mean), ctx.to_device(var), ctx.to_device(Y)
+    sw = None
+    if weights is not None:
+        if np.shape(weights) != (S,):
+            raise ValueError("sample weights must have shape (S,)")
+        sw = ctx.to_device(np.asarray(weights, dtype=np.float64))
+    R = S * N
+    if ldt is None:
+        ldt = -(-R // 16) * 16
+    blocks = -(-(ldt * D if transposed else R * D) // 256)
+    part = _guarded(ctx, 2 * blocks, guard)
+    names = () if not adjoints and not transposed else (("MBt", "VBt") if transposed else ("dmean", "dvar"))
+    bufs = [_guarded(ctx, ldt * D if transposed else R * D, guard) for _ in names]
+    a, b = (bufs + [None, None])[:2]
+    _lib.check(ctx.lib.dsdgp_lik_elbo_readout(ctx.handle, int(kind), float(p0), float(p1), ptr(m), ptr(v), ptr(y), N, S, D, float(w),
+                                              ptr(sw), ptr(part), *((ptr(None), ptr(None), ptr(a), ptr(b)) if transposed else
+                                                                    (ptr(a), ptr(b), ptr(None), ptr(None))), ldt))
+    ctx.sync()
+    out = {}
+    for name, buf, shape in [("part", part, (blocks, 2))] + [(nm, bf, (D, ldt) if transposed else (S, N, D)) for nm, bf in zip(names, bufs)]:
+        h = buf.cpu().numpy()
+        out[name] = h[:h.size - guard].reshape(shape)
+        if guard:
+            out[name + "_guard"] = h[h.size - guard:]
+    return out
+
+
+def multiclass_readout(mean, var, Y, w=1.0, weights=None, guard=0):
+    """dsdgp_multiclass_readout (verification aid): the training step's MultiClass launch (and the quadrature-weight launch behind it) on
+    (S, N, K) mean / var and (N, 1) labels -> dict: ve (S, N), dmean, dvar (S, N, K) (+ *_guard as lik_elbo_readout).  The labels are
+    checked here, before anything is uploaded: the kernel indexes its per-class accumulators with them."""
+    from . import _lib
+    from .engine import Context, ptr
+    mean = np.asarray(mean, dtype=np.float64)
+    S, N, K = mean.shape
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.shape != (N, 1) or np.shape(var) != mean.shape:
+        raise ValueError(f"mean, var must be (S, N, K) and the labels (N, 1), got {Y.shape}")
+    if not 2 <= K <= 32:
+        raise ValueError(f"MultiClass: K = {K} outside [2, 32]")
+    if not np.all(np.isfinite(Y)) or np.any(Y != np.floor(Y)) or np.any(Y < 0) or np.any(Y >= K):
+        raise ValueError(f"MultiClass targets must be integer labels in [0, {K})")
+    ctx = Context.get()
+    m, v, y = ctx.to_device(mean), ctx.to_device(var), ctx.to_device(Y)
+    sw = None
+    if weights is not None:
+        if np.shape(weights) != (S,):
+            raise ValueError("sample weights must have shape (S,)")
+        sw = ctx.to_device(np.asarray(weights, dtype=np.float64))
+    R = S * N
+    bufs = {"ve": _guarded(ctx, R, guard), "dmean": _guarded(ctx, R * K, guard), "dvar": _guarded(ctx, R * K, guard)}
+    _lib.check(ctx.lib.dsdgp_multiclass_readout(ctx.handle, ptr(m), ptr(v), ptr(y), N, S, K, float(w), ptr(sw), ptr(bufs["ve"]),
+                                                ptr(bufs["dmean"]), ptr(bufs["dvar"])))
+    ctx.sync()
+    out = {}
+    for name, buf in bufs.items():
+        h = buf.cpu().numpy()
+        out[name] = h[:h.size - guard].reshape((S, N) if name == "ve" else (S, N, K))
+        if guard:
+            out[name + "_guard"] = h[h.size - guard:]
+    return out
+
+
 class BroadcastingLikelihood:
     """Wrapper giving every likelihood method (S,N,D) semantics with Y of shape (N,D) (utils.py:54-121): the Gaussian
     broadcasts Y[None]; every other likelihood is evaluated on the flattened (S*N, D) arrays with Y tiled S times

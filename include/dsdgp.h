@@ -345,6 +345,26 @@ int dsdgp_lik_var_exp(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const 
 int dsdgp_lik_predict(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const double* mean, const double* var, int64_t count,
                       double* out_mean, double* out_var);
 
+/* Read-out of the likelihood launch of a training step (verification aid: nothing on the evaluation path calls it).  Launches the
+ * kernel dsdgp_model_elbo ends its forward pass with — the same instance, the same grid — on caller-supplied DEVICE arrays: mean, var
+ * (S x n x DY), Y (n x DY).  kind = any element-wise DSDGP_LIK_* (Gaussian and Bernoulli included); p0, p1 as for dsdgp_eval_mixture;
+ * w = data_scale / S; sample_w (S doubles or NULL) = the quadrature weights of DGP_Quad.  With ve = the variational expectation of one
+ * element and f = sample_w[s] S (1 without weights) it writes
+ *   dmean, dvar (S n DY each, row-major; both or neither):  -w f d ve / d mean, -w f d ve / d var — the form a one-layer model reads;
+ *   MBt, VBt (DY x ldt each, ldt >= S n; both or neither, and not together with dmean): the same numbers transposed, MBt[d][row], rows
+ *     S n .. ldt - 1 written as +0.0 — the form the last layer's backward chain of a deeper model reads (ldt = S n rounded up to 16);
+ *   part (2 x blocks doubles; blocks = ceil(S n DY / 256), with MBt ceil(ldt DY / 256)): part[2 b] = sum of f ve over the 256 elements
+ *     of block b, part[2 b + 1] = sum of f d ve / d p0 (0 for the kinds without a parameter).  ELBO data term = w sum_b part[2 b].
+ * Asynchronous on the ctx stream. */
+int dsdgp_lik_elbo_readout(dsdgp_ctx* ctx, int32_t kind, double p0, double p1, const double* mean, const double* var, const double* Y,
+                           int64_t n, int32_t S, int32_t DY, double w, const double* sample_w, double* part, double* dmean,
+                           double* dvar, double* MBt, double* VBt, int64_t ldt);
+/* The same for MultiClass(K): ve[row] (S n) = f var_exp of row s n + i with label Y[i] (n x 1 doubles, integers in [0, K): the kernel
+ * indexes with them and does not check), dmean / dvar (S n x K) = -w f d var_exp / d mean, / d var; 2 <= K <= 32.  The factor f is
+ * applied by the launch that follows the likelihood kernel in a DGP_Quad step, after rounding. */
+int dsdgp_multiclass_readout(dsdgp_ctx* ctx, const double* mean, const double* var, const double* Y, int64_t n, int32_t S, int32_t K,
+                             double w, const double* sample_w, double* ve, double* dmean, double* dvar);
+
 /* Held-out evaluation, the reduction of demos/run_regression.py:108-123 over the S components of DGP_Base.predict_y / predict_density
  * (dgp.py:116-126), on caller-supplied mean / var ((S*n) x DY, row s*n + i, as dsdgp_model_propagate writes them) and Y (n x DY;
  * MultiClass: n x 1 labels, DY = K).  With (E_s, V_s) = predict_mean_and_var of component s, per (i, d):
