@@ -148,6 +148,16 @@ _PROTOS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     "dsdgp_pca": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64,
                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # layers.py:415-417, 494-495: expectation(DiagonalGaussian, (RBF, InducingPoints)[, (RBF, InducingPoints)])
+    "dsdgp_rbf_expectations": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    # layers.py:426-427 (tf.transpose(tmp), AAT / sigma2, AAT + eye), :443-448 (the bound's terms), :521-524 (the predictive variance)
+    "dsdgp_scale_copy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p,
+                                   C.c_int64]),
+    "dsdgp_collapsed_bound": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "dsdgp_collapsed_var": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                      C.c_double, C.c_void_p]),
     "dsdgp_model_set_grad_first_layer": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),

@@ -1,6 +1,7 @@
 """Host mirror of the reference's layer classes (layers.py:36-246): `Layer`, `SVGP_Layer` with the same constructor,
 attributes (`q_mu`, `q_sqrt`, `feature.Z`, `kern`, `mean_function`, `num_outputs`, `white`) and methods
-(`conditional_ND`, `conditional_SND`, `sample_from_conditional`, `KL`).  All arithmetic runs in libdsdgp (HIP)."""
+(`conditional_ND`, `conditional_SND`, `sample_from_conditional`, `KL`), and of the collapsed layers `Collapsed_Layer`, `SGPR_Layer`
+(layers.py:296-307, 345-367, 371-525).  All arithmetic runs in libdsdgp (HIP)."""
 import numpy as np
 
 from . import settings
@@ -121,3 +122,175 @@ class SVGP_Layer(Layer):
     # layers.py:221-246
     def KL(self):
         return self._engine().layer_kl(self._index())
+
+
+def _rbf_spec(kern, what):
+    """(KernelSpec, its lengthscale array — keep it alive) of a plain RBF kernel; NotImplementedError, saying why, for any other"""
+    from . import _lib
+    stat, white = split_kernel(kern)
+    if stat.kind != "rbf" or white is not None:
+        raise NotImplementedError(f"{what}: the expectations of the kernel under a Gaussian input have a closed form here for a "
+                                  f"plain RBF kernel only, not for {type(stat).__name__}" + (" + White" if white is not None else ""))
+    ls = np.ascontiguousarray(np.asarray(stat.lengthscales.value, dtype=np.float64).reshape(-1))
+    spec = _lib.KernelSpec(kind=_lib.KERN_RBF, input_dim=int(stat.input_dim), ard=int(stat.ARD), has_white=0,
+                           variance=float(stat.variance.value), white_variance=0.0, lengthscales=ls.ctypes.data_as(_lib.c_double_p))
+    return spec, ls
+
+
+def kernel_expectations(kern, Z, X_mean, X_var=None, on_device=False):
+    """The expectations of an RBF kernel under the diagonal Gaussians N(X_mean[n], diag(X_var[n])) — GPflow 1.1.1's
+    expectation(DiagonalGaussian, kern), expectation(DiagonalGaussian, (kern, Z)) and the sum over rows of
+    expectation(DiagonalGaussian, (kern, Z), (kern, Z)) as layers.py:415-417 uses them — on the device (dsdgp_rbf_expectations):
+    (psi0 scalar, psi1 (N, M), psi2 (M, M)).  Z (M, D), X_mean, X_var (N, D): numpy arrays or device tensors; X_var=None is zero
+    variance.  on_device: return device tensors (psi0 of shape (1,)) without waiting for them.  The same arguments give the same bits."""
+    import ctypes as C
+    from . import _lib
+    from .engine import Context, ptr
+    spec, ls = _rbf_spec(kern, "kernel_expectations")
+    ctx = Context.get()
+    dev = lambda a: a.contiguous() if hasattr(a, "data_ptr") else ctx.to_device(np.asarray(a, dtype=np.float64))
+    Zd, mu = dev(Z), dev(X_mean)
+    s = None if X_var is None else dev(X_var)
+    if mu.dim() != 2 or Zd.dim() != 2 or mu.shape[1] != spec.input_dim or Zd.shape[1] != spec.input_dim or \
+            (s is not None and tuple(s.shape) != tuple(mu.shape)):
+        raise ValueError("kernel_expectations: Z must be (M, D), X_mean and X_var (N, D), D the kernel's input_dim")
+    N, M = mu.shape[0], Zd.shape[0]
+    psi0, psi1, psi2 = ctx.empty(1), ctx.empty(N, M), ctx.empty(M, M)
+    _lib.check(ctx.lib.dsdgp_rbf_expectations(ctx.handle, C.byref(spec), ptr(Zd), M, ptr(mu), ptr(s), N, ptr(psi0), ptr(psi1), M,
+                                              ptr(psi2), M))
+    if on_device:
+        return psi0, psi1, psi2
+    ctx.sync()
+    return float(psi0.cpu().numpy()[0]), psi1.cpu().numpy(), psi2.cpu().numpy()
+
+
+class Collapsed_Layer(Layer):
+    """Extra functions for a collapsed layer (layers.py:296-307): a last layer whose Gaussian posterior is at its exact optimum for
+    the data it has been given, so it carries no variational parameters and no KL term of its own."""
+    white = False
+
+    def set_data(self, X_mean, X_var, Y, lik_variance):
+        self._X_mean = X_mean
+        self._X_var = X_var
+        self._Y = Y
+        self._lik_variance = lik_variance
+
+    def build_likelihood(self):
+        raise NotImplementedError
+
+    def _engine(self):
+        """where sample_from_conditional draws when it is given no z: the owning DGP_Collapsed (its `randn`, under its seeds)"""
+        ref = getattr(self, "_model", None)          # a weak reference: the model is not one of the layer's parameters
+        model = ref() if ref is not None else None
+        if model is None:
+            raise RuntimeError("a collapsed layer outside a DGP_Collapsed owns no random numbers: pass z to sample_from_conditional")
+        return model
+
+
+class SGPR_Layer(Collapsed_Layer):
+    """A sparse variational GP layer with a Gaussian likelihood where the GP is integrated out (layers.py:345-367): the bound of
+    gplvm_build_likelihood and the prediction of gplvm_build_predict, psi branch (layers.py:405-450, 483-525), with the input noise
+    of the last hop integrated analytically through the expectations of the kernel (dsdgp_rbf_expectations).  set_data factorises
+    once — L = chol(Kuu), LB = chol(L^-1 psi2 L^-T / s2 + I), c = LB^-1 L^-1 psi1^T Y / s2 stay on the device — and
+    build_likelihood / conditional_ND read the factors.  X_var=None is zero variance.  Only a plain RBF kernel has the closed-form
+    expectations, and only the Zero mean function is consistent: the reference's psi branch ignores the mean function in the bound
+    and adds it in the prediction."""
+
+    def __init__(self, kern, Z, num_outputs, mean_function, **kwargs):
+        Collapsed_Layer.__init__(self, **kwargs)
+        _rbf_spec(kern, "SGPR_Layer")
+        if getattr(mean_function, "kind", None) != "zero":
+            raise NotImplementedError(f"SGPR_Layer: mean function {type(mean_function).__name__}: the reference's bound ignores the "
+                                      "mean function and its prediction adds it, so only Zero is consistent")
+        self.feature = Z if isinstance(Z, InducingPoints) else InducingPoints(np.array(Z, dtype=np.float64))
+        self.num_inducing = self.feature.Z.shape[0]
+        self.kern = kern
+        self.mean_function = mean_function
+        self.num_outputs = int(num_outputs)
+        object.__setattr__(self, "_factors", None)
+
+    def set_data(self, X_mean, X_var, Y, lik_variance):
+        """X_mean, X_var (N, D_in) — numpy or device tensors, X_var may be None — Y (N, D_Y) and the noise variance.  Runs the
+        expectations and both factorisations; CholeskyError if Kuu or AAT + I is not positive definite (the layer then holds no data)."""
+        import ctypes as C
+        object.__setattr__(self, "_factors", None)
+        from . import _lib
+        from .engine import Context, ptr
+        ctx = Context.get()
+        lib, h = ctx.lib, ctx.handle
+        dev = lambda a: a.contiguous() if hasattr(a, "data_ptr") else ctx.to_device(np.asarray(a, dtype=np.float64))
+        mu, Yd = dev(X_mean), dev(Y)
+        s = None if X_var is None else dev(X_var)
+        N, D = mu.shape
+        M, DY = self.num_inducing, Yd.shape[1]
+        if Yd.shape[0] != N or (s is not None and tuple(s.shape) != (N, D)) or D != self.feature.Z.shape[1]:
+            raise ValueError("set_data: X_mean and X_var must be (N, D_in) and Y (N, D_Y)")
+        s2 = float(lik_variance)
+        spec, ls = _rbf_spec(self.kern, "SGPR_Layer")
+        Z = ctx.to_device(self.feature.Z.value)
+        psi0, psi1, psi2 = kernel_expectations(self.kern, Z, mu, s, on_device=True)
+        L, G, B, T = ctx.empty(M, M), ctx.empty(M, M), ctx.empty(M, M), psi2
+        info = C.c_int(0)
+        _lib.check(lib.dsdgp_gram(h, C.byref(spec), ptr(Z), M, None, 0, float(settings.jitter), ptr(L), M))
+        _lib.check(lib.dsdgp_potrf(h, 1, M, ptr(L), M, M * M, C.byref(info)))             # L = chol(Kuu)
+        _lib.check(lib.dsdgp_trsm(h, 0, M, M, ptr(L), M, ptr(T), M))                      # tmp = L^-1 psi2
+        _lib.check(lib.dsdgp_scale_copy(h, 1, M, M, ptr(T), M, 1.0, 0.0, ptr(G), M))      # tmp^T
+        _lib.check(lib.dsdgp_trsm(h, 0, M, M, ptr(L), M, ptr(G), M))                      # G = L^-1 psi2 L^-T = s2 AAT
+        _lib.check(lib.dsdgp_scale_copy(h, 0, M, M, ptr(G), M, s2, 1.0, ptr(B), M))       # B = AAT + I
+        _lib.check(lib.dsdgp_potrf(h, 1, M, ptr(B), M, M * M, C.byref(info)))             # LB = chol(B)
+        c = ctx.empty(M, DY)
+        _lib.check(lib.dsdgp_gemm(h, 1, 0, M, DY, N, 1.0 / s2, ptr(psi1), M, ptr(Yd), DY, 0.0, ptr(c), DY))    # psi1^T Y / s2
+        _lib.check(lib.dsdgp_trsm(h, 0, M, DY, ptr(L), M, ptr(c), DY))
+        _lib.check(lib.dsdgp_trsm(h, 0, M, DY, ptr(B), M, ptr(c), DY))                    # c = LB^-1 L^-1 psi1^T Y / s2
+        Collapsed_Layer.set_data(self, mu, s, Yd, s2)
+        object.__setattr__(self, "_factors", dict(ctx=ctx, spec=spec, ls=ls, Z=Z, L=L, LB=B, G=G, c=c, psi0=psi0, N=N, DY=DY, s2=s2,
+                                                  kdiag=float(spec.variance)))
+
+    def _need_factors(self):
+        if self._factors is None:
+            raise RuntimeError("SGPR_Layer: call set_data(X_mean, X_var, Y, lik_variance) first")
+        return self._factors
+
+    def bound_terms(self):
+        """(bound, its six terms) of layers.py:443-448 as the device assembled them."""
+        from . import _lib
+        from .engine import ptr
+        f = self._need_factors()
+        ctx, M = f["ctx"], self.num_inducing
+        out = ctx.empty(7)
+        _lib.check(ctx.lib.dsdgp_collapsed_bound(ctx.handle, M, f["N"], f["DY"], ptr(f["LB"]), M, ptr(f["G"]), M, ptr(f["c"]),
+                                                 ptr(self._Y), ptr(f["psi0"]), f["s2"], ptr(out)))
+        ctx.sync()
+        o = out.cpu().numpy()
+        return float(o[0]), o[1:].copy()
+
+    def build_likelihood(self):
+        return self.bound_terms()[0]
+
+    # layers.py:483-525
+    def conditional_ND(self, Xnew, full_cov=False):
+        import ctypes as C
+        from . import _lib
+        from .engine import ptr
+        f = self._need_factors()
+        ctx, M, DY = f["ctx"], self.num_inducing, f["DY"]
+        lib, h = ctx.lib, ctx.handle
+        Xs = Xnew.contiguous() if hasattr(Xnew, "data_ptr") else ctx.to_device(np.asarray(Xnew, dtype=np.float64))
+        ns = Xs.shape[0]
+        tmp1, tmp2, mean = ctx.empty(M, ns), ctx.empty(M, ns), ctx.empty(ns, DY)
+        _lib.check(lib.dsdgp_gram(h, C.byref(f["spec"]), ptr(f["Z"]), M, ptr(Xs), ns, 0.0, ptr(tmp1), ns))       # K(Z, X*)
+        _lib.check(lib.dsdgp_trsm(h, 0, M, ns, ptr(f["L"]), M, ptr(tmp1), ns))
+        _lib.check(lib.dsdgp_scale_copy(h, 0, M, ns, ptr(tmp1), ns, 1.0, 0.0, ptr(tmp2), ns))
+        _lib.check(lib.dsdgp_trsm(h, 0, M, ns, ptr(f["LB"]), M, ptr(tmp2), ns))
+        _lib.check(lib.dsdgp_gemm(h, 1, 0, ns, DY, M, 1.0, ptr(tmp2), ns, ptr(f["c"]), DY, 0.0, ptr(mean), DY))
+        if full_cov:
+            K = ctx.empty(ns, ns)
+            _lib.check(lib.dsdgp_gram(h, C.byref(f["spec"]), ptr(Xs), ns, None, 0, 0.0, ptr(K), ns))
+            _lib.check(lib.dsdgp_gemm(h, 1, 0, ns, ns, M, 1.0, ptr(tmp2), ns, ptr(tmp2), ns, 1.0, ptr(K), ns))
+            _lib.check(lib.dsdgp_gemm(h, 1, 0, ns, ns, M, -1.0, ptr(tmp1), ns, ptr(tmp1), ns, 1.0, ptr(K), ns))
+            ctx.sync()
+            return mean.cpu().numpy(), np.tile(K.cpu().numpy()[:, :, None], [1, 1, DY])       # layers.py:518-519: a copy per output
+        var = ctx.empty(ns, DY)
+        _lib.check(lib.dsdgp_collapsed_var(h, M, ns, DY, ptr(tmp1), ns, ptr(tmp2), ns, f["kdiag"], ptr(var)))
+        ctx.sync()
+        return mean.cpu().numpy(), var.cpu().numpy()

@@ -1,0 +1,202 @@
+"""Host mirror of the reference's model_zoo.py:25-57: `DGP_Collapsed`, a DGP whose last layer is a collapsed one (layers.SGPR_Layer).
+Its bound is the one of the reference's `_build_likelihood`: the last layer at its exact optimum over the WHOLE training set, the input
+noise of the last hop integrated analytically through the kernel expectations, minus the KL terms of the inner layers.  The inner
+layers run as one device Engine over `layers[:-1]` (`inner_engine()`; S = 1 on the full training set, explicit `zs` accepted); the
+last layer is the host layer loop that `DGP_Base.propagate(full_cov=True)` uses.  No reverse pass is built through the expectations:
+`train_step` and the optimisers raise NotImplementedError — train a `DGP` (Adam plus natural-gradient steps), then read the collapsed
+bound and the predictions of the exactly optimal last layer through `DGP_Collapsed.from_dgp(model)`.  There is no engine over ALL
+layers (the collapsed layer has no variational parameters to put into one), so `engine()` and the device-side scoring methods built
+on it (`evaluate`, `predict_quantiles`, `calibration`, `classification_report`) raise NotImplementedError as well: score a collapsed
+model from `predict_y` / `predict_density`."""
+import ctypes as C
+import weakref
+
+import numpy as np
+
+from . import _lib
+from .dgp import DGP_Base
+from .gpflow_compat import Gaussian
+from .layers import Collapsed_Layer, SGPR_Layer, concat_input_prop
+
+
+class DGP_Collapsed(DGP_Base):
+    supports_gradients = False
+
+    def __init__(self, X, Y, likelihood, layers, **kwargs):
+        if kwargs.get("minibatch_size") is not None:
+            raise ValueError("DGP_Collapsed: minibatch_size must be None — the last layer is optimal for the whole training set "
+                             "(model_zoo.py:54)")
+        if not isinstance(likelihood, Gaussian):
+            raise NotImplementedError(f"DGP_Collapsed: the last layer is collapsed against a Gaussian likelihood, not "
+                                      f"{type(likelihood).__name__}")
+        layers = list(layers)
+        if not layers or not isinstance(layers[-1], Collapsed_Layer):
+            raise ValueError("DGP_Collapsed: the last layer must be a Collapsed_Layer (SGPR_Layer)")
+        if any(isinstance(layer, Collapsed_Layer) for layer in layers[:-1]):
+            raise ValueError("DGP_Collapsed: only the last layer is collapsed")
+        DGP_Base.__init__(self, X, Y, likelihood, layers, **kwargs)
+        self.white = bool(layers[0].white) if len(layers) > 1 else False
+        object.__setattr__(layers[-1], "_model", weakref.ref(self))          # the last layer draws its samples through this model's seeds
+
+    @classmethod
+    def from_dgp(cls, model):
+        """The collapsed view of a trained DGP: the inner layers, the last layer's kernel and inducing inputs and the likelihood are
+        SHARED with `model` (not copied), its last SVGP_Layer is replaced by an SGPR_Layer."""
+        last = model.layers[-1]
+        top = SGPR_Layer(last.kern, last.feature, last.num_outputs, last.mean_function)
+        return cls(model.X_data, model.Y_data, model.likelihood.likelihood, list(model.layers[:-1]) + [top])
+
+    # ------------------------------------------------------------------ what has no meaning without an engine over all layers
+    def _no_full_engine(self, what):
+        raise NotImplementedError(f"DGP_Collapsed.{what}: there is no device engine over all layers (the collapsed last layer is not "
+                                  "part of one); use predict_f / predict_y / predict_density")
+
+    def engine(self):
+        self._no_full_engine("engine")
+
+    def evaluate(self, *args, **kwargs):
+        self._no_full_engine("evaluate")
+
+    def predict_quantiles(self, *args, **kwargs):
+        self._no_full_engine("predict_quantiles")
+
+    def calibration(self, *args, **kwargs):
+        self._no_full_engine("calibration")
+
+    def classification_report(self, *args, **kwargs):
+        self._no_full_engine("classification_report")
+
+    def next_minibatch(self):
+        self._no_full_engine("next_minibatch")
+
+    # ------------------------------------------------------------------ engine over the inner layers
+    def inner_engine(self):
+        if len(self.layers) == 1:
+            raise RuntimeError("a one-layer DGP_Collapsed has no inner layers and no engine")
+        if self._eng is None:
+            from .engine import Engine
+            inner = self.layers[:-1]
+            for layer in inner:                       # a shared layer's own engine may hold newer values than the host copy
+                for p in layer.parameters():
+                    p.value
+            eng = Engine(inner, self.likelihood.likelihood, self.white, n_max=self.X_data.shape[0], s_max=1)
+            for i, layer in enumerate(inner):
+                if getattr(layer, "_model_engine", None) is None:
+                    object.__setattr__(layer, "_model_engine", (eng, i))
+            object.__setattr__(self, "_eng", eng)
+        return self._eng
+
+    def _context(self):
+        from .engine import Context
+        return Context.get()
+
+    def _device_data(self):
+        if self._dev_data is None:
+            ctx = self._context()
+            object.__setattr__(self, "_dev_data", (ctx.to_device(self.X_data), ctx.to_device(self.Y_data)))
+        return self._dev_data
+
+    def randn(self, shape, seed=None):
+        """N(0, 1) draws for the last layer's samples (Layer.sample_from_conditional without z) under this model's seed sequence:
+        stream len(layers) - 1 of `_draw_seed()`, as the engine numbers the streams of the layers it draws for."""
+        ctx = self._context()
+        n = int(np.prod(shape))
+        out = ctx.empty(n)
+        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(self._draw_seed() if seed is None else seed),
+                                       C.c_uint64(len(self.layers) - 1), n, C.c_void_p(out.data_ptr())))
+        ctx.sync()
+        return out.cpu().numpy().reshape(shape)
+
+    def _refresh(self):
+        """Parameters that another engine (the DGP the inner layers are shared with) has trained since the last evaluation: reading
+        `.value` pulls them to the host; if the inner engine's parameter vector then differs from the one it last saw, it uploads.
+        (Whether the other engine still counts itself as newer than the host says nothing: any earlier read has settled that.)"""
+        if len(self.layers) == 1:
+            return
+        eng = self.inner_engine()
+        for p, *_ in eng.entries:
+            p.value
+        theta = eng._pack_host()
+        seen = getattr(self, "_theta_seen", None)
+        if seen is None or not np.array_equal(theta, seen):
+            eng.mark_host_dirty()
+            object.__setattr__(self, "_theta_seen", theta)
+
+    # ------------------------------------------------------------------ model_zoo.py:26-44
+    def inner_layers_propagate(self, X, full_cov=False, S=1, zs=None):
+        X = np.asarray(X.cpu().numpy() if hasattr(X, "data_ptr") else X, dtype=np.float64)
+        sX = np.tile(X[None], [int(S), 1, 1])
+        if len(self.layers) == 1:                                   # model_zoo.py:30-31
+            return [sX], [sX], [np.zeros_like(sX)]
+        inner = self.layers[:-1]
+        zs = list(zs)[:len(inner)] if zs is not None else None
+        self._refresh()
+        if full_cov:
+            F, Fs, Fmeans, Fvars = sX, [], [], []
+            for layer, z in zip(inner, zs or [None] * len(inner)):
+                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=True)
+                Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
+            return Fs, Fmeans, Fvars
+        eng = self.inner_engine()
+        Fs, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._draw_seed())
+        eng.ctx.sync()
+        Fs, Fmeans, Fvars = self._np(Fs), self._np(Fmeans), self._np(Fvars)
+        Fin = sX
+        for l, layer in enumerate(inner):                           # layers.py:105-117, as DGP_Base.propagate
+            if layer.input_prop_dim:
+                Fs[l], Fmeans[l], Fvars[l] = concat_input_prop(Fin, layer.input_prop_dim, Fs[l], Fmeans[l], Fvars[l])
+            Fin = Fs[l]
+        return Fs, Fmeans, Fvars
+
+    def _set_data(self, zs=None):
+        """model_zoo.py:48-49, 54-55: the marginal mean and variance of the last layer's inputs at the training set (S = 1) become
+        the collapsed layer's data.  One layer: the inputs themselves, zero variance.  The statistics go from the engine to the
+        layer as device tensors (unless the last inner layer propagates inputs: that concatenation is a host copy)."""
+        lik_var = float(self.likelihood.likelihood.variance.value)
+        Xd, Yd = self._device_data()
+        if len(self.layers) == 1:
+            self.layers[-1].set_data(Xd, None, Yd, lik_var)
+            return
+        if self.layers[-2].input_prop_dim:
+            _, ms, vs = self.inner_layers_propagate(self.X_data, full_cov=False, S=1, zs=zs)
+            self.layers[-1].set_data(ms[-1][0], vs[-1][0], Yd, lik_var)
+            return
+        self._refresh()
+        eng = self.inner_engine()
+        zs = list(zs)[:len(self.layers) - 1] if zs is not None else None
+        _, ms, vs = eng.propagate(Xd, 1, zs=zs, seed=self._draw_seed(), want=("mean", "var"))
+        self.layers[-1].set_data(ms[-1][0], vs[-1][0], Yd, lik_var)
+
+    # ------------------------------------------------------------------ model_zoo.py:46-50
+    def propagate(self, X, full_cov=False, S=1, zs=None):
+        """zs: explicit draws per layer for the propagation of X (they are shaped for X, not for the training set); the statistics
+        of the training set (S = 1) use fresh draws — with one inner layer they do not depend on any."""
+        self._set_data()
+        if len(self.layers) == 1:
+            Fs, Fmeans, Fvars = [], [], []
+            F = np.tile(np.asarray(X, dtype=np.float64)[None], [int(S), 1, 1])
+        else:
+            Fs, Fmeans, Fvars = self.inner_layers_propagate(X, full_cov=full_cov, S=S, zs=zs)
+            F = Fs[-1]
+        z = zs[len(self.layers) - 1] if zs is not None and len(zs) >= len(self.layers) else None
+        F, Fmean, Fvar = self.layers[-1].sample_from_conditional(F, z=z, full_cov=full_cov)
+        return Fs + [F], Fmeans + [Fmean], Fvars + [Fvar]
+
+    def _build_predict(self, X, full_cov=False, S=1, zs=None):
+        _, Fmeans, Fvars = self.propagate(X, full_cov=full_cov, S=S, zs=zs)
+        return Fmeans[-1], Fvars[-1]
+
+    # ------------------------------------------------------------------ model_zoo.py:52-57
+    def _build_likelihood(self, X=None, Y=None, zs=None, with_grad=False, **kwargs):
+        if X is not None or Y is not None:
+            raise ValueError("DGP_Collapsed: the bound is that of the whole training set (model_zoo.py:54); no minibatch is taken")
+        if with_grad:
+            raise NotImplementedError("DGP_Collapsed: no reverse pass is built through the kernel expectations")
+        self._set_data(zs=zs)
+        bound = self.layers[-1].build_likelihood()
+        KL = sum(layer.KL() for layer in self.layers[:-1])
+        return bound - KL
+
+    def train_step(self, *args, **kwargs):
+        raise NotImplementedError("DGP_Collapsed: no reverse pass is built through the kernel expectations — train a DGP and read "
+                                  "the collapsed bound through DGP_Collapsed.from_dgp(model)")

@@ -7,6 +7,8 @@ class AdamOptimizer:
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, epsilon
 
     def minimize(self, model, maxiter=1000):
+        if not getattr(model, "supports_gradients", True):
+            raise NotImplementedError(f"{type(model).__name__} builds no reverse pass: there is no gradient to step along")
         n = int(maxiter)
         for it in range(n):
             # steps are asynchronous; the last one synchronises and surfaces a failed Kuu factorisation (CholeskyError)
@@ -32,6 +34,8 @@ class NatGradOptimizer:
         return idx
 
     def minimize(self, model, var_list, maxiter=1, X=None, Y=None, zs=None):
+        if not getattr(model, "supports_gradients", True):
+            raise NotImplementedError(f"{type(model).__name__} builds no reverse pass: there is no gradient to step along")
         layers = self._layer_indices(model, var_list)
         eng = model.engine()
         for _ in range(int(maxiter)):

@@ -60,7 +60,7 @@ int dsdgp_ctx_destroy(dsdgp_ctx* ctx);
 int dsdgp_sync(dsdgp_ctx* ctx);
 /* HIP-event timing of the most recent launch of a named kernel class on the ctx stream (bench.py roofline):
  * enable, run, then read the accumulated milliseconds and launch count. name in
- * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig"}. */
+ * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig","psi","psi2"}. */
 int dsdgp_prof_enable(dsdgp_ctx* ctx, int on);
 int dsdgp_prof_read(dsdgp_ctx* ctx, const char* name, double* total_ms, int64_t* launches, int reset);
 /* Kernel launches this library has enqueued in this process so far (all contexts; memsets / copies not counted): the difference
@@ -517,6 +517,45 @@ int dsdgp_greedy_inducing(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double
  * scratch (they are 4.5 MB at D = 1024; the number of splits is chosen so that all of them stay below that cap). */
 int dsdgp_pca(dsdgp_ctx* ctx, const double* X, int64_t n, int32_t D, int32_t k, int32_t center, int32_t max_sweeps, double* W, int64_t ldw,
               double* evals, double* mean, double* gram, int32_t* info);
+
+/* dsdgp_rbf_expectations: the expectations of an RBF kernel under a diagonal Gaussian input (the psi statistics) that the reference's
+ * collapsed layers take from GPflow 1.1.1's expectation(DiagonalGaussian, (RBF, InducingPoints)[, (RBF, InducingPoints)])
+ * (layers.py:415-417, 494-495).  mu, s (device, n x D): means and variances of the rows, s == NULL: zero variance; Z (device, M x D);
+ * kern as for dsdgp_gram, D = kern->input_dim, variance v, lengthscales l_d (scalar or ARD).
+ *   psi0 (device, 1 double, or NULL)      = n v
+ *   psi1 (device, n x ld1, or NULL)[r, i] = v prod_d (l_d^2 / (l_d^2 + s_rd))^1/2 exp(-1/2 sum_d (mu_rd - z_id)^2 / (l_d^2 + s_rd))
+ *   psi2 (device, M x ld2, or NULL)[i, j] = sum_r v^2 prod_d (l_d^2 / (l_d^2 + 2 s_rd))^1/2
+ *                                           exp(-sum_d [(z_id - z_jd)^2 / (4 l_d^2) + (mu_rd - (z_id + z_jd) / 2)^2 / (l_d^2 + 2 s_rd)])
+ * The columns M .. ld of psi1 and psi2 are not written.  Every exponent is formed from differences of the inputs, never from an
+ * expanded square; for s >= 0 every term of an exponent is <= 0, so a far pair underflows to +0.  s is not clamped: a row with
+ * l_d^2 + 2 s_rd < 0 gives NaN in the entries it feeds, as upstream's sqrt does.  psi2 is n M (M + 1) / 2 exponentials: only the 16 x 16
+ * tiles on or below the diagonal are formed (the mirror image is written with them: psi2 is exactly symmetric), the rows split over
+ * workgroups, the term sum_d t_rd (z_id - z_jd)^2 of the exponent on the fp64 MFMA pipe, and the partial tiles added in ascending split
+ * order — no floating-point atomics: the same arguments give the same bits on every call.  Asynchronous on the context's stream; the
+ * row tables (8 n (3 D + M + 6) bytes) live in the context's scratch.
+ * DSDGP_ERR_UNSUPPORTED for a kernel that is not RBF or has a White part (Matern52 has no closed form), or when the row tables would
+ * exceed 8 GB (pass the rows in batches and add the results).  DSDGP_ERR_BAD_ARG for M outside 1..2048, n < 1, n >= 2^31,
+ * kern->input_dim outside 1..1024, ld1 / ld2 < M or a NULL kern / Z / mu. */
+int dsdgp_rbf_expectations(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu, const double* s,
+                           int64_t n, double* psi0, double* psi1, int64_t ld1, double* psi2, int64_t ld2);
+
+/* The small steps of the reference's collapsed bound and its prediction (gplvm_build_likelihood / gplvm_build_predict, psi branch,
+ * layers.py:405-450, 483-525) that the primitives above lack; SGPR_Layer of the host mirror composes them with dsdgp_gram, dsdgp_potrf,
+ * dsdgp_trsm and dsdgp_gemm.  All asynchronous; every sum in a fixed order.
+ * dsdgp_scale_copy: B (m x n) = op(A) / div + diag_add I, op(A) = A (trans = 0) or A^T (trans = 1) — tf.transpose(tmp) of layers.py:426,
+ * AAT / sigma2 and AAT + eye of :426-427.  A and B must not overlap. */
+int dsdgp_scale_copy(dsdgp_ctx* ctx, int trans, int m, int n, const double* A, int64_t lda, double div, double diag_add, double* B,
+                     int64_t ldb);
+/* dsdgp_collapsed_bound: the terms of layers.py:443-448 from LB = chol(AAT + I) (M x ldb), G = L^-1 psi2 L^-T (M x ldg; AAT = G /
+ * noise_var), c (M x DY), Y (n x DY), psi0 (device scalar) and the likelihood's noise variance.  out (device, 7 doubles): out[0] = the
+ * bound, out[1..6] = -1/2 n DY log(2 pi noise_var), -DY sum log diag(LB), -1/2 sum Y^2 / noise_var, 1/2 sum c^2,
+ * -1/2 DY psi0 / noise_var, 1/2 DY tr(G) / noise_var;  out[0] adds them in this order. */
+int dsdgp_collapsed_bound(dsdgp_ctx* ctx, int32_t M, int64_t n, int32_t DY, const double* LB, int64_t ldb, const double* G, int64_t ldg,
+                          const double* c, const double* Y, const double* psi0, double noise_var, double* out);
+/* dsdgp_collapsed_var: var[r, d] = kdiag + sum_m tmp2[m, r]^2 - sum_m tmp1[m, r]^2 for every output d < DY (layers.py:521-524);
+ * tmp1 = L^-1 K(Z, X*), tmp2 = LB^-1 tmp1 (M x ld, ns columns used), var (ns x DY). */
+int dsdgp_collapsed_var(dsdgp_ctx* ctx, int32_t M, int64_t ns, int32_t DY, const double* tmp1, int64_t ld1, const double* tmp2,
+                        int64_t ld2, double kdiag, double* var);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
