@@ -118,31 +118,7 @@ struct LayerBwdArgs {
 // whether the backward chain of this shape can take the adjoint prologue (its LDS reduction scratch holds 2 x 16 x D_out partials)
 int sm_adj_fusable(int Mp, int64_t nblk, int D_in, int D_out);
 
-// out[split][i][j] = sum_{r in split} P[i][r] * scale[r] * Q[j][r]
-struct WgradJob {
-  const double* P;
-  const double* Q;
-  const double* scale;  // or NULL
-  double* out;          // [nsplit][rowsP][ldo]
-  int32_t ti, tj;       // tiles in i / j (tile = 16*NI x 16*NJ; the last j tile may be partial, see qrows16)
-  int32_t ldo;
-  int32_t task_start;
-  int32_t sym;          // P == Q (symmetric result): only tiles with tile_j <= tile_i are computed
-  int32_t qrows16;      // rows of Q / 16 (= columns of the result / 16)
-  int32_t ns_diag;      // sym: K splits of the (cheaper, 10/16) diagonal tiles; their tasks follow the off-diagonal ones
-  int32_t ng;           // 0: one result per task.  1..4: a GROUP of ng symmetric, scaled results that share P = Q (the P_d of a layer)
-                        // on 32 x 32 tiles, result o at out + o * ostride, scaled by scale + o * sstride (see k_wgrad_coop)
-  // In-launch split-K reduction (round 6): with `fin` set the LAST of a tile's splits to arrive (ticket counter `tick[tile]`, zero between
-  // launches) adds the tile's partials in split order and writes rows < fin_rows, columns < fin_cols of the result (leading dimension
-  // fin_ld) — and, for sym, the mirror tile / the uncomputed upper blocks of a diagonal tile — so that no reduction launch follows the
-  // products.  One split: the tile goes from registers to `fin`, `out` is not touched.  NULL: partials only (k_reduce_grouped adds them).
-  double* fin;
-  int32_t* tick;
-  int32_t fin_ld, fin_rows, fin_cols, pad2;
-  int64_t ostride, sstride;      // ng > 0: distance between the group's results / between their scale vectors (doubles)
-};
-
-// jobs_dev: device copy of `njobs` jobs with task_start filled (64 x 64 tiles, one workgroup per (job, split, tile) task; grouped
+// jobs_dev: device copy (WgradJob: plan_types.hpp) of `njobs` jobs with task_start filled (64 x 64 tiles, one workgroup per (job, split, tile) task; grouped
 // jobs: one workgroup per (split, 32 x 32 tile) task of the group's outputs)
 int wgrad_launch(dsdgp_ctx* ctx, const WgradJob* jobs_dev, int njobs, int total_tasks, int nsplit, int64_t ld, int64_t Rp,
                  hipStream_t stream = nullptr);
@@ -180,8 +156,6 @@ struct GemmLayerWs {
   int64_t pb_doubles; // capacity of Pb
 };
 #define GL_MAX_GROUPS 4
-// doubles of each GemmLayerWs array for a model whose gemm-path layers have at most these extents
-struct GemmLayerExtents { int64_t Mp, ld, D_out, D_in; };
 int layer_gemm_hyp_parts(int64_t ld, int Mp);
 int layer_gemm_lik_blocks(int64_t Rin, int D_out);
 int layer_fwd_gemm_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, int Mp, int kern_kind, int white, const GemmLayerWs& ws);

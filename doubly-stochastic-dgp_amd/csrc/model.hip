@@ -12,6 +12,7 @@ int gram_launch(dsdgp_ctx* ctx, int kind, const double* X, int64_t n, const doub
 
 #define SOFTPLUS_LOWER 1e-6  // [UPSTREAM] gpflow.transforms.positive
 
+#include "model_plan.hpp"       // split-K plan of the weight-gradient products (pure host code)
 #include "model_types.hpp"      // descriptors, policies
 #include "model_layout.hpp"     // workspace layout
 #include "model_kernels.hpp"    // device kernels (transforms, KL, likelihoods, reduction, assembly, tail)
@@ -358,11 +359,9 @@ extern "C" int dsdgp_model_set_bucket_callback(dsdgp_model* m, dsdgp_bucket_fn f
   if (fn) {
     // the buckets are contiguous SEGMENTS of theta: layer l owns [off_Z_l, off_Z_{l+1}), the likelihood variance follows the last
     // layer's segment.  A descriptor with another ordering would hand out segments that are incomplete or not yet produced.
-    const int L = m->desc.L;
-    const int64_t lik_lo = lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : m->desc.n_theta;
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < m->desc.L; ++l) {
       const dsdgp_layer_desc& d = m->L[l].d;
-      const int64_t lo = d.off_Z, hi = (l + 1 < L) ? m->L[l + 1].d.off_Z : lik_lo;
+      const int64_t lo = theta_segment_lo(m, l), hi = theta_segment_lo(m, l + 1);
       const int64_t offs[] = {d.off_q_mu, d.off_q_sqrt, d.off_kvar, d.off_kls, d.has_white ? d.off_wvar : lo,
                               d.off_mean_A >= 0 ? d.off_mean_A : lo, d.off_mean_b >= 0 ? d.off_mean_b : lo};
       bool ok = lo < hi;
@@ -399,9 +398,7 @@ extern "C" int dsdgp_model_track_theta(dsdgp_model* m, int enable) {
 }
 extern "C" int dsdgp_model_theta_changed(dsdgp_model* m) {
   DS_CHECK_ARG(m != nullptr);
-  m->prepared = false;
-  m->kuu_valid = false;
-  m->q_dirty = -2;
+  mark_theta_moved(m);
   return DSDGP_OK;
 }
 

@@ -24,7 +24,7 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
   m->gp_wz = b.take<GemmProblem>(D.L);
   m->gp_w1 = b.take<GemmProblem>(2 * D.L); m->gp_w2 = b.take<GemmProblem>(D.L); m->gp_w3 = b.take<GemmProblem>(D.L);
   m->rjobs_cap = 0;
-  for (int l = 0; l < D.L; ++l) m->rjobs_cap += D.layers[l].D_out + 5;
+  for (int l = 0; l < D.L; ++l) m->rjobs_cap += plan_red_slots(D.layers[l].D_out);
   m->rjobs = b.take<RedJob>(m->rjobs_cap);
   // layers with the same (large) M keep their Ku / Lu^-1 / Lu^-T contiguous so that one batched factorisation serves them all
   bool uniform = D.L > 1 && pad_M(D.layers[0].M) >= big_mp(true);
@@ -93,8 +93,7 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
     v.off_mean_A = (d.mean_kind == DSDGP_MEAN_LINEAR) ? d.off_mean_A : -1;
     v.off_mean_b = (d.mean_kind == DSDGP_MEAN_LINEAR) ? d.off_mean_b : -1;
     S.mean_grad = (v.off_mean_A >= 0 && d.trainable_mean_A) || (v.off_mean_b >= 0 && d.trainable_mean_b);
-    const int mrows = 64 * ceil_div(v.DinP16, 64);
-    v.meanAB = S.mean_grad ? b.take<double>((size_t)mrows * v.DP16) : nullptr;
+    v.meanAB = S.mean_grad ? b.take<double>((size_t)64 * ceil_div(v.DinP16, 64) * v.DP16) : nullptr;
     v.R2 = b.take<double>(MM);
     v.Zp1 = b.take<double>(Mp * v.DinP16); v.WZ = b.take<double>(Mp * v.DinP16);
     S.R_max = (int64_t)m->s_max * m->n_max;
@@ -110,15 +109,9 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
     S.prop = (l + 1 < D.L) ? d.input_prop_dim : 0;     // the last layer's concatenation is host glue (nothing consumes it)
     S.dF = b.take<double>(S.R_max * (d.D_out + S.prop));
     S.Xcat = S.prop ? b.take<double>(S.R_max * (d.D_out + S.prop)) : nullptr;
-    int NI, ti;
-    wgrad_shapes(v.Mp, NI, ti);
-    const int tj_big = ti;
-    S.nsplit_big_max = choose_nsplit((v.alg_g ? 0 : ti * tj_big) + d.D_out * (ti * (ti - 1) / 2) + (int)ceil(d.D_out * ti * (NI + 1) / (2.0 * NI)),
-                                     S.ld_max / 16, 512);
-    S.nsplit_thin_max = choose_nsplit(ti * (v.DP16 / 16 + v.DinP16 / 16), S.ld_max / 16, 256);
-    S.part_big = b.take<double>((size_t)S.nsplit_big_max * (1 + d.D_out) * Mw * Mw);
-    S.part_thin = b.take<double>((size_t)S.nsplit_big_max * Mw * (v.DP16 + v.DinP16));
-    S.part_mean = S.mean_grad ? b.take<double>((size_t)S.nsplit_big_max * mrows * v.DP16) : nullptr;
+    S.cap = plan_caps(v.alg_g, d.D_out, v.Mp, v.DP16, v.DinP16, S.mean_grad, S.ld_max);
+    S.part_big = b.take<double>(S.cap.part_big); S.part_thin = b.take<double>(S.cap.part_thin);
+    S.part_mean = S.mean_grad ? b.take<double>(S.cap.part_mean) : nullptr;
     S.gemm = m->force.gemm_mp > 0 && v.Mp >= m->force.gemm_mp;
     S.hyp_part = b.take<double>((size_t)(std::max<int64_t>(std::max<int64_t>(sm_hyp_parts(S.ld_max, v.Mp, d.D_in), layer_gemm_hyp_parts(S.ld_max, v.Mp)),
                                                            8 * 160) + 16) * (d.D_in + 2));
@@ -126,12 +119,7 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
     S.bpart = b.take<double>((size_t)1024 * (Mp * 16 + 16));
     S.bcnt = b.take<int>(512);
     S.lq = b.take<GemmProblem>(12);
-    S.wj = b.take<WgradJob>(d.D_out + 4);
-    {
-      const int tq = (int)ceil_div(v.DP16 / 16, 4), tz = (int)ceil_div(v.DinP16 / 16, 4);
-      S.wtick_cap = (d.D_out + 1) * ti * ti + ti * (tq + tz) + tz * tq + 16;
-      S.wtick = b.take<int32_t>(S.wtick_cap);
-    }
+    S.wj = b.take<WgradJob>(S.cap.jobs); S.wtick = b.take<int32_t>(S.cap.ticks);
     S.ng_gp = b.take<GemmProblem>(4);
     S.ng_items = b.take<PotrfItem>(d.D_out);
   }

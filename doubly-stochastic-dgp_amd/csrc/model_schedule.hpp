@@ -1,6 +1,6 @@
-// Launch schedule of one evaluation: prepare (Ku, factor, parameter products; main / side stream), forward layers (dgp.py:61-76), plan of
-// the weight-gradient products and reductions, reverse pass with the stream overlap and the data-parallel buckets, ELBO / training step.
-// Part of the model translation unit.
+// Launch schedule of one evaluation: prepare (Ku, factor, parameter products; main / side stream), forward layers (dgp.py:61-76), upload
+// of the split-K plan (ensure_plan; the arithmetic is model_plan.hpp), reverse pass — its decisions taken once (BwdSchedule, bwd_schedule),
+// then launches only (backward_layers and its three endings) — ELBO / training step.  Part of the model translation unit.
 #pragma once
 // Side-stream overlap pays for its cross-stream events (a few microseconds each) only when the kernels are long enough:
 // tiny models (cfg 1: 100 rows, M = 50: n S Mp = 6400) are launch-latency-bound and run 40 % faster on a single stream.  The threshold
@@ -13,6 +13,11 @@ static bool overlap_on(const dsdgp_model* m, int64_t n, int S) {
   for (int l = 0; l < m->desc.L; ++l) mp_max = std::max(mp_max, (int)m->L[l].dev.Mp);
   return n * S * (int64_t)mp_max >= (int64_t)m->force.overlap_min;
 }
+
+// The four sub-lists of a layer's own grouped-GEMM problems (LayerState::lq: forward | U, n, KS | U U^T | P_d T_d, GS_d) start here
+static const GemmProblem* lq_unks(const LayerState& S) { return S.lq + S.lq_nf; }
+static const GemmProblem* lq_uut(const LayerState& S) { return lq_unks(S) + S.lq_n1; }
+static const GemmProblem* lq_pt(const LayerState& S) { return lq_uut(S) + S.lq_n2; }
 
 // main stream waits for the parameter-only side work of the last prepare (no-op when nothing is pending)
 static int join_prep(dsdgp_model* m) {
@@ -126,13 +131,13 @@ static int prepare_async(dsdgp_model* m, bool with_grad = false, bool side = fal
   if (with_grad && !m->desc.white) {
     if (lq >= 0) {
       LayerState& Sq = m->L[lq];
-      DS_TRY(gemm_launch(ctx, Sq.lq + Sq.lq_nf, Sq.lq_n1, Sq.lq_t1, st));
-      DS_TRY(gemm_launch(ctx, Sq.lq + Sq.lq_nf + Sq.lq_n1, Sq.lq_n2, Sq.lq_t2, st));
+      DS_TRY(gemm_launch(ctx, lq_unks(Sq), Sq.lq_n1, Sq.lq_t1, st));
+      DS_TRY(gemm_launch(ctx, lq_uut(Sq), Sq.lq_n2, Sq.lq_t2, st));
     } else if (gfirst > 0) {
       for (int l = gfirst; l < L; ++l) {
         LayerState& Sq = m->L[l];
-        DS_TRY(gemm_launch(ctx, Sq.lq + Sq.lq_nf, Sq.lq_n1, Sq.lq_t1, st));
-        DS_TRY(gemm_launch(ctx, Sq.lq + Sq.lq_nf + Sq.lq_n1, Sq.lq_n2, Sq.lq_t2, st));
+        DS_TRY(gemm_launch(ctx, lq_unks(Sq), Sq.lq_n1, Sq.lq_t1, st));
+        DS_TRY(gemm_launch(ctx, lq_uut(Sq), Sq.lq_n2, Sq.lq_t2, st));
       }
     } else {
       DS_TRY(gemm_launch(ctx, m->gp_bwd1, m->n_bwd1, m->t_bwd1, st));
@@ -378,196 +383,223 @@ extern "C" int dsdgp_model_classification(dsdgp_model* m, const double* X, const
                                        accumulate);
 }
 
-// (re)build the split-K job lists for minibatch shape (n, S); uploaded once, reused by every step of that shape
+// (re)build the split-K job lists for minibatch shape (n, S); uploaded once, reused by every step of that shape.  The arithmetic is
+// model_plan.hpp's (pure host code, tests/test_plan_cpu.py); here: capacity checks, clearing, uploads, the record in St / m.
 static int ensure_plan(dsdgp_model* m, int64_t n, int S) {
   if (m->plan_n == n && m->plan_S == S) return DSDGP_OK;
   dsdgp_ctx* ctx = m->ctx;
-  const int L = m->desc.L;
+  const int L = m->desc.L, overlap = overlap_on(m, n, S);
   std::vector<RedJob> red;
+  PlanOut P;
   for (int l = 0; l < L; ++l) {
     LayerState& St = m->L[l];
     const LayerDev& v = St.dev;
-    const int64_t Rin = (l == 0) ? n : (int64_t)S * n;
-    const int64_t ld = round_up(Rin, 16), nch = ld / 16;
-    int NI, ti;
-    wgrad_shapes(v.Mp, NI, ti);
-    const int64_t MM = (int64_t)v.Mp * v.Mp;
-    const int Mw = pad_Mw(v.Mp);
-    const int64_t MMw = (int64_t)Mw * Mw;
-    // G = E A^T is full; the D_out P_d are symmetric: off-diagonal tiles cost 1, diagonal tiles (NI+1)/(2 NI) and get that fraction
-    // of the K splits, so every task carries about the same number of MFMAs.  alg_g layers have no G job (k_asm_kbar
-    // assembles sum_r e a^T from the P_d).
-    const int n_off = ti * (ti - 1) / 2;
-    const double dfrac = (NI + 1) / (2.0 * NI);
-    int ns = choose_nsplit((v.alg_g ? 0 : ti * ti) + v.D_out * n_off + (int)ceil(v.D_out * ti * dfrac), nch, 512);
-    if (ns > St.nsplit_big_max) ns = St.nsplit_big_max;
-    St.ns_big = ns;
-    St.ns_thin = ns;
-    const int ns_diag = std::max(1, (int)ceil(ns * dfrac));
-    const int tjq = ceil_div(v.DP16 / 16, NI), tjz = ceil_div(v.DinP16 / 16, NI);
-    double* const out_q = St.part_thin;
-    double* const out_z = St.part_thin + (int64_t)ns * Mw * v.DP16;
-    std::vector<WgradJob> jobsA, jobsB;
-    std::vector<RedJob> redA, redB;
-    int startA = 0, startB = 0;
-    // in-launch split-K reduction (WgradJob::fin): a job's tiles draw their tickets from St.wtick, the result goes where the reduction
-    // launch used to put it and the job leaves k_reduce_grouped's list.  By default only where the plan has ONE split (large M: more
-    // tiles than workgroup slots — the "reduction" was a copy-and-mirror pass over every P_d): the tile goes from registers to its
-    // place(s) with no partial, no ticket.  With several splits every workgroup of the launch would wait for its partial's write
-    // acknowledgement and draw a ticket before it can leave — measured at config 2 (23 splits of ~17 us tasks, wg_red = 2): the three
-    // product launches 0.114 -> 0.294 ms per step, the step 0.510 -> 0.618 ms; config 3 +2 %.  (wg_red = 0: never; 2: always — parity tests.)
-    const bool wfuse = m->force.wg_red >= 2 || (m->force.wg_red == 1 && ns == 1);
-    int tick_off = 0;
-    auto fuse = [&](WgradJob& J, double* fin, int fin_ld, int fin_rows, int fin_cols) {
-      if (!wfuse) return;
-      J.fin = fin; J.fin_ld = fin_ld; J.fin_rows = fin_rows; J.fin_cols = fin_cols;
-      J.tick = St.wtick + tick_off;
-      tick_off += J.sym ? J.ti * (J.ti + 1) / 2 : J.ti * J.tj;
-    };
-    // ---- A jobs: operands from the forward chain (A, [X^T;1]) and from the producer of this layer's upstream adjoints (VB, MB)
-    // The D_out P_d share their operand A: grouped jobs (WgradJob::ng: up to four P_d per 32 x 32 tile task) load each A fragment once
-    // for the whole group.  Same K splits (ns above fixes every element's order of summation: it must not depend on the grouping), same
-    // partials.  Half the L2 requests but more L2 misses: at config 2 the launch is faster beside the next layer's backward chain and
-    // slower alone; config 3 (Mw = 256) was slower.  So by default only on the two-stream schedule at Mw = 128 with
-    // D_out >= 3 (groups of 3 or 4: a group of two moves as many bytes per MFMA as a 64 x 64 tile), and only for partials (wfuse jobs
-    // keep the 64 x 64 tiles their in-launch reduction stages).  wg_group = 0: never; 2: every shape and schedule (parity tests).
-    const bool wgroup = !wfuse && (m->force.wg_group >= 2 || (m->force.wg_group == 1 && v.D_out >= 3 && ti <= 2 && overlap_on(m, n, S)));
-    const int ngroups = wgroup ? ceil_div(v.D_out, 4) : 0;
-    for (int k = 0, j = 1; k < ngroups; ++k) {
-      const int ng = v.D_out / ngroups + (k < v.D_out % ngroups ? 1 : 0);
-      WgradJob J{};
-      J.P = St.A; J.Q = St.A;
-      J.scale = St.VB + (int64_t)(j - 1) * ld; J.sstride = ld;
-      J.out = St.part_big + (int64_t)j * ns * MMw; J.ostride = (int64_t)ns * MMw;
-      J.ti = ti; J.tj = ti; J.ldo = Mw; J.task_start = startA;
-      J.sym = 1; J.qrows16 = Mw / 16;
-      J.ns_diag = ns_diag; J.ng = ng;
-      startA += 4 * ns * n_off + 3 * ns_diag * ti;      // per split: 4 32-tiles of an off-diagonal 64-tile, 3 of a diagonal one
-      jobsA.push_back(J);
-      for (int o = 0; o < ng; ++o, ++j)
-        redA.push_back(RedJob{J.out + o * J.ostride, v.bigred + (int64_t)j * MM, MM, ns, 0, 0, v.Mp, 16, MMw, Mw, v.Mp});
-    }
-    for (int j = 1; j <= (wgroup ? 0 : v.D_out); ++j) {
-      WgradJob J{};
-      J.P = St.A; J.Q = St.A;
-      J.scale = St.VB + (int64_t)(j - 1) * ld;
-      J.out = St.part_big + (int64_t)j * ns * MMw;
-      J.ti = ti; J.tj = ti; J.ldo = Mw; J.task_start = startA;
-      J.sym = 1; J.qrows16 = Mw / 16;                     // P_d = sum_r vbar_d a a^T is symmetric
-      J.ns_diag = ns_diag; J.ng = 0;
-      startA += ns * n_off + ns_diag * ti;
-      fuse(J, v.bigred + (int64_t)j * MM, v.Mp, v.Mp, v.Mp);
-      jobsA.push_back(J);
-      if (!wfuse) redA.push_back(RedJob{J.out, v.bigred + (int64_t)j * MM, MM, ns, 0, 0, v.Mp, 16, MMw, Mw, v.Mp});   // mirror at 16-block granularity
-    }
-    {
-      WgradJob J{St.A, St.MB, nullptr, out_q, ti, tjq, v.DP16, startA, 0, v.DP16 / 16, 0, 0};      // A mbar^T -> q_mu
-      fuse(J, v.thinq, v.DP16, v.Mp, v.DP16);
-      jobsA.push_back(J);
-    }
-    startA += ns * ti * tjq;
-    if (!wfuse) redA.push_back(RedJob{out_q, v.thinq, (int64_t)v.Mp * v.DP16, ns, 0, 0, 0, 0, (int64_t)Mw * v.DP16, 0, 0});
-    if (St.mean_grad) {
-      // trainable Linear mean function: d loss / d [A ; b] = [X ; 1]^T MB^T  (XT1 is zero-padded to whole 16*NI-row tiles)
-      const int tim = ceil_div(v.DinP16 / 16, NI), tjm = ceil_div(v.DP16 / 16, NI);
-      WgradJob J{St.XT1, St.MB, nullptr, St.part_mean, tim, tjm, v.DP16, startA, 0, v.DP16 / 16, 0, 0};
-      fuse(J, v.meanAB, v.DP16, 16 * NI * tim, v.DP16);
-      jobsA.push_back(J);
-      startA += ns * tim * tjm;
-      if (!wfuse) redA.push_back(RedJob{St.part_mean, v.meanAB, (int64_t)16 * NI * tim * v.DP16, ns, 0, 0, 0, 0, (int64_t)16 * NI * tim * v.DP16, 0, 0});
-    }
-    // ---- B jobs: operands from this layer's backward chain (E, GW)
-    if (!v.alg_g) {
-      WgradJob J{};
-      J.P = St.E; J.Q = St.A; J.scale = nullptr;
-      J.out = St.part_big;
-      J.ti = ti; J.tj = ti; J.ldo = Mw; J.task_start = startB;
-      J.sym = 0; J.qrows16 = Mw / 16; J.ns_diag = ns_diag; J.ng = 0;
-      startB += ns * ti * ti;
-      fuse(J, v.bigred, v.Mp, v.Mp, v.Mp);
-      jobsB.push_back(J);
-      if (!wfuse) redB.push_back(RedJob{J.out, v.bigred, MM, ns, 0, 0, 0, 16, MMw, Mw, v.Mp});
-    }
-    {
-      WgradJob J{St.GW, St.XT1, nullptr, out_z, ti, tjz, v.DinP16, startB, 0, v.DinP16 / 16, 0, 0};   // GW [X|1]^T -> Z
-      fuse(J, v.thinz, v.DinP16, v.Mp, v.DinP16);
-      jobsB.push_back(J);
-    }
-    startB += ns * ti * tjz;
-    if (!wfuse) redB.push_back(RedJob{out_z, v.thinz, (int64_t)v.Mp * v.DinP16, ns, 0, 0, 0, 0, (int64_t)Mw * v.DinP16, 0, 0});
-    redB.push_back(RedJob{St.hyp_part, v.hyp_red, (int64_t)v.D_in + 2, St.gemm ? layer_gemm_hyp_parts(ld, v.Mp) : (int)sm_hyp_parts(ld, v.Mp, v.D_in), 0, 1, 0, 0, (int64_t)v.D_in + 2, 0, 0});
-    // one list [A | B] with cumulative task numbers: one launch per layer
-    std::vector<WgradJob> jobs(jobsA);
-    for (WgradJob J : jobsB) {
-      J.task_start += startA;
-      jobs.push_back(J);
-    }
-    St.njobs = (int)jobs.size();
-    St.njobsA = (int)jobsA.size();
-    St.totA = startA;
-    St.tot_big = startA + startB;
-    St.tot_thin = 0;
-    St.red_off = (int)red.size();
-    red.insert(red.end(), redA.begin(), redA.end());
-    red.insert(red.end(), redB.begin(), redB.end());
-    St.red_n = (int)red.size() - St.red_off;
-    if (tick_off > St.wtick_cap) {
-      dsdgp_set_error("internal: weight-gradient ticket list overflow (%d > %d)", tick_off, St.wtick_cap);
+    const int64_t ld = round_up((l == 0) ? n : (int64_t)S * n, 16);
+    const int hyp_parts = St.gemm ? layer_gemm_hyp_parts(ld, v.Mp) : (int)sm_hyp_parts(ld, v.Mp, v.D_in);
+    plan_layer(PlanIn{&v, &St, ld, hyp_parts, m->force.wg_red, m->force.wg_group, overlap}, P);
+    if (P.ticks > St.cap.ticks) {
+      dsdgp_set_error("internal: weight-gradient ticket list overflow (%d > %d)", P.ticks, St.cap.ticks);
       return DSDGP_ERR_WORKSPACE;
     }
-    DS_HIP(hipMemsetAsync(St.wtick, 0, (size_t)St.wtick_cap * sizeof(int32_t), ctx->stream));
+    if ((int)P.jobs.size() > St.cap.jobs) {
+      dsdgp_set_error("internal: weight-gradient job list overflow (%d jobs > %d slots of wj)", (int)P.jobs.size(), St.cap.jobs);
+      return DSDGP_ERR_WORKSPACE;
+    }
+    St.njobs = (int)P.jobs.size(); St.njobsA = P.njobsA; St.totA = P.totA; St.tot_big = P.tot; St.ns_big = P.ns;
+    St.red_off = (int)red.size();
+    red.insert(red.end(), P.red.begin(), P.red.end());
+    DS_HIP(hipMemsetAsync(St.wtick, 0, (size_t)St.cap.ticks * sizeof(int32_t), ctx->stream));
     // diagonal tiles fill only their first ns_diag partial slots: the rest must read as zero under the new plan
-    DS_HIP(hipMemsetAsync(St.part_big, 0, (size_t)St.nsplit_big_max * (1 + v.D_out) * MMw * sizeof(double), ctx->stream));
-    DS_HIP(hipMemcpyAsync(St.wj, jobs.data(), jobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice, ctx->stream));
+    DS_HIP(hipMemsetAsync(St.part_big, 0, St.cap.part_big * sizeof(double), ctx->stream));
+    DS_HIP(hipMemcpyAsync(St.wj, P.jobs.data(), P.jobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice, ctx->stream));
     DS_HIP(hipStreamSynchronize(ctx->stream));
   }
-  int blocks = 0;
-  bool any64 = false;
-  for (auto& r : red) {
-    r.ways = (!r.wide && r.nsplit >= 12) ? 4 : 0;
-    const bool even = r.count % 2 == 0 && r.pstride % 2 == 0 && r.in_ld % 2 == 0 && r.out_ld % 2 == 0 && r.sym_tile % 2 == 0 &&
-                      ((uintptr_t)r.part & 15) == 0;
-    if (r.ways == 4 && even) r.ways = 8;
-    const int64_t rows = r.out_ld > 0 ? r.count / r.out_ld : 0;
-    const bool tiled = !r.wide && r.sym_n > 0 && r.sym_tile == 16 && r.out_ld > 0 && rows == r.out_ld && rows % 16 == 0 && even;
-    if (tiled) r.ways = 16;
-    // one or two splits of a symmetric result on whole 64-tiles: the copy-and-mirror form (one 64 x 64 tile per workgroup)
-    const bool tiled64 = tiled && r.nsplit <= 2 && rows % 64 == 0 && r.sym_n % 64 == 0 && ((uintptr_t)r.out & 15) == 0;
-    if (tiled64) {
-      r.ways = 64;
-      any64 = true;
-    }
-    r.blk_start = blocks;
-    blocks += r.wide ? (int)r.count
-                     : (tiled64 ? (int)((rows / 64) * (rows / 64 + 1) / 2)
-                                : (tiled ? (int)((rows / 16) * (rows / 16 + 1) / 2) : ceil_div(r.count, r.ways == 8 ? 128 : (r.ways == 4 ? 64 : 256))));
-  }
-  for (int l = 0; l < L; ++l) {
-    LayerState& St = m->L[l];
-    auto blk_at = [&](int idx) { return idx < (int)red.size() ? red[idx].blk_start : blocks; };
-    St.red_blk0 = blk_at(St.red_off);
-    St.red_blkn = blk_at(St.red_off + St.red_n) - St.red_blk0;
-  }
+  const RedPlan rp = plan_reductions(red);
+  for (int l = 0; l < L; ++l) m->L[l].red_blk0 = red[m->L[l].red_off].blk_start;      // (every layer has its hyper-parameter job)
   if ((int)red.size() > m->rjobs_cap) {
     dsdgp_set_error("internal: reduction job list overflow");
     return DSDGP_ERR_WORKSPACE;
   }
   DS_HIP(hipMemcpyAsync(m->rjobs, red.data(), red.size() * sizeof(RedJob), hipMemcpyHostToDevice, ctx->stream));
   DS_HIP(hipStreamSynchronize(ctx->stream));
-  m->n_red = (int)red.size();
-  m->red_blocks = blocks;
-  m->red_lds = any64 ? 64 * 65 * sizeof(double) : 0;      // dynamic LDS of k_reduce_grouped: the 64 x 64 copy-and-mirror tile
-  m->plan_n = n;
-  m->plan_S = S;
+  m->n_red = (int)red.size(); m->red_blocks = rp.blocks;
+  m->red_lds = rp.any64 ? 64 * 65 * sizeof(double) : 0;      // dynamic LDS of k_reduce_grouped: the 64 x 64 copy-and-mirror tile
+  m->plan_n = n; m->plan_S = S;
   return DSDGP_OK;
+}
+
+// layer l's parameters are one segment of theta: [off_Z, next layer's off_Z); the last ends at the likelihood's parameter or the vector's end
+static int64_t theta_segment_lo(const dsdgp_model* m, int l) {
+  return l < m->desc.L ? m->L[l].d.off_Z : (lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : m->desc.n_theta);
+}
+// offset of the likelihood's positive parameter in theta / grad, -1: it has none
+static int64_t lik_var_offset(const dsdgp_model* m) { return lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : (int64_t)-1; }
+static FinArgs fin_args(const dsdgp_model* m) {
+  return FinArgs{m->lik_part, m->fin.nblocks, m->fin.w, m->fin.kl_weight, m->lik_const, lik_var_offset(m), m->fin.out, m->desc.L, 1};
 }
 
 static int launch_finalize(dsdgp_model* m, hipStream_t st) {
   DS_LAUNCH(k_finalize, dim3(1), dim3(256), 0, st, m->layers_dev, m->desc.L, m->lik_part, m->fin.nblocks, m->fin.w,
-                     m->fin.kl_weight, m->lik_const, m->grad,
-                     lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : (int64_t)-1, m->fin.with_grad, m->fin.out);
+                     m->fin.kl_weight, m->lik_const, m->grad, lik_var_offset(m), m->fin.with_grad, m->fin.out);
   DS_HIP(hipGetLastError());
   m->fin.done = true;
+  return DSDGP_OK;
+}
+
+// The schedule of one reverse pass: every decision, taken once before the first launch (bwd_schedule; on the caller's stack).
+// Who writes a layer's transposed upstream adjoints MB / VB (+ [X^T ; 1]): the producer where one exists — the likelihood kernel
+// for the last layer, the next layer's backward chain for inner layers; for a first layer below others this layer's own backward
+// chain in its prologue (LayerBwdArgs::up_dF); else (first layer: S output rows per input row; MultiClass) k_adj_prep
+enum AdjFrom : uint8_t { ADJ_PRODUCER, ADJ_PROLOGUE, ADJ_PREP };
+// Where a layer's weight-gradient products go: main stream behind its chain, side stream behind an event at the end of its chain,
+// or main stream behind the lowest layer's products (defer_upper)
+enum ProductsAt : uint8_t { PROD_MAIN, PROD_SIDE, PROD_DEFERRED };
+struct BwdSchedule {
+  int gfirst; bool overlap, bucketed, pipelined, kinv_only, q_only, defer_upper, red_ahead;
+  struct Layer { AdjFrom adj; bool chain; int d_split; ProductsAt products; } layer[DSDGP_MAX_LAYERS];      // entries [gfirst, L)
+};
+static BwdSchedule bwd_schedule(const dsdgp_model* m, int64_t n, int S) {
+  const int L = m->desc.L;
+  BwdSchedule s{}; s.overlap = overlap_on(m, n, S);
+  const int g = s.gfirst = m->desc.white ? 0 : m->grad_first;     // reverse mode stops below this layer (dsdgp_model_set_grad_first_layer)
+  // data-parallel buckets: every layer's reduction, products, assembly and hyper-parameter gradients right behind its weight-gradient
+  // products, then the caller's collective on that layer's segment of the gradient, on the stream the segment was produced on — the
+  // exchange of the upper layers runs under the lower layers' backward chains (dsdgp_model_set_bucket_callback)
+  s.bucketed = m->bucket_fn != nullptr && m->tail_ok && g == 0 && !m->fuse_adam.on;
+  s.pipelined = s.bucketed || (s.overlap && m->force.pipe_tail != 0 && !m->desc.white);
+  // Ku^-1, S_d (and KS, U, UU for the assembly) come from the side stream.  In the overlapped schedule the chains wait for the event
+  // behind the first of those launches only (prepare_async: ev_kinv); the join with the side stream at the end of backward_layers — which
+  // the assembly launches follow — covers the rest.  The per-layer tails (buckets) read KS / U inside the loop: they take the full join.
+  s.kinv_only = s.overlap && !s.pipelined && !m->desc.white && m->kinv_pending && m->side_pending;
+  // (q_mu, q_sqrt)-only gradients (dsdgp_model_set_grad_q_only): the lowest layer of the pass needs d/dq_mu = sum_r a mbar^T and
+  // d/dq_sqrt_d = 2 tril(P_d q_sqrt_d), P_d = sum_r vbar_d a a^T — the forward pass's A and the upstream adjoints, nothing the backward
+  // chain produces (E, GW, dX feed Z, the kernel hyper-parameters and the layers below): no chain, and only the A jobs of its products
+  s.q_only = m->grad_q_only && !m->desc.white;
+  // Deep models (round 5): only the products of layer gfirst + 1 go to the side stream (they run under the lowest chain, the one launch
+  // with too few row blocks to fill the chip); those of the layers above follow the lowest layer's products on the main stream — no
+  // event record / wait pair per layer (6 + 12 us) and no products squeezed in beside a chain that saturates the MFMA pipe anyway.
+  // 5-layer config 3: 7.60 -> 7.37 ms per step; the 3-layer configs (one deferred launch) are within +-1 %, so the rule starts at
+  // four layers in the pass.  (DSDGP_FORCE wg_defer = 0 / 2: off / on at any depth.)
+  s.defer_upper = s.overlap && !s.pipelined && (m->force.wg_defer == 2 || (m->force.wg_defer < 0 && L - g >= 4));
+  // the lowest layer's products ran on the main stream: its split-K reduction goes ahead of the join, so that the side stream's
+  // completion signal (a just-in-time cross-stream wait costs ~12 us of idle time) travels while the main stream works
+  s.red_ahead = s.overlap && !s.pipelined && g == 0 && L > 1 && m->force.red_ahead != 0;
+  for (int l = g; l < L; ++l) {
+    const LayerState& St = m->L[l];
+    const LayerDev& v = St.dev;
+    BwdSchedule::Layer& y = s.layer[l];
+    const bool last = (l == L - 1), produced = last ? m->fused_last : l >= 1;
+    const int64_t nblk = St.ld_used / 16;
+    y.chain = !(s.q_only && l == g);
+    const bool prologue = !produced && !last && y.chain && m->force.adj_fuse != 0 && !St.c_used && !St.gemm && sm_adj_fusable(v.Mp, nblk, v.D_in, v.D_out);
+    y.adj = produced ? ADJ_PRODUCER : (prologue ? ADJ_PROLOGUE : ADJ_PREP);
+    // few row blocks (the N-row first layer, small shards): spread the d-loop over up to four workgroups per row block.
+    // Only from Mp = 512 (bwd_split = 2 forces it everywhere, 0 disables): every workgroup of a split repeats the chain's prologue
+    // and epilogue phases.  63-row-block first layer of config 2 (M = 128): +57 us with the __threadfence() hand-over of
+    // round 2, still +6 us per step with the fence-free sc1 hand-over of round 3 (cutting the upper layer's weight-gradient
+    // task list over both streams to use the shortened chain: +10..+20 us); -0.9 ms on the 32-row-block, 30-output first
+    // layer of config 4 (M = 512)
+    const bool want = m->force.bwd_split >= 2 || (m->force.bwd_split == 1 && v.Mp > 256);
+    y.d_split = (want && St.bpart) ? chain_d_split(nblk, v.D_out) : 1;
+    // the lowest layer of the reverse pass keeps its products on the main stream: nothing is left to run them under, and the
+    // join then waits for side-stream work that finished long ago instead of for a just-in-time signal
+    const bool on_main = s.overlap && l == g && L - g > 1;
+    y.products = (!s.overlap || on_main) ? PROD_MAIN : ((s.defer_upper && l >= g + 2) ? PROD_DEFERRED : PROD_SIDE);
+  }
+  return s;
+}
+
+// argument block of layer l's backward chain
+static LayerBwdArgs fill_bwd_args(const dsdgp_model* m, int l, const BwdSchedule& sc, int64_t n) {
+  const LayerState& St = m->L[l];
+  const LayerDev& v = St.dev;
+  LayerBwdArgs b{};
+  b.X = St.X_used; b.Rin = St.Rin_used; b.D_in = v.D_in; b.D_out = v.D_out; b.M = v.M; b.DP4 = v.DP4;
+  b.Zp = v.Zp; b.Zs = v.Zs; b.hyp = v.hyp; b.Kinv = v.Kinv; b.Linv = v.Linv; b.LinvT = v.LinvT; b.Sd = v.Sd; b.qmu4 = v.qmu4;
+  b.Asave = St.A; b.Csave = St.c_used ? St.C : nullptr; b.Tp = v.Tp; b.TpT = v.TpT; b.ldA = St.ld_used; b.VB = St.VB; b.MB = St.MB;
+  b.E = v.alg_g ? nullptr : St.E; b.GW = St.GW;
+  b.dX = (l > sc.gfirst) ? m->L[l - 1].dF : nullptr;
+  if (l >= 2 && l > sc.gfirst) {   // the previous layer is an inner layer: hand it its transposed adjoints directly
+    const LayerState& Pv = m->L[l - 1];
+    b.dX = nullptr;
+    b.MBp = Pv.MB; b.VBp = Pv.VB;
+    b.zp = Pv.z_used; b.zp_s = Pv.zs_s; b.zp_n = Pv.zs_n; b.zp_d = Pv.zs_d; b.n_inner = n;
+    b.varp = Pv.var; b.Dp = Pv.dev.D_out; b.prop = Pv.prop; b.jitter = m->desc.jitter;
+  }
+  b.mean_kind = St.d.mean_kind; b.mean_A = St.meanA; b.hyp_part = St.hyp_part;
+  if (sc.layer[l].adj == ADJ_PROLOGUE) {
+    b.up_dF = St.dF; b.up_rep = St.rep_used; b.up_ld = v.D_out + St.prop; b.up_off = St.prop;
+    b.up_z = St.z_used; b.up_zs = St.zs_s; b.up_zn = St.zs_n; b.up_zd = St.zs_d; b.up_n_inner = n;
+    b.up_var = St.var; b.up_jitter = m->desc.jitter; b.MBw = St.MB; b.VBw = St.VB;
+  }
+  b.d_split = sc.layer[l].d_split; b.part = St.bpart; b.part_cnt = St.bcnt;
+  return b;
+}
+
+// split-K reductions of the layers [first, end): their jobs and blocks are contiguous in the plan (ordered by layer)
+static int launch_reduce(dsdgp_model* m, int first, int end, hipStream_t st) {
+  const LayerState& S0 = m->L[first];
+  const int njobs = (end < m->desc.L ? m->L[end].red_off : m->n_red) - S0.red_off;
+  const int nblk = (end < m->desc.L ? m->L[end].red_blk0 : m->red_blocks) - S0.red_blk0;
+  DS_LAUNCH(k_reduce_grouped, dim3(nblk), dim3(256), m->red_lds, st, m->rjobs + S0.red_off, njobs, S0.red_blk0);
+  DS_HIP(hipGetLastError());
+  return DSDGP_OK;
+}
+// (a layer without a backward chain — q_only, the lowest — has only the A jobs of its products)
+static int launch_wgrad(dsdgp_model* m, const BwdSchedule& sc, int l, hipStream_t st) {
+  const LayerState& Sx = m->L[l];
+  const bool all = sc.layer[l].chain;
+  return wgrad_launch(m->ctx, Sx.wj, all ? Sx.njobs : Sx.njobsA, all ? Sx.tot_big : Sx.totA, Sx.ns_big, Sx.ld_used, Sx.ld_used, st);
+}
+// split-K reduction + P_d T_d / GS_d products of one layer right behind its weight-gradient products (pipelined tail); bucketed:
+// its assembly and the caller's collective on its segment of the gradient as well
+static int layer_tail(dsdgp_model* m, const BwdSchedule& sc, int l, hipStream_t st, double kl_weight) {
+  const LayerState& St = m->L[l];
+  DS_TRY(launch_reduce(m, l, l + 1, st));
+  DS_TRY(gemm_launch(m->ctx, lq_pt(St), St.lq_np, St.lq_tp, st));
+  if (sc.bucketed) {
+    DS_LAUNCH(k_asm_rows, dim3(St.dev.M, 1), dim3(256), (size_t)m->mp_max_all * sizeof(double), st, (const LayerDev*)(m->layers_dev + l), m->grad,
+              kl_weight, m->mp_max_all, m->force.asm_pre);
+    DS_LAUNCH(k_tail, dim3(1), dim3(256), 0, st, m->layers_dev, l, 1, m->grad, FinArgs{}, AdamArgs{});
+    DS_HIP(hipGetLastError());
+    const int64_t lo = theta_segment_lo(m, l);
+    m->bucket_fn(m->bucket_user, l, m->grad + lo, theta_segment_lo(m, l + 1) - lo, (void*)st);
+  }
+  return DSDGP_OK;
+}
+
+// The three endings of a reverse pass.  Bucketed: the last bucket — likelihood-variance gradient and the four result scalars (contiguous behind the layers' segments when
+// `out` is grad + n_theta, as the contract of dsdgp_allreduce asks)
+static int end_last_bucket(dsdgp_model* m, hipStream_t st) {
+  const int L = m->desc.L;
+  DS_LAUNCH(k_tail, dim3(1), dim3(256), 0, st, m->layers_dev, 0, 0, m->grad, fin_args(m), AdamArgs{});
+  DS_HIP(hipGetLastError());
+  m->fin.done = true;
+  const int64_t lo = theta_segment_lo(m, L);
+  const bool tail_scalars = m->fin.out == m->grad + m->desc.n_theta;
+  m->bucket_fn(m->bucket_user, L, m->grad + lo, (m->desc.n_theta - lo) + (tail_scalars ? 4 : 0), (void*)st);
+  if (!tail_scalars) m->bucket_fn(m->bucket_user, L + 1, m->fin.out, 4, (void*)st);
+  return DSDGP_OK;
+}
+// tail_ok: one wave per inducing row (k_asm_rows), then hyper-parameter gradients, value and — in a training step — Adam (k_tail)
+static int end_rows_tail(dsdgp_model* m, hipStream_t st, int gfirst, int La, double kl_weight) {
+  DS_LAUNCH(k_asm_rows, dim3(m->m_max_all, La), dim3(256), (size_t)m->mp_max_all * sizeof(double), st, (const LayerDev*)(m->layers_dev + gfirst),
+            m->grad, kl_weight, m->mp_max_all, m->force.asm_pre);
+  AdamArgs A{m->theta, m->adam_m, m->adam_v, m->mask, m->desc.n_theta, m->fuse_adam.lr_t, m->fuse_adam.b1, m->fuse_adam.b2,
+             m->fuse_adam.eps, (m->fuse_adam.on && gfirst == 0) ? 1 : 0};
+  const int nadam = A.on ? (int)std::min<int64_t>(2048, ceil_div(m->desc.n_theta, 512)) : 0;      // a thread per pair of entries, eight workgroups per CU
+  DS_LAUNCH(k_tail, dim3(La + 1 + nadam), dim3(256), 0, st, m->layers_dev, gfirst, La, m->grad, fin_args(m), A);
+  DS_HIP(hipGetLastError());
+  m->fin.done = true;
+  return DSDGP_OK;
+}
+// white=True / wide inputs: the unfused assembly (the value follows in k_finalize)
+static int end_unfused(dsdgp_model* m, hipStream_t st, const LayerDev* lay, int La, double kl_weight) {
+  DS_LAUNCH(k_asm_kbar, dim3(m->kuu_blocks, La), dim3(256), 0, st, lay, kl_weight);
+  if (m->n_wz) DS_TRY(gemm_launch(m->ctx, m->gp_wz, m->n_wz, m->t_wz));   // (wm of the layers below gfirst is stale: their WZ is never read)
+  if (m->need_hyp_part) DS_LAUNCH(k_asm_hyp_part, dim3(NPART, La), dim3(256), 0, st, lay);
+  DS_LAUNCH(k_asm_params, dim3(m->asm_blocks + 1, La), dim3(256), 0, st, lay, m->grad, kl_weight);
+  DS_HIP(hipGetLastError());
   return DSDGP_OK;
 }
 
@@ -579,153 +611,53 @@ static int launch_finalize(dsdgp_model* m, hipStream_t st) {
 //          tail); with the pipelined tail (data-parallel buckets) also that layer's reduction, products and assembly.
 // Every reduction is fixed-order, so the schedule does not change a bit of the result (tests/test_gpu_parity.py:
 // test_stream_overlap_is_bitwise_neutral, tests/test_gpu_round3.py).
+// The decisions are bwd_schedule's; here: wait, the layers (adjoint producer -> chain -> products), reductions, join, ending.
 static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
   dsdgp_ctx* ctx = m->ctx;
   const int L = m->desc.L;
   DS_TRY(ensure_plan(m, n, S));
-  const bool overlap = overlap_on(m, n, S);
-  // Ku^-1, S_d (and KS, U, UU for the assembly below) come from the side stream.  In the overlapped schedule the chains wait for the event
-  // behind the first of those launches only (prepare_async: ev_kinv); the join with the side stream at the end of this function — which
-  // the assembly launches follow — covers the rest.  The per-layer tails (buckets) read KS / U inside the loop: they take the full join.
-  const int gfirst0 = m->desc.white ? 0 : m->grad_first;
-  const bool tail_in_loop = (m->bucket_fn != nullptr && m->tail_ok && gfirst0 == 0 && !m->fuse_adam.on) ||
-                            (overlap && m->force.pipe_tail != 0 && !m->desc.white);
-  const bool kinv_only = overlap && !tail_in_loop && !m->desc.white && m->kinv_pending && m->side_pending;
-  if (kinv_only) DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_kinv, 0));
+  const BwdSchedule sc = bwd_schedule(m, n, S);
+  const int gfirst = sc.gfirst;
+  if (sc.kinv_only) DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_kinv, 0));
   else DS_TRY(join_prep(m));
-  const int gfirst = m->desc.white ? 0 : m->grad_first;     // reverse mode stops below this layer (dsdgp_model_set_grad_first_layer)
-  // data-parallel buckets: every layer's reduction, products, assembly and hyper-parameter gradients right behind its weight-gradient
-  // products, then the caller's collective on that layer's segment of the gradient, on the stream the segment was produced on — the
-  // exchange of the upper layers runs under the lower layers' backward chains (dsdgp_model_set_bucket_callback)
-  const bool bucketed = m->bucket_fn != nullptr && m->tail_ok && gfirst == 0 && !m->fuse_adam.on;
-  const bool pipelined = bucketed || (overlap && m->force.pipe_tail != 0 && !m->desc.white);
-  // split-K reduction + P_d T_d / GS_d products of one layer right behind its weight-gradient products (pipelined tail)
-  auto layer_tail = [&](LayerState& St, hipStream_t st) -> int {
-    DS_LAUNCH(k_reduce_grouped, dim3(St.red_blkn), dim3(256), m->red_lds, st, m->rjobs + St.red_off, St.red_n, St.red_blk0);
-    DS_HIP(hipGetLastError());
-    DS_TRY(gemm_launch(ctx, St.lq + St.lq_nf + St.lq_n1 + St.lq_n2, St.lq_np, St.lq_tp, st));
-    if (bucketed) {
-      const int l = (int)(&St - m->L);
-      const LayerDev* lay1 = m->layers_dev + l;
-      DS_LAUNCH(k_asm_rows, dim3(St.dev.M, 1), dim3(256), (size_t)m->mp_max_all * sizeof(double), st, lay1, m->grad, kl_weight,
-                         m->mp_max_all, m->force.asm_pre);
-      FinArgs F{};
-      AdamArgs A{};
-      DS_LAUNCH(k_tail, dim3(1), dim3(256), 0, st, m->layers_dev, l, 1, m->grad, F, A);
-      DS_HIP(hipGetLastError());
-      // this layer's parameters are one contiguous segment of theta: [off_Z, next layer's off_Z) (the last layer's ends where the
-      // likelihood variance or the vector ends)
-      const int64_t lo = St.d.off_Z;
-      const int64_t hi = (l + 1 < L) ? m->L[l + 1].d.off_Z
-                                     : (lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : m->desc.n_theta);
-      m->bucket_fn(m->bucket_user, l, m->grad + lo, hi - lo, (void*)st);
-    }
-    return DSDGP_OK;
-  };
-  // (q_mu, q_sqrt)-only gradients (dsdgp_model_set_grad_q_only): the lowest layer of the pass needs d/dq_mu = sum_r a mbar^T and
-  // d/dq_sqrt_d = 2 tril(P_d q_sqrt_d), P_d = sum_r vbar_d a a^T — the forward pass's A and the upstream adjoints, nothing the backward
-  // chain produces (E, GW, dX feed Z, the kernel hyper-parameters and the layers below): no chain, and only the A jobs of its products
-  const bool q_only = m->grad_q_only && !m->desc.white;
-  auto launch_wgrad = [&](LayerState& Sx, hipStream_t st) -> int {
-    const int64_t ldx = Sx.ld_used;
-    if (q_only && &Sx == &m->L[gfirst]) return wgrad_launch(ctx, Sx.wj, Sx.njobsA, Sx.totA, Sx.ns_big, ldx, ldx, st);
-    return wgrad_launch(ctx, Sx.wj, Sx.njobs, Sx.tot_big, Sx.ns_big, ldx, ldx, st);
-  };
-  // Deep models (round 5): only the products of layer gfirst + 1 go to the side stream (they run under the lowest chain, the one launch
-  // with too few row blocks to fill the chip); those of the layers above follow the lowest layer's products on the main stream — no
-  // event record / wait pair per layer (6 + 12 us) and no products squeezed in beside a chain that saturates the MFMA pipe anyway.
-  // 5-layer config 3: 7.60 -> 7.37 ms per step; the 3-layer configs (one deferred launch) are within +-1 %, so the rule starts at
-  // four layers in the pass.  (DSDGP_FORCE wg_defer = 0 / 2: off / on at any depth.)
-  const bool defer_upper = overlap && !pipelined && (m->force.wg_defer == 2 || (m->force.wg_defer < 0 && L - gfirst >= 4));
   for (int l = L - 1; l >= gfirst; --l) {
     LayerState& St = m->L[l];
     const LayerDev& v = St.dev;
     const bool last = (l == L - 1);
-    const int64_t Rin = St.Rin_used, ld = St.ld_used;
-    const int rep = St.rep_used;
-    // transposed upstream adjoints MB / VB (+ [X^T ; 1]): written by the producer where one exists — the likelihood kernel
-    // for the last layer, the next layer's backward chain for inner layers — else (first layer: S output rows per input
-    // row; MultiClass) by k_adj_prep
-    const bool fused = (last && m->fused_last) || (!last && l >= 1);
-    // ... or, for a first layer below others, by this layer's own backward chain in its prologue (LayerBwdArgs::up_dF)
-    const bool skip_chain = q_only && l == gfirst;
-    const bool in_chain = !fused && !last && !skip_chain && m->force.adj_fuse != 0 && !St.c_used && !St.gemm &&
-                          sm_adj_fusable(v.Mp, ld / 16, v.D_in, v.D_out);
-    if (!fused && !in_chain)
+    const int64_t ld = St.ld_used;
+    if (sc.layer[l].adj == ADJ_PREP)
       DS_LAUNCH(k_adj_prep, dim3(ceil_div(ld, 256), std::max(v.DP16, v.DinP16)), dim3(256), 0, ctx->stream, last ? nullptr : St.dF,
                          last ? m->lik_dmean : nullptr, last ? m->lik_dvar : nullptr, St.z_used, St.zs_s, St.zs_n,
-                         St.zs_d, n, St.var, St.X_used, Rin, rep, v.D_in, v.D_out, v.DP16, v.DinP16, m->desc.jitter, ld,
+                         St.zs_d, n, St.var, St.X_used, St.Rin_used, St.rep_used, v.D_in, v.D_out, v.DP16, v.DinP16, m->desc.jitter, ld,
                          St.MB, St.VB, St.XT1, v.D_out + St.prop, St.prop);
     DS_HIP(hipGetLastError());
-    // the lowest layer of the reverse pass keeps its products on the main stream: nothing is left to run them under, and the
-    // join below then waits for side-stream work that finished long ago instead of for a just-in-time signal
-    const bool on_main = overlap && l == gfirst && L - gfirst > 1;
-    LayerBwdArgs b{};
-    b.X = St.X_used; b.Rin = Rin; b.D_in = v.D_in; b.D_out = v.D_out; b.M = v.M; b.DP4 = v.DP4;
-    b.Zp = v.Zp; b.Zs = v.Zs; b.hyp = v.hyp; b.Kinv = v.Kinv; b.Linv = v.Linv; b.LinvT = v.LinvT; b.Sd = v.Sd; b.qmu4 = v.qmu4;
-    b.Asave = St.A; b.Csave = St.c_used ? St.C : nullptr; b.Tp = v.Tp; b.TpT = v.TpT; b.ldA = ld; b.VB = St.VB; b.MB = St.MB;
-    b.E = v.alg_g ? nullptr : St.E; b.GW = St.GW;
-    b.dX = (l > gfirst) ? m->L[l - 1].dF : nullptr;
-    if (l >= 2 && l > gfirst) {   // the previous layer is an inner layer: hand it its transposed adjoints directly
-      LayerState& Pv = m->L[l - 1];
-      b.dX = nullptr;
-      b.MBp = Pv.MB; b.VBp = Pv.VB;
-      b.zp = Pv.z_used; b.zp_s = Pv.zs_s; b.zp_n = Pv.zs_n; b.zp_d = Pv.zs_d; b.n_inner = n;
-      b.varp = Pv.var; b.Dp = Pv.dev.D_out; b.prop = Pv.prop; b.jitter = m->desc.jitter;
-    }
-    b.mean_kind = St.d.mean_kind; b.mean_A = St.meanA;
-    b.hyp_part = St.hyp_part;
-    if (in_chain) {
-      b.up_dF = St.dF; b.up_rep = rep; b.up_ld = v.D_out + St.prop; b.up_off = St.prop;
-      b.up_z = St.z_used; b.up_zs = St.zs_s; b.up_zn = St.zs_n; b.up_zd = St.zs_d; b.up_n_inner = n;
-      b.up_var = St.var; b.up_jitter = m->desc.jitter; b.MBw = St.MB; b.VBw = St.VB;
-    }
-    {   // few row blocks (the N-row first layer, small shards): spread the d-loop over up to four workgroups per row block.
-        // Only from Mp = 512 (bwd_split = 2 forces it everywhere, 0 disables): every workgroup of a split repeats the chain's prologue
-        // and epilogue phases.  63-row-block first layer of config 2 (M = 128): +57 us with the __threadfence() hand-over of
-        // round 2, still +6 us per step with the fence-free sc1 hand-over of round 3 (cutting the upper layer's weight-gradient
-        // task list over both streams to use the shortened chain: +10..+20 us); -0.9 ms on the 32-row-block, 30-output first
-        // layer of config 4 (M = 512)
-      const int64_t nblk = ld / 16;
-      const bool want = m->force.bwd_split >= 2 || (m->force.bwd_split == 1 && v.Mp > 256);
-      const int ds = (want && St.bpart) ? chain_d_split(nblk, v.D_out) : 1;
-      b.d_split = ds; b.part = St.bpart; b.part_cnt = St.bcnt;
-    }
+    const LayerBwdArgs b = fill_bwd_args(m, l, sc, n);
     if (last && m->last_deferred) {
       DS_TRY(layer_last_launch(ctx, m->last_fwd, b, v.Mp, v.kern_kind, (int)(sm_hyp_parts(ld, v.Mp, v.D_in) / (ld / 16))));
       m->last_deferred = false;
-    } else if (skip_chain) { /* nothing downstream of this layer's chain is wanted */ }
+    } else if (!sc.layer[l].chain) { /* nothing downstream of this layer's chain is wanted */ }
     else if (St.gemm) DS_TRY(layer_bwd_gemm_launch(ctx, b, v.Mp, v.kern_kind, m->desc.white ? 1 : 0, m->gws));
     else DS_TRY(layer_bwd_sm_launch(ctx, b, v.Mp, v.kern_kind, m->desc.white));
     // in-launch split-K reduction: what is left for k_reduce_grouped of this layer are the chain's hyper-parameter partials — added
     // right behind the chain (a handful of workgroups beside the side stream's products) instead of in a launch behind the final join
-    if (!overlap || on_main) {
-      DS_TRY(launch_wgrad(St, ctx->stream));
-      if (defer_upper)
-        for (int lu = gfirst + 2; lu < L; ++lu) DS_TRY(launch_wgrad(m->L[lu], ctx->stream));
-      if (pipelined) DS_TRY(layer_tail(St, ctx->stream));
-      continue;
+    if (sc.layer[l].products == PROD_MAIN) {
+      DS_TRY(launch_wgrad(m, sc, l, ctx->stream));
+      for (int lu = l + 1; lu < L; ++lu)
+        if (sc.layer[lu].products == PROD_DEFERRED) DS_TRY(launch_wgrad(m, sc, lu, ctx->stream));
+      if (sc.pipelined) DS_TRY(layer_tail(m, sc, l, ctx->stream, kl_weight));
+    } else if (sc.layer[l].products == PROD_SIDE) {
+      // ONE event per chain boundary (an event record costs the recording stream ~6 us): behind it the side stream takes this layer's
+      // products, which then run under the NEXT layer's backward chain.  Measured slower and removed in round 3: the products of a layer
+      // ahead of its own chain's end (they need only the upstream adjoints), completion events attached to the chain / product launches
+      // (hipExtLaunchKernelGGL: +3 us), a cap on the split count.
+      DS_HIP(hipEventRecord(m->ev_bwd[l], ctx->stream));
+      DS_HIP(hipStreamWaitEvent(m->side, m->ev_bwd[l], 0));
+      DS_TRY(launch_wgrad(m, sc, l, m->side));
+      if (sc.pipelined) DS_TRY(layer_tail(m, sc, l, m->side, kl_weight));
     }
-    if (defer_upper && l >= gfirst + 2) continue;
-    // ONE event per chain boundary (an event record costs the recording stream ~6 us): behind it the side stream takes this layer's
-    // products, which then run under the NEXT layer's backward chain.  Measured slower and removed in round 3: the products of a layer
-    // ahead of its own chain's end (they need only the upstream adjoints), completion events attached to the chain / product launches
-    // (hipExtLaunchKernelGGL: +3 us), a cap on the split count.
-    hipStream_t ss = m->side;
-    DS_HIP(hipEventRecord(m->ev_bwd[l], ctx->stream));
-    DS_HIP(hipStreamWaitEvent(ss, m->ev_bwd[l], 0));
-    DS_TRY(launch_wgrad(St, ss));
-    if (pipelined) DS_TRY(layer_tail(St, ss));
   }
-  // the lowest layer's products ran on the main stream: its split-K reduction goes ahead of the join, so that the side stream's
-  // completion signal (a just-in-time cross-stream wait costs ~12 us of idle time) travels while the main stream works
-  const bool red_ahead = overlap && !pipelined && gfirst == 0 && L > 1 && m->force.red_ahead != 0;
-  if (red_ahead) {
-    LayerState& S0 = m->L[0];
-    DS_LAUNCH(k_reduce_grouped, dim3(S0.red_blkn), dim3(256), m->red_lds, ctx->stream, m->rjobs + S0.red_off, S0.red_n, S0.red_blk0);
-    DS_HIP(hipGetLastError());
-  }
-  if (overlap) {
+  if (sc.red_ahead) DS_TRY(launch_reduce(m, 0, 1, ctx->stream));
+  if (sc.overlap) {
     // value + likelihood-variance gradient: needs the likelihood partials (main, before ev_bwd) and KL (side).  AFTER the
     // weight-gradient launches: its single workgroup was observed to sit for > 1 ms behind the co-running large-M chain, and
     // everything queued behind it on this stream waited with it
@@ -733,20 +665,10 @@ static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
     DS_HIP(hipEventRecord(m->ev_side, m->side));
     DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_side, 0));
     m->side_pending = false;      // (in order behind the parameter products: this join is theirs too)
-
   }
-  if (!pipelined) {
-    if (red_ahead) {
-      LayerState& S1 = m->L[1];
-      DS_LAUNCH(k_reduce_grouped, dim3(m->red_blocks - S1.red_blk0), dim3(256), m->red_lds, ctx->stream, m->rjobs + S1.red_off,
-                         m->n_red - S1.red_off, S1.red_blk0);
-    } else {
-      // (the partial sums of the layers below a pruned pass are stale: their jobs — ordered by layer — are left out)
-      const LayerState& Sg = m->L[gfirst];
-      DS_LAUNCH(k_reduce_grouped, dim3(m->red_blocks - Sg.red_blk0), dim3(256), m->red_lds, ctx->stream, m->rjobs + Sg.red_off,
-                         m->n_red - Sg.red_off, Sg.red_blk0);
-    }
-    DS_HIP(hipGetLastError());
+  if (!sc.pipelined) {
+    // (the partial sums of the layers below a pruned pass are stale: their jobs — ordered by layer — are left out)
+    DS_TRY(launch_reduce(m, sc.red_ahead ? 1 : gfirst, L, ctx->stream));
     if (m->desc.white) {
       DS_LAUNCH(k_white_lbar, dim3(32, L), dim3(256), 0, ctx->stream, m->layers_dev);
       DS_TRY(gemm_launch(ctx, m->gp_w1, 2 * L, m->t_w1));
@@ -754,51 +676,15 @@ static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
       DS_TRY(gemm_launch(ctx, m->gp_w2, L, m->t_w2));
       DS_TRY(gemm_launch(ctx, m->gp_w3, L, m->t_w3));
     } else if (gfirst > 0) {
-      for (int l = gfirst; l < L; ++l) {
-        LayerState& Sq = m->L[l];
-        DS_TRY(gemm_launch(ctx, Sq.lq + Sq.lq_nf + Sq.lq_n1 + Sq.lq_n2, Sq.lq_np, Sq.lq_tp));
-      }
+      for (int l = gfirst; l < L; ++l) DS_TRY(gemm_launch(ctx, lq_pt(m->L[l]), m->L[l].lq_np, m->L[l].lq_tp));
     } else {
       DS_TRY(gemm_launch(ctx, m->gp_pt, m->n_pt, m->t_pt));
     }
   }
   // the assembly of the layers that took part (their gradient entries; those of the layers below gfirst keep their old content)
-  const LayerDev* lay = m->layers_dev + gfirst;
-  const int La = L - gfirst;
-  if (bucketed) {
-    // last bucket: likelihood-variance gradient and the four result scalars (contiguous behind the layers' segments when `out`
-    // is grad + n_theta, as the contract of dsdgp_allreduce asks)
-    FinArgs F{m->lik_part, m->fin.nblocks, m->fin.w, m->fin.kl_weight, m->lik_const,
-              lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : (int64_t)-1, m->fin.out, L, 1};
-    AdamArgs A{};
-    DS_LAUNCH(k_tail, dim3(1), dim3(256), 0, ctx->stream, m->layers_dev, 0, 0, m->grad, F, A);
-    DS_HIP(hipGetLastError());
-    m->fin.done = true;
-    const int64_t lo = lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : m->desc.n_theta;
-    const bool tail_scalars = m->fin.out == m->grad + m->desc.n_theta;
-    m->bucket_fn(m->bucket_user, L, m->grad + lo, (m->desc.n_theta - lo) + (tail_scalars ? 4 : 0), (void*)ctx->stream);
-    if (!tail_scalars) m->bucket_fn(m->bucket_user, L + 1, m->fin.out, 4, (void*)ctx->stream);
-    return DSDGP_OK;
-  }
-  if (m->tail_ok) {
-    DS_LAUNCH(k_asm_rows, dim3(m->m_max_all, La), dim3(256), (size_t)m->mp_max_all * sizeof(double), ctx->stream, lay, m->grad,
-                       kl_weight, m->mp_max_all, m->force.asm_pre);
-    FinArgs F{m->lik_part, m->fin.nblocks, m->fin.w, m->fin.kl_weight, m->lik_const,
-              lik_has_param(m->desc.lik_kind) ? m->desc.off_lik_var : (int64_t)-1, m->fin.out, L, 1};
-    AdamArgs A{m->theta, m->adam_m, m->adam_v, m->mask, m->desc.n_theta, m->fuse_adam.lr_t, m->fuse_adam.b1, m->fuse_adam.b2,
-               m->fuse_adam.eps, (m->fuse_adam.on && gfirst == 0) ? 1 : 0};
-    const int nadam = A.on ? (int)std::min<int64_t>(2048, ceil_div(m->desc.n_theta, 512)) : 0;      // a thread per pair of entries, eight workgroups per CU
-    DS_LAUNCH(k_tail, dim3(La + 1 + nadam), dim3(256), 0, ctx->stream, m->layers_dev, gfirst, La, m->grad, F, A);
-    DS_HIP(hipGetLastError());
-    m->fin.done = true;
-    return DSDGP_OK;
-  }
-  DS_LAUNCH(k_asm_kbar, dim3(m->kuu_blocks, La), dim3(256), 0, ctx->stream, lay, kl_weight);
-  if (m->n_wz) DS_TRY(gemm_launch(ctx, m->gp_wz, m->n_wz, m->t_wz));   // (wm of the layers below gfirst is stale: their WZ is never read)
-  if (m->need_hyp_part) DS_LAUNCH(k_asm_hyp_part, dim3(NPART, La), dim3(256), 0, ctx->stream, lay);
-  DS_LAUNCH(k_asm_params, dim3(m->asm_blocks + 1, La), dim3(256), 0, ctx->stream, lay, m->grad, kl_weight);
-  DS_HIP(hipGetLastError());
-  return DSDGP_OK;
+  if (sc.bucketed) return end_last_bucket(m, ctx->stream);
+  if (m->tail_ok) return end_rows_tail(m, ctx->stream, gfirst, L - gfirst, kl_weight);
+  return end_unfused(m, ctx->stream, m->layers_dev + gfirst, L - gfirst, kl_weight);
 }
 
 // minibatch to gather before the evaluation (dsdgp_model_train_step_minibatch): rows idx[0..n) of the resident data
@@ -925,21 +811,24 @@ extern "C" int dsdgp_model_set_sample_weights(dsdgp_model* m, const double* w, i
   return DSDGP_OK;
 }
 
+// Adam's bias-corrected step size at step t
+static double adam_lr_t(double lr, double b1, double b2, int64_t t) { return lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t)); }
+// theta moved (an optimiser step, the caller's write): nothing prepared from it stands
+static void mark_theta_moved(dsdgp_model* m) { m->prepared = m->kuu_valid = false; m->q_dirty = -2; }
+
 extern "C" int dsdgp_model_adam_step(dsdgp_model* m, double lr, double beta1, double beta2, double eps, int64_t t) {
   DS_CHECK_ARG(m && m->grad && m->adam_m && m->adam_v && t >= 1);
   if (m->grad_pruned) {
     dsdgp_set_error("dsdgp_model_adam_step: the last gradient was evaluated for layers >= %d only (dsdgp_model_set_grad_first_layer)", m->grad_first);
     return DSDGP_ERR_BAD_ARG;
   }
-  const double lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  const double lr_t = adam_lr_t(lr, beta1, beta2, t);
   const int64_t n = m->desc.n_theta;
   const int nb = (int)std::min<int64_t>(2048, ceil_div(n, 512));      // a thread per pair of entries (adam_sweep), eight workgroups per CU
   DS_LAUNCH(k_adam, dim3(nb), dim3(256), 0, m->ctx->stream, m->theta, m->grad, m->adam_m, m->adam_v, m->mask, n,
                      lr_t, beta1, beta2, eps, (const LayerDev*)m->layers_dev, m->desc.L);
   DS_HIP(hipGetLastError());
-  m->prepared = false;
-  m->kuu_valid = false;
-  m->q_dirty = -2;
+  mark_theta_moved(m);
   return DSDGP_OK;
 }
 
@@ -960,13 +849,11 @@ static int train_step_impl(dsdgp_model* m, const double* X, const double* Y, int
     return dsdgp_model_adam_step(m, lr, beta1, beta2, eps, t);
   }
   m->fuse_adam.on = 1;
-  m->fuse_adam.lr_t = lr * sqrt(1.0 - pow(beta2, (double)t)) / (1.0 - pow(beta1, (double)t));
+  m->fuse_adam.lr_t = adam_lr_t(lr, beta1, beta2, t);
   m->fuse_adam.b1 = beta1; m->fuse_adam.b2 = beta2; m->fuse_adam.eps = eps;
   const int rc = elbo_impl(m, X, Y, n, S, zs, zstride, seed, data_scale, kl_weight, 1, out, gs);
   m->fuse_adam.on = 0;
   DS_TRY(rc);
-  m->prepared = false;
-  m->kuu_valid = false;
-  m->q_dirty = -2;
+  mark_theta_moved(m);
   return DSDGP_OK;
 }

@@ -1,71 +1,23 @@
-// Descriptors of the model path: the device-resident per-layer record, reduction / weight-gradient job records, host-side layer and
-// model state, and the size policies (padding, split counts, chain / GEMM path selection).  Part of the model translation unit
-// (model.hip includes it; nothing else does).
+// Descriptors of the model path: host-side layer and model state, the DSDGP_FORCE table, the size policies of the chains (Csave, d-split,
+// blocked factorisation).  LayerDev, the job records and the split counts: plan_types.hpp / model_plan.hpp.  Part of the model translation unit.
 #pragma once
-// ------------------------------------------------------------------------------------------------------
-// device-resident per-layer descriptor shared by all the small per-layer kernels
-// ------------------------------------------------------------------------------------------------------
-struct LayerDev {
-  int32_t M, Mp, D_in, D_out, DP4, DP16, DinP16, kern_kind, ard, has_white, white, hyp_parts;   // rows of hyp2part per backward: > 0 written by k_asm_kbar (folded), < 0: -NPART rows by k_asm_hyp_part
-  int32_t kl_parts, kvar_identity;   // partial sums k_kl_part leaves in klpart (the launch's block columns); dsdgp_layer_desc::kvar_identity
-  int64_t off_Z, off_q_mu, off_q_sqrt, off_kvar, off_kls, off_wvar;
-  double *Zp, *Zs, *hyp, *Tp, *TpT, *qmu, *qmu4;
-  double *Kp, *Linv, *LinvT, *Kinv, *scal;
-  double *V, *nL, *Sd, *klv;
-  double *U, *n4, *PT, *UU, *Kbar, *wm, *wk;
-  double *bigred, *thinq, *thinz, *hyp_red;
-  double* meanAB;              // (64 ti x DP16) [X;1]^T MB^T: gradient of a trainable Linear mean function (rows: D_in of A, then b)
-  int64_t off_mean_A, off_mean_b;   // -1: not a free parameter
-  double *R2, *Zp1, *WZ;       // scaled squared distances of Z (Mp x Mp); [Z | 1] and wm [Z | 1] (Mp x DinP16, D_in > 32 only)
-  double *klpart, *hyp2part;   // [NPART] KL partial sums ; [NPART][D_in + 2] Ku-side hyper-parameter partials
-  // alg_g: sum_r e_r a_r^T is assembled from the (already needed) P_d and A mbar^T instead of a split-K product over the rows:
-  //   sum_r e a^T = sum_d (2 Ku^-1 S_d - I) P_d + n (A mbar^T)^T   (e = Ku^-1 abar - g a, abar = sum_d 2 vbar_d S_d a + q_mu mbar)
-  // KS_d = Ku^-1 S_d (parameter-only, side stream), GS_d = KS_d P_d (same launch as P_d T_d).  Chosen per layer when the row
-  // count dwarfs D_out * M (2 D_out M^3 flops instead of 2 M^2 R, and the chain stops writing E).
-  double *KS, *GS;
-  int32_t alg_g, need_tpt;   // need_tpt: some chain kernel reads q_sqrt^T (Mp >= 512 row-oriented loads; the Csave backward chain)
-  double *wLbar, *wH, *wY, *wX;  // white=True: Cholesky-adjoint temporaries (Mp x Mp each)
-  // natural-gradient temporaries, (D_out x Mp x Mp) each unless noted
-  double *ngTI, *ngTinv, *ngTbar, *ngH, *ngY, *ngX, *ngSinv, *ngA, *ngLAinv, *ngLAinvT, *ngV /* D_out x Mp */, *ngTheta1 /* D_out x Mp */, *ngScal /* 2 x D_out */;
-};
 #define NPART 32
 #define PREP_BLOCKS 64      // minimum; large models take more (dsdgp_model::prep_blocks: ~2048 elements of q_sqrt per thread block pass)
 #define WIDE_DIN 32   // layers with D_in above this take the GEMM form of the Ku-side Z / lengthscale adjoints
 
-struct RedJob {
-  const double* part;
-  double* out;
-  int64_t count;
-  int32_t nsplit, blk_start;
-  int32_t wide;        // wide: few outputs, many splits -> one workgroup per output element (fixed-order tree)
-  int32_t sym_n;       // > 0: symmetric result whose tiles above the diagonal were not computed (mirrored here)
-  int32_t sym_tile;
-  int64_t pstride;     // elements between consecutive splits of `part`
-  int32_t in_ld, out_ld;   // > 0: 2-D result, `part` rows have leading dimension in_ld (the weight-gradient products run on
-                           // whole 64-row tiles: Mw = round_up(Mp, 64)), `out` rows out_ld; 0: linear
-  int32_t ways;            // 4: a workgroup owns 64 outputs, each of its four waves a quarter of the splits (many splits, few outputs:
-                           // one thread per output walked 156 splits eight at a time — 20 dependent round trips); else one thread each
-};
-
-struct LayerState {
+struct LayerState : PlanBufs {      // (operands and partial buffers of the weight-gradient plan: model_plan.hpp)
   dsdgp_layer_desc d;
   LayerDev dev;
   int64_t R_max;    // max output rows (s_max * n_max)
   int64_t ld_max;
-  int nsplit_big_max, nsplit_thin_max;
-  double *A, *C, *E, *GW, *VB, *MB, *XT1;
+  double* C;
   double *F, *mean, *var, *zbuf, *dF;
   const double *meanA, *meanb;   // Linear mean function: A (fixed device array or inside theta), bias or NULL
   int njobs;                     // weight-gradient jobs of this layer in the current plan
   int njobsA = 0, totA = 0;      // ... of which the first njobsA (tasks [0, totA)) read only the forward pass's A and the upstream adjoints
-  double* part_mean;             // split-K partials of the mean-function gradient product (only when it is trainable)
-  bool mean_grad;
   double* Xcat;     // [X_prop | F] handed to the next layer when input propagation is on (layers.py:105-110)
   int prop;
-  double *part_big, *part_thin, *hyp_part;
-  int32_t* wtick = nullptr;      // arrival counters of the in-launch split-K reduction, one per (job, tile) of this layer's products
-  int wtick_cap = 0;
-  int red_off = 0, red_n = 0, red_blk0 = 0, red_blkn = 0;   // this layer's range of the reduction job list / of its blocks
+  int red_off = 0, red_blk0 = 0;   // this layer's first entry of the reduction job list / first of its blocks (they end where the next layer's begin)
   double* bpart = nullptr;      // backward-chain d-split: partial abar tiles [row block][split][Mp * 16 + 16]
   int* bcnt = nullptr;          //   arrival counters per row block (zero between launches)
   bool big = false;    // Mp >= big_mp(), a multiple of 64: multi-workgroup blocked factorisations (linalg.hpp BigChol)
@@ -77,11 +29,8 @@ struct LayerState {
   // step on this layer alone: the other layers' S_d / U_d / ... are still those of the previous evaluation)
   GemmProblem* lq = nullptr;
   int lq_nf = 0, lq_tf = 0, lq_n1 = 0, lq_t1 = 0, lq_n2 = 0, lq_t2 = 0, lq_np = 0, lq_tp = 0;   // forward / U, n, KS / U U^T / P_d T_d, GS_d
-  // weight-gradient jobs of ONE launch per layer, rebuilt when (n, S) changes: [A | B] — the A jobs (P_d = A diag(vbar_d) A^T, A mbar^T,
-  // the mean-function product) read what the forward chain and the producer of this layer's upstream adjoints left, the B jobs
-  // (E A^T, GW [X|1]^T) the backward chain's outputs
-  WgradJob* wj;
-  int ns_big, ns_thin, tot_big, tot_thin;
+  WgradJob* wj;     // weight-gradient jobs of ONE launch per layer, rebuilt when (n, S) changes: [A | B] (plan_layer, model_plan.hpp)
+  int ns_big, tot_big;
   // z actually used by the last forward (for the backward pass)
   const double* z_used;
   int64_t zs_s, zs_n, zs_d;
@@ -171,41 +120,25 @@ struct dsdgp_model {
   struct Force { int save_c = 1, cs_min_blocks = 160, cs_min_dout = 3, cs_max_dout = 1 << 20, wg_defer = -1, alg_g = -1, bwd_split = 1, pipe_tail = 0, head = 1, tail = 1, adj_fuse = 1, ext_ev = 1, lik_fuse = 1, red_ahead = 1, white_fwd = 1, gemm_mp = 512, last_fuse = 1, last_min_blocks = 1, asm_pre = 1, overlap_min = 1 << 18, wg_red = 1, wg_group = 1; } force;
 };
 static void parse_force(dsdgp_model* m) {
+  using F = dsdgp_model::Force;
+  static const struct { const char* name; int F::*field; } keys[] = {
+      {"save_c", &F::save_c}, {"cs_min_blocks", &F::cs_min_blocks}, {"cs_min_dout", &F::cs_min_dout}, {"cs_max_dout", &F::cs_max_dout},
+      {"wg_defer", &F::wg_defer}, {"alg_g", &F::alg_g}, {"bwd_split", &F::bwd_split}, {"red_ahead", &F::red_ahead},
+      {"white_fwd", &F::white_fwd}, {"pipe_tail", &F::pipe_tail}, {"head", &F::head}, {"tail", &F::tail}, {"adj_fuse", &F::adj_fuse},
+      {"ext_ev", &F::ext_ev}, {"lik_fuse", &F::lik_fuse}, {"gemm_mp", &F::gemm_mp}, {"last_fuse", &F::last_fuse},
+      {"last_min_blocks", &F::last_min_blocks}, {"asm_pre", &F::asm_pre}, {"overlap_min", &F::overlap_min}, {"wg_red", &F::wg_red},
+      {"wg_group", &F::wg_group}};
   const char* e = getenv("DSDGP_FORCE");
   if (!e) return;
-  std::string str(e);
-  size_t pos = 0;
-  while (pos < str.size()) {
+  const std::string str(e);
+  for (size_t pos = 0; pos < str.size();) {
     size_t end = str.find(',', pos);
     if (end == std::string::npos) end = str.size();
     const std::string kv = str.substr(pos, end - pos);
     const size_t eq = kv.find('=');
-    if (eq != std::string::npos) {
-      const std::string k = kv.substr(0, eq);
-      const int v = atoi(kv.c_str() + eq + 1);
-      if (k == "save_c") m->force.save_c = v;
-      else if (k == "cs_min_blocks") m->force.cs_min_blocks = v;
-      else if (k == "cs_min_dout") m->force.cs_min_dout = v;
-      else if (k == "cs_max_dout") m->force.cs_max_dout = v;
-      else if (k == "wg_defer") m->force.wg_defer = v;
-      else if (k == "alg_g") m->force.alg_g = v;
-      else if (k == "bwd_split") m->force.bwd_split = v;
-      else if (k == "red_ahead") m->force.red_ahead = v;
-      else if (k == "white_fwd") m->force.white_fwd = v;
-      else if (k == "pipe_tail") m->force.pipe_tail = v;
-      else if (k == "head") m->force.head = v;
-      else if (k == "tail") m->force.tail = v;
-      else if (k == "adj_fuse") m->force.adj_fuse = v;
-      else if (k == "ext_ev") m->force.ext_ev = v;
-      else if (k == "lik_fuse") m->force.lik_fuse = v;
-      else if (k == "gemm_mp") m->force.gemm_mp = v;
-      else if (k == "last_fuse") m->force.last_fuse = v;
-      else if (k == "last_min_blocks") m->force.last_min_blocks = v;
-      else if (k == "asm_pre") m->force.asm_pre = v;
-      else if (k == "overlap_min") m->force.overlap_min = v;
-      else if (k == "wg_red") m->force.wg_red = v;
-      else if (k == "wg_group") m->force.wg_group = v;
-    }
+    if (eq != std::string::npos)
+      for (const auto& k : keys)      // (unknown keys are ignored)
+        if (kv.compare(0, eq, k.name) == 0) m->force.*k.field = atoi(kv.c_str() + eq + 1);
     pos = end + 1;
   }
 }
@@ -246,19 +179,4 @@ static int chain_d_split(int64_t nblk, int D_out) {
 static int big_mp(bool uniform) {
   static const int nonuniform = getenv("DSDGP_BIG_MP") ? atoi(getenv("DSDGP_BIG_MP")) : 192;      // (A/B aid)
   return uniform ? 192 : nonuniform;
-}
-// K splits of a weight-gradient launch: about `target_tasks` workgroup tasks (512 = two workgroups of four waves per CU), every
-// wave at least two 16-row chunks
-static int choose_nsplit(int tiles_per_split, int64_t nchunks, int target_tasks) {
-  int ns = target_tasks / (tiles_per_split > 0 ? tiles_per_split : 1);
-  if (ns < 1) ns = 1;
-  int64_t cap = nchunks / 8;
-  if (cap < 1) cap = 1;
-  if (ns > cap) ns = (int)cap;
-  return ns;
-}
-// 64 x 64 tiles (NI = 4 blocks of 16) on Mw = round_up(Mp, 64) rows (zero rows beyond Mp)
-static void wgrad_shapes(int Mp, int& NI, int& ti) {
-  NI = 4;
-  ti = pad_Mw(Mp) / 64;
 }
