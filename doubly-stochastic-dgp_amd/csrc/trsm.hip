@@ -6,7 +6,8 @@
 //    flops, nothing like the n^3 / 3 of a full inverse (rounds 1-2 inverted all of L with ONE workgroup and multiplied densely:
 //    2x a solve's flops and a serial 25 ms at n = 1024);
 //  * panels of <= 128 rows are solved by k_trsm_panel, ONE WAVE PER 16 RIGHT-HAND-SIDE COLUMNS: the wave walks the panel's 16-row
-//    blocks, X_i = D_i (B_i - sum_k L_ik X_k), with every X_k of its columns in registers — the D layout of one MFMA product is
+//    blocks, X_i = D_i (B_i - sum_k L_ik X_k) and one refinement step X_i += D_i (acc - L_ii X_i) (the explicit inverse alone leaves
+//    |D^-1||D| roundings of componentwise residual), with every X_k of its columns in registers — the D layout of one MFMA product is
 //    the B-operand layout of the next, so nothing goes through LDS and no wave waits for another; thousands of waves in flight at
 //    the right-hand-side counts of the layer (nrhs = S N = 20 000 at config 2);
 //  * between panels the remaining rows take B_rest -= L_rest,panel X_panel as ONE grouped MFMA GEMM launch per panel (all matrices
@@ -108,11 +109,25 @@ __global__ __launch_bounds__(256) void k_trsm_panel(const TrsmPanel P) {
       // X_i = D_i acc  (trans: D_i^T acc);  A operand [row c][k 4 s + g] = D[c][4 s + g]  or  D[4 s + g][c]
       gcptr Di = Dv + (int64_t)(b0 + i) * 256;
       d4 xi = (d4){0, 0, 0, 0};
+      double dv[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        const double dv = P.trans ? Di[(4 * s + g) * 16 + c] : Di[c * 16 + 4 * s + g];
-        xi = mfma_f64(dv, acc0[s], xi);
+        dv[s] = P.trans ? Di[(4 * s + g) * 16 + c] : Di[c * 16 + 4 * s + g];
+        xi = mfma_f64(dv[s], acc0[s], xi);
       }
+      // one refinement step against the block itself: r = acc - op(D_i) X_i, X_i += D_i^-1 r.  The product with the explicit inverse alone
+      // leaves a componentwise residual of |D^-1||D| roundings (128 units of 2^-53 measured on the factor of a 16-point 1-D grid, where
+      // substitution leaves 1.4); the step brings it to the level of a substitution.  A operand [row c][k 4 s + g] of op(D_i), its triangle only
+      d4 res = acc0;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int kk = 4 * s + g;
+        const int ra = P.trans ? rI + kk : rI + c, ca = P.trans ? rI + c : rI + kk;
+        const double a = (ca <= ra && ra < P.n) ? L[(int64_t)ra * P.ldl + ca] : 0.0;
+        res = mfma_f64(-a, xi[s], res);
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s) xi = mfma_f64(dv[s], res[s], xi);
       x[step] = xi;
       if (cok) {
 #pragma unroll

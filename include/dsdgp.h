@@ -92,8 +92,9 @@ int dsdgp_potrf(dsdgp_ctx* ctx, int batch, int n, double* A, int64_t lda, int64_
 
 /* K4 — tf.matrix_triangular_solve(L, B, lower=True) and its transposed form (layers.py:186,188):
  *   trans=0: B <- L^{-1} B ;  trans=1: B <- L^{-T} B.   L: n x n lower (only the lower triangle is read), B: n x nrhs, in place.
- * Blocked: 16 x 16 diagonal-block inverses, 128-row panels solved one wave per 16 right-hand-side columns (MFMA products chained in
- * registers), MFMA GEMM updates of the rows below / above a panel.  n^2 nrhs flops; any n, any nrhs; asynchronous. */
+ * Blocked: 16 x 16 diagonal-block inverses with one refinement step per block (componentwise backward error at the level of a
+ * substitution's), 128-row panels solved one wave per 16 right-hand-side columns (MFMA products chained in registers), MFMA GEMM
+ * updates of the rows below / above a panel.  n^2 nrhs flops; any n, any nrhs; asynchronous. */
 int dsdgp_trsm(dsdgp_ctx* ctx, int trans, int n, int64_t nrhs, const double* L, int64_t ldl, double* B, int64_t ldb);
 /* The batched form of layers.py:239, tf.matrix_triangular_solve(self.Lu_tiled, self.q_sqrt): `batch` right-hand-side matrices
  * strideB doubles apart, their L matrices strideL apart — strideL = 0: ONE L shared by the batch (the reference tiles Lu D_out
