@@ -9,7 +9,7 @@
 //   E_rij = h_r + L_ri + L_rj + sum_d t_rd (z_id - z_jd)^2,    h_r = 1/2 sum_d log(l_d^2 w_rd),  L_ri = -1/2 sum_d w_rd (mu_rd - z_id)^2,
 //   t_rd = (w_rd - l_d^-2) / 4
 // (for s >= 0 every term is <= 0: nothing overflows, a far pair underflows to +0).  k_psi_rows writes the per-row tables (w, t, h),
-// k_psi_cross the n x M table L together with psi1 (same form with w = 1 / (l^2 + s)), and k_psi2 — the hot path, n M (M + 1) / 2
+// k_psi_cross the n x M table L together with psi1 (same form with w = 1 / (l^2 + s)) — both in psi_tables.hpp — and k_psi2 — the hot path, n M (M + 1) / 2
 // exponentials — sums exp(E) over the rows.
 //
 // k_psi2.  Only the 16 x 16 tiles (I, J), I >= J, on or below the diagonal are formed.  A workgroup of four waves owns a tile and a split
@@ -23,62 +23,7 @@
 // four 16-lane groups are combined by sum_groups; a split writes its partial tile, k_psi2_reduce adds the partials in ascending split
 // order, scales by v^2 and writes the entry and its mirror image (a diagonal tile is mirrored from its lower half: psi2 is exactly
 // symmetric).  No floating-point atomics: the summation order depends on (n, M, D) alone.
-#include <math.h>
-
-#include "common.hpp"
-
-#define PS_MAX_M 2048
-#define PS_MAX_D 1024
-#define PS_T 256
-#define PS_TILE 16          // tile edge of psi2
-#define PS_KC 32            // input dimensions per chunk of the delta^2 operand (8 MFMA k-steps)
-#define PS_TARGET_WG 4096
-#define PS_MIN_ROWS 64      // fewest rows worth a split
-#define PS_SCRATCH_CAP ((size_t)8 << 30)
-
-// one thread per row: w1 = 1 / (l^2 + s), w2 = 1 / (l^2 + 2 s), t = (w2 - l^-2) / 4 (columns D .. Dq - 1 zero), h1, h2
-__global__ __launch_bounds__(PS_T) void k_psi_rows(const double* __restrict__ s, const double* __restrict__ ls2, int64_t n, int D, int Dq,
-                                                   double variance, double* __restrict__ W1, double* __restrict__ W2,
-                                                   double* __restrict__ T, double* __restrict__ H1, double* __restrict__ H2,
-                                                   double* __restrict__ psi0) {
-  const int64_t r = (int64_t)blockIdx.x * PS_T + threadIdx.x;
-  if (r == 0 && psi0) psi0[0] = (double)n * variance;
-  if (r >= n) return;
-  double h1 = 0.0, h2 = 0.0;
-  for (int d = 0; d < D; ++d) {
-    const double l2 = ls2[d], sv = s ? s[r * D + d] : 0.0;
-    const double w1 = 1.0 / (l2 + sv), w2 = 1.0 / (l2 + 2.0 * sv);
-    W1[r * D + d] = w1;
-    W2[r * D + d] = w2;
-    T[r * Dq + d] = 0.25 * (w2 - 1.0 / l2);
-    h1 += log(l2 * w1);
-    h2 += log(l2 * w2);
-  }
-  for (int d = D; d < Dq; ++d) T[r * Dq + d] = 0.0;
-  H1[r] = 0.5 * h1;
-  H2[r] = 0.5 * h2;
-}
-
-// entry (r, i): psi1 = v exp(h1_r - 1/2 sum_d w1_rd (mu_rd - z_id)^2),  L = -1/2 sum_d w2_rd (mu_rd - z_id)^2
-__global__ __launch_bounds__(PS_T) void k_psi_cross(const double* __restrict__ mu, const double* __restrict__ Z,
-                                                    const double* __restrict__ W1, const double* __restrict__ W2,
-                                                    const double* __restrict__ H1, int64_t n, int M, int D, double variance,
-                                                    double* __restrict__ psi1, int64_t ld1, double* __restrict__ Ltab) {
-  const int64_t total = n * M, stride = (int64_t)gridDim.x * PS_T;
-  for (int64_t e = (int64_t)blockIdx.x * PS_T + threadIdx.x; e < total; e += stride) {
-    const int64_t r = e / M;
-    const int i = (int)(e - r * M);
-    const double *pm = mu + r * D, *pz = Z + (int64_t)i * D, *p1 = W1 + r * D, *p2 = W2 + r * D;
-    double a1 = 0.0, a2 = 0.0;
-    for (int d = 0; d < D; ++d) {
-      const double df = pm[d] - pz[d], q = df * df;
-      a1 = fma(p1[d], q, a1);
-      a2 = fma(p2[d], q, a2);
-    }
-    if (psi1) psi1[r * ld1 + i] = variance * exp(H1[r] - 0.5 * a1);
-    if (Ltab) Ltab[e] = -0.5 * a2;
-  }
-}
+#include "psi_tables.hpp"      // the per-row tables k_psi_rows / k_psi_cross and the PS_ constants, shared with psi_grad.hip
 
 // tile t of the lower triangle -> (I, J), I >= J
 __device__ __forceinline__ void ps_tile(int t, int& I, int& J) {

@@ -151,6 +151,10 @@ _PROTOS = {
     # layers.py:415-417, 494-495: expectation(DiagonalGaussian, (RBF, InducingPoints)[, (RBF, InducingPoints)])
     "dsdgp_rbf_expectations": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    # the reverse pass tf.gradients builds through layers.py:415-417 (tests/test_collapsed.py:10, tests/test_dgp.py:150: ScipyOptimizer().minimize(m))
+    "dsdgp_rbf_expectations_grad": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
     # layers.py:426-427 (tf.transpose(tmp), AAT / sigma2, AAT + eye), :443-448 (the bound's terms), :521-524 (the predictive variance)
     "dsdgp_scale_copy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_void_p,
                                    C.c_int64]),
@@ -158,6 +162,9 @@ _PROTOS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "dsdgp_collapsed_var": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                       C.c_double, C.c_void_p]),
+    "dsdgp_collapsed_adjoints": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
     "dsdgp_model_set_grad_first_layer": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),

@@ -164,6 +164,41 @@ def kernel_expectations(kern, Z, X_mean, X_var=None, on_device=False):
     return float(psi0.cpu().numpy()[0]), psi1.cpu().numpy(), psi2.cpu().numpy()
 
 
+def kernel_expectations_grad(kern, Z, X_mean, X_var, g_psi0, g_psi1, g_psi2, on_device=False):
+    """The reverse pass of `kernel_expectations` (dsdgp_rbf_expectations_grad): given the adjoints g_psi0 (a number), g_psi1 (N, M) and
+    g_psi2 (M, M; need not be symmetric) of a scalar F — either matrix may be None: zero — the gradients of F as a dict
+    `X_mean`, `X_var` (N, D), `Z` (M, D), `variance` (a number), `lengthscales` (D entries with ARD, else one).  X_var=None is zero
+    variance; `X_var` is then the derivative at zero variance.  Arguments as for `kernel_expectations`; on_device: device tensors
+    (`variance` of shape (1,)) without waiting for them.  The same arguments give the same bits."""
+    import ctypes as C
+    from . import _lib
+    from .engine import Context, ptr
+    spec, ls = _rbf_spec(kern, "kernel_expectations_grad")
+    ctx = Context.get()
+    dev = lambda a: a.contiguous() if hasattr(a, "data_ptr") else ctx.to_device(np.asarray(a, dtype=np.float64))
+    Zd, mu = dev(Z), dev(X_mean)
+    s = None if X_var is None else dev(X_var)
+    g1 = None if g_psi1 is None else dev(g_psi1)
+    g2 = None if g_psi2 is None else dev(g_psi2)
+    if mu.dim() != 2 or Zd.dim() != 2 or mu.shape[1] != spec.input_dim or Zd.shape[1] != spec.input_dim or \
+            (s is not None and tuple(s.shape) != tuple(mu.shape)):
+        raise ValueError("kernel_expectations_grad: Z must be (M, D), X_mean and X_var (N, D), D the kernel's input_dim")
+    N, M, D = mu.shape[0], Zd.shape[0], mu.shape[1]
+    if (g1 is not None and tuple(g1.shape) != (N, M)) or (g2 is not None and tuple(g2.shape) != (M, M)):
+        raise ValueError("kernel_expectations_grad: g_psi1 must be (N, M) and g_psi2 (M, M)")
+    nls = D if spec.ard else 1
+    d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(1 + nls)
+    _lib.check(ctx.lib.dsdgp_rbf_expectations_grad(ctx.handle, C.byref(spec), ptr(Zd), M, ptr(mu), ptr(s), N, float(g_psi0), ptr(g1), M,
+                                                   ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k)))
+    out = dict(X_mean=d_mu, X_var=d_s, Z=d_Z, variance=d_k[:1], lengthscales=d_k[1:])
+    if on_device:
+        return out
+    ctx.sync()
+    out = {k: v.cpu().numpy() for k, v in out.items()}
+    out["variance"] = float(out["variance"][0])
+    return out
+
+
 class Collapsed_Layer(Layer):
     """Extra functions for a collapsed layer (layers.py:296-307): a last layer whose Gaussian posterior is at its exact optimum for
     the data it has been given, so it carries no variational parameters and no KL term of its own."""
@@ -230,6 +265,8 @@ class SGPR_Layer(Collapsed_Layer):
         Z = ctx.to_device(self.feature.Z.value)
         psi0, psi1, psi2 = kernel_expectations(self.kern, Z, mu, s, on_device=True)
         L, G, B, T = ctx.empty(M, M), ctx.empty(M, M), ctx.empty(M, M), psi2
+        psi2_kept = ctx.empty(M, M)                  # the first solve overwrites psi2; bound_gradients reads it
+        _lib.check(lib.dsdgp_scale_copy(h, 0, M, M, ptr(psi2), M, 1.0, 0.0, ptr(psi2_kept), M))
         info = C.c_int(0)
         _lib.check(lib.dsdgp_gram(h, C.byref(spec), ptr(Z), M, None, 0, float(settings.jitter), ptr(L), M))
         _lib.check(lib.dsdgp_potrf(h, 1, M, ptr(L), M, M * M, C.byref(info)))             # L = chol(Kuu)
@@ -244,7 +281,7 @@ class SGPR_Layer(Collapsed_Layer):
         _lib.check(lib.dsdgp_trsm(h, 0, M, DY, ptr(B), M, ptr(c), DY))                    # c = LB^-1 L^-1 psi1^T Y / s2
         Collapsed_Layer.set_data(self, mu, s, Yd, s2)
         object.__setattr__(self, "_factors", dict(ctx=ctx, spec=spec, ls=ls, Z=Z, L=L, LB=B, G=G, c=c, psi0=psi0, N=N, DY=DY, s2=s2,
-                                                  kdiag=float(spec.variance)))
+                                                  kdiag=float(spec.variance), psi1=psi1, psi2=psi2_kept))
 
     def _need_factors(self):
         if self._factors is None:
@@ -266,6 +303,64 @@ class SGPR_Layer(Collapsed_Layer):
 
     def build_likelihood(self):
         return self.bound_terms()[0]
+
+    def bound_gradients(self, on_device=False):
+        """The bound of build_likelihood and its gradients with respect to the CONSTRAINED values of everything it depends on, as a
+        dict: `bound`, `Z` (M, D), `variance`, `lengthscales` (the kernel's), `lik_variance` (the noise variance given to set_data),
+        `X_mean`, `X_var` (N, D; `X_var` is present — the derivative at zero variance — even when the layer was given None).
+        numpy arrays and numbers, or device tensors (the scalars of shape (1,)) without waiting for them with on_device=True.
+        Read as F(Kuu, psi0, psi1, psi2, s2) with Sigma = Kuu + psi2 / s2 = L B L^T and alpha = Sigma^-1 psi1^T Y / s2 = L^-T LB^-T c,
+        the bound has the adjoints (dsdgp_collapsed_adjoints; the inverses from the factors of set_data by dsdgp_trsm / dsdgp_gemm)
+            dF/dSigma = -1/2 D_Y Sigma^-1 - 1/2 alpha alpha^T,   g_psi0 = -1/2 D_Y / s2,   g_psi1 = Y alpha^T / s2,
+            g_psi2 = dF/dSigma / s2 + 1/2 D_Y Kuu^-1 / s2,   d_Kuu = dF/dSigma + 1/2 D_Y Kuu^-1 - 1/2 D_Y Kuu^-1 psi2 Kuu^-1 / s2,
+        and they reach the inputs, Z and the kernel through the reverse pass of the expectations (dsdgp_rbf_expectations_grad): once
+        with (g_psi0, g_psi1, g_psi2), and once more for Kuu = K(Z, Z) + jitter I, which is psi1 at X_mean = Z with zero variance —
+        g_psi1 = d_Kuu, and both of its input adjoints belong to Z (the jitter is a constant).  The same data give the same bits."""
+        import ctypes as C
+        from . import _lib
+        from .engine import ptr
+        f = self._need_factors()
+        ctx, M, DY, N, s2 = f["ctx"], self.num_inducing, f["DY"], f["N"], f["s2"]
+        lib, h, spec = ctx.lib, ctx.handle, f["spec"]
+        D = int(spec.input_dim)
+        nls = D if spec.ard else 1
+        run = lambda rc: _lib.check(rc)
+        zeros = ctx.torch.zeros(M, M, dtype=ctx.torch.float64, device=f["Z"].device)
+        Li, W, Si, Ki, tmp, KpK = (ctx.empty(M, M) for _ in range(6))
+        run(lib.dsdgp_scale_copy(h, 0, M, M, ptr(zeros), M, 1.0, 1.0, ptr(Li), M))                 # I
+        run(lib.dsdgp_trsm(h, 0, M, M, ptr(f["L"]), M, ptr(Li), M))                                # L^-1
+        run(lib.dsdgp_scale_copy(h, 0, M, M, ptr(Li), M, 1.0, 0.0, ptr(W), M))
+        run(lib.dsdgp_trsm(h, 0, M, M, ptr(f["LB"]), M, ptr(W), M))                                # LB^-1 L^-1
+        run(lib.dsdgp_gemm(h, 1, 0, M, M, M, 1.0, ptr(W), M, ptr(W), M, 0.0, ptr(Si), M))          # Sigma^-1
+        run(lib.dsdgp_gemm(h, 1, 0, M, M, M, 1.0, ptr(Li), M, ptr(Li), M, 0.0, ptr(Ki), M))        # Kuu^-1
+        run(lib.dsdgp_gemm(h, 0, 0, M, M, M, 1.0, ptr(Ki), M, ptr(f["psi2"]), M, 0.0, ptr(tmp), M))
+        run(lib.dsdgp_gemm(h, 0, 0, M, M, M, 1.0, ptr(tmp), M, ptr(Ki), M, 0.0, ptr(KpK), M))      # Kuu^-1 psi2 Kuu^-1
+        alpha = ctx.empty(M, DY)
+        run(lib.dsdgp_scale_copy(h, 0, M, DY, ptr(f["c"]), DY, 1.0, 0.0, ptr(alpha), DY))
+        run(lib.dsdgp_trsm(h, 1, M, DY, ptr(f["LB"]), M, ptr(alpha), DY))
+        run(lib.dsdgp_trsm(h, 1, M, DY, ptr(f["L"]), M, ptr(alpha), DY))                           # alpha = L^-T LB^-T c
+        g1, g2, dK, out, bound = ctx.empty(N, M), ctx.empty(M, M), ctx.empty(M, M), ctx.empty(8), ctx.empty(7)
+        run(lib.dsdgp_gemm(h, 0, 1, N, M, DY, 1.0 / s2, ptr(self._Y), DY, ptr(alpha), DY, 0.0, ptr(g1), M))      # Y alpha^T / s2
+        run(lib.dsdgp_collapsed_adjoints(h, M, N, DY, ptr(Si), ptr(Ki), ptr(KpK), ptr(f["psi2"]), ptr(alpha), ptr(f["c"]), ptr(self._Y),
+                                         ptr(f["psi0"]), s2, ptr(g2), ptr(dK), ptr(out)))
+        run(lib.dsdgp_collapsed_bound(h, M, N, DY, ptr(f["LB"]), M, ptr(f["G"]), M, ptr(f["c"]), ptr(self._Y), ptr(f["psi0"]), s2,
+                                      ptr(bound)))
+        d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(1 + nls)
+        k_mu, k_Z, k_k = ctx.empty(M, D), ctx.empty(M, D), ctx.empty(1 + nls)
+        run(lib.dsdgp_rbf_expectations_grad(h, C.byref(spec), ptr(f["Z"]), M, ptr(self._X_mean), ptr(self._X_var), N, -0.5 * DY / s2,
+                                            ptr(g1), M, ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k)))
+        run(lib.dsdgp_rbf_expectations_grad(h, C.byref(spec), ptr(f["Z"]), M, ptr(f["Z"]), None, M, 0.0, ptr(dK), M, None, 0,
+                                            ptr(k_mu), None, ptr(k_Z), ptr(k_k)))
+        d_Z = d_Z + (k_Z + k_mu)                     # element-wise sums of the two calls' results, on the context's stream
+        d_k = d_k + k_k
+        res = dict(bound=bound[:1], Z=d_Z, variance=d_k[:1], lengthscales=d_k[1:], lik_variance=out[:1], X_mean=d_mu, X_var=d_s)
+        if on_device:
+            return res
+        ctx.sync()
+        res = {k: v.cpu().numpy() for k, v in res.items()}
+        for k in ("bound", "variance", "lik_variance"):
+            res[k] = float(res[k][0])
+        return res
 
     # layers.py:483-525
     def conditional_ND(self, Xnew, full_cov=False):

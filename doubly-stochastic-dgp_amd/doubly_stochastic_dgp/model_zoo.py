@@ -2,9 +2,12 @@
 Its bound is the one of the reference's `_build_likelihood`: the last layer at its exact optimum over the WHOLE training set, the input
 noise of the last hop integrated analytically through the kernel expectations, minus the KL terms of the inner layers.  The inner
 layers run as one device Engine over `layers[:-1]` (`inner_engine()`; S = 1 on the full training set, explicit `zs` accepted); the
-last layer is the host layer loop that `DGP_Base.propagate(full_cov=True)` uses.  No reverse pass is built through the expectations:
-`train_step` and the optimisers raise NotImplementedError — train a `DGP` (Adam plus natural-gradient steps), then read the collapsed
-bound and the predictions of the exactly optimal last layer through `DGP_Collapsed.from_dgp(model)`.  There is no engine over ALL
+last layer is the host layer loop that `DGP_Base.propagate(full_cov=True)` uses.  No reverse pass is built through the inner layers'
+engine: `train_step`, `AdamOptimizer` and `NatGradOptimizer` raise NotImplementedError — train a `DGP` (Adam plus natural-gradient
+steps), then read the collapsed bound and the predictions of the exactly optimal last layer through `DGP_Collapsed.from_dgp(model)`.
+What the collapsed layer itself owns — its inducing inputs, its kernel, the noise variance — has gradients
+(`compute_log_likelihood_gradients`, the reverse pass of the kernel expectations) and is fitted by `training.ScipyOptimizer`: for a
+one-layer model that is complete sparse-GP-regression training.  There is no engine over ALL
 layers (the collapsed layer has no variational parameters to put into one), so `engine()` and the device-side scoring methods built
 on it (`evaluate`, `predict_quantiles`, `calibration`, `classification_report`) raise NotImplementedError as well: score a collapsed
 model from `predict_y` / `predict_density`."""
@@ -196,6 +199,26 @@ class DGP_Collapsed(DGP_Base):
         bound = self.layers[-1].build_likelihood()
         KL = sum(layer.KL() for layer in self.layers[:-1])
         return bound - KL
+
+    def compute_log_likelihood_gradients(self, zs=None):
+        """(bound, [(Parameter, gradient), ...], {"X_mean": ..., "X_var": ...}): the bound of `compute_log_likelihood` and its
+        gradients with respect to the constrained values of the parameters the collapsed last layer owns — its `feature.Z`,
+        `kern.variance` and `kern.lengthscales` — and of the likelihood's `variance` (SGPR_Layer.bound_gradients; each gradient has its
+        Parameter's shape).  These four are exact at any depth: the inner layers do not depend on them, and the KL terms do not either.
+        The inner layers' OWN parameters are not covered: the bound reaches them only through the mean and the variance of the last
+        layer's inputs, whose adjoints are the third result, `X_mean` and `X_var` (N, D_in) — where a reverse pass through the inner
+        layers' engine connects.  zs: as for `compute_log_likelihood`."""
+        from .gpflow_compat import split_kernel
+        self._set_data(zs=zs)
+        top = self.layers[-1]
+        g = top.bound_gradients()
+        KL = sum(layer.KL() for layer in self.layers[:-1])
+        stat, _ = split_kernel(top.kern)
+        lik = self.likelihood.likelihood
+        pairs = [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape))
+                 for p, k in ((top.feature.Z, "Z"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales"),
+                              (lik.variance, "lik_variance"))]
+        return g["bound"] - KL, pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
 
     def train_step(self, *args, **kwargs):
         raise NotImplementedError("DGP_Collapsed: no reverse pass is built through the kernel expectations — train a DGP and read "

@@ -45,3 +45,76 @@ class NatGradOptimizer:
             for l in layers:
                 eng.natgrad_step(l, self.gamma)
         eng.ctx.sync()
+
+
+class ScipyOptimizer:
+    """[UPSTREAM] gpflow.training.ScipyOptimizer mirror: `ScipyOptimizer().minimize(m)` as the reference's tests and demos fit their
+    collapsed baselines (tests/test_collapsed.py:10, tests/test_dgp.py:150).  For a `DGP_Collapsed` it MAXIMISES the bound over the trainable ones among the
+    parameters the collapsed last layer owns — `feature.Z`, `kern.variance`, `kern.lengthscales` — and the likelihood's `variance`,
+    with the gradients of `DGP_Collapsed.compute_log_likelihood_gradients` (device) and scipy.optimize.minimize on the host.  The inner
+    layers are held fixed.  The search runs in unconstrained space: a positive parameter theta = softplus(x) + 1e-6 (gpflow_compat),
+    d theta / dx = 1 - exp(-(theta - 1e-6)).  Values go back through `Parameter.assign`, so models that share layers stay coherent.
+    A factorisation that fails inside the line search (CholeskyError) is a step back, not an exception: that trial point reports an
+    objective well above the last one that succeeded, `f + 10 (|f| + 1)`, with a zero gradient.  (Not +inf: the interpolation of
+    scipy's L-BFGS-B line search turns an infinite or a huge trial value into a step of zero length and then reports convergence at
+    the point it started from; tests/test_psi_grad_reference_cpu.py shows the finite value recovering.)  A failure at the starting
+    point itself is raised: there is nothing to step back to.
+    Any other model: NotImplementedError.  `options`: further entries of scipy's options dict (`maxiter` is minimize's argument)."""
+
+    def __init__(self, method="L-BFGS-B", tol=None, options=None):
+        self.method, self.tol, self.options = method, tol, dict(options or {})
+
+    def minimize(self, model, maxiter=1000, zs=None):
+        """returns scipy's OptimizeResult (`fun` = minus the bound); zs: fixed draws for the inner layers, as compute_log_likelihood"""
+        import numpy as np
+        import scipy.optimize
+        from ._lib import CholeskyError
+        from .gpflow_compat import SOFTPLUS_LOWER, positive_backward, positive_forward, split_kernel
+        from .model_zoo import DGP_Collapsed
+        if not isinstance(model, DGP_Collapsed):
+            raise NotImplementedError(f"ScipyOptimizer fits the collapsed last layer of a DGP_Collapsed; {type(model).__name__} is "
+                                      "trained by AdamOptimizer / NatGradOptimizer")
+        top = model.layers[-1]
+        params = [top.feature.Z, split_kernel(top.kern)[0].variance, split_kernel(top.kern)[0].lengthscales,
+                  model.likelihood.likelihood.variance]
+        train = [p for p in params if p.trainable]
+        if not train:
+            raise ValueError("ScipyOptimizer: none of the collapsed layer's parameters is trainable")
+        sizes = [int(np.prod(p.shape)) for p in train]
+
+        def pack(values):
+            return np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1) for v in values])
+
+        def assign(x):
+            at = 0
+            for p, k in zip(train, sizes):
+                v = x[at:at + k].reshape(p.shape)
+                p.assign(positive_forward(v) if p.transform == "positive" else v)
+                at += k
+
+        last = [None]                                 # the last objective that succeeded
+
+        def objective(x):
+            assign(x)
+            try:
+                bound, pairs, _ = model.compute_log_likelihood_gradients(zs=zs)
+            except CholeskyError:
+                if last[0] is None:
+                    raise
+                return last[0] + 10.0 * (abs(last[0]) + 1.0), np.zeros_like(x)
+            last[0] = -float(bound)
+            grads = {id(p): g for p, g in pairs}
+            out = []
+            for p in train:
+                g = grads[id(p)]
+                if p.transform == "positive":
+                    g = g * -np.expm1(-(p.value - SOFTPLUS_LOWER))
+                out.append(-g)
+            return -float(bound), pack(out)
+
+        x0 = pack([positive_backward(p.value) if p.transform == "positive" else p.value for p in train])
+        options = dict(self.options)
+        options["maxiter"] = int(maxiter)
+        res = scipy.optimize.minimize(objective, x0, jac=True, method=self.method, tol=self.tol, options=options)
+        assign(res.x)
+        return res

@@ -540,6 +540,29 @@ int dsdgp_pca(dsdgp_ctx* ctx, const double* X, int64_t n, int32_t D, int32_t k, 
 int dsdgp_rbf_expectations(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu, const double* s,
                            int64_t n, double* psi0, double* psi1, int64_t ld1, double* psi2, int64_t ld2);
 
+/* dsdgp_rbf_expectations_grad: the reverse pass of dsdgp_rbf_expectations — what tf.gradients builds through
+ * expectation(DiagonalGaussian, (RBF, InducingPoints)[, (RBF, InducingPoints)]) (layers.py:415-417) when the reference's demos and tests
+ * fit a collapsed model with ScipyOptimizer().minimize(m) (tests/test_collapsed.py:10, tests/test_dgp.py:150).  Given the adjoints g_psi0 (a number),
+ * g_psi1 (device, n x ldg1, or NULL: zero) and g_psi2 (device, M x ldg2, or NULL: zero; need not be symmetric: (g + g^T) / 2 is what
+ * acts) of a scalar F, it OVERWRITES
+ *   d_mu, d_s (device, n x D)   dF/dmu, dF/ds   (s == NULL: the derivative at s = 0)
+ *   d_Z (device, M x D)         dF/dZ
+ *   d_kern (device)             [0] = dF/d variance, [1 ..] = dF/d lengthscales: D entries with ARD, else one
+ * every one of them optional (NULL).  kern: a plain RBF kernel with input_dim <= 32 (one chunk of the forward's operand).  The psi2
+ * part recomputes the forward's exponent from the forward's own row tables rather than store n M^2 values: a workgroup owns a tile row
+ * of 16 inducing inputs and a split of the rows and walks every tile column (n M^2 exponentials), the exponent's sum_d t_rd Delta_ijd^2
+ * and the two contractions of the weighted terms over the pairs on the fp64 MFMA pipe; every difference is formed as a difference of
+ * the inputs.  No floating-point atomics, every summation order depends on (n, M, D) alone: the same arguments give the same bits.  A
+ * row with l_d^2 + 2 s_rd < 0 gives NaN in its own rows of d_mu and d_s and in every output that sums over rows; a pair whose
+ * exponential underflows contributes +0.  Asynchronous on the context's stream; the tables (8 n (3 M + (M / 16 + 5) D + 8) bytes at
+ * most) live in the context's scratch.
+ * DSDGP_ERR_UNSUPPORTED for a kernel that is not RBF or has a White part, for input_dim > 32, or when the tables would exceed 8 GB (pass
+ * the rows in batches and add the results).  DSDGP_ERR_BAD_ARG for M outside 1..2048, n < 1, n >= 2^31, kern->input_dim outside
+ * 1..1024, ldg1 / ldg2 < M or a NULL kern / Z / mu.  A refused call launches nothing. */
+int dsdgp_rbf_expectations_grad(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu, const double* s,
+                                int64_t n, double g_psi0, const double* g_psi1, int64_t ldg1, const double* g_psi2, int64_t ldg2,
+                                double* d_mu, double* d_s, double* d_Z, double* d_kern);
+
 /* The small steps of the reference's collapsed bound and its prediction (gplvm_build_likelihood / gplvm_build_predict, psi branch,
  * layers.py:405-450, 483-525) that the primitives above lack; SGPR_Layer of the host mirror composes them with dsdgp_gram, dsdgp_potrf,
  * dsdgp_trsm and dsdgp_gemm.  All asynchronous; every sum in a fixed order.
@@ -557,6 +580,17 @@ int dsdgp_collapsed_bound(dsdgp_ctx* ctx, int32_t M, int64_t n, int32_t DY, cons
  * tmp1 = L^-1 K(Z, X*), tmp2 = LB^-1 tmp1 (M x ld, ns columns used), var (ns x DY). */
 int dsdgp_collapsed_var(dsdgp_ctx* ctx, int32_t M, int64_t ns, int32_t DY, const double* tmp1, int64_t ld1, const double* tmp2,
                         int64_t ld2, double kdiag, double* var);
+/* dsdgp_collapsed_adjoints: the adjoints of the bound of layers.py:443-448, read as F(Kuu, psi0, psi1, psi2, noise_var), that
+ * tf.gradients forms when a collapsed model is fitted (tests/test_collapsed.py:10, tests/test_dgp.py:150), from the dense M x M matrices (leading dimension
+ * M) Si = Sigma^-1 with Sigma = Kuu + psi2 / noise_var, Ki = Kuu^-1, KpK = Ki psi2 Ki, psi2, and alpha = Sigma^-1 psi1^T Y / noise_var,
+ * c (both M x DY), Y (n x DY), psi0 (device scalar).  With dS = -1/2 DY Si - 1/2 alpha alpha^T:
+ *   g_psi2 (M x M) = dS / noise_var + 1/2 DY Ki / noise_var,   d_Kuu (M x M) = dS + 1/2 DY Ki - 1/2 DY KpK / noise_var,
+ *   out (device, 8 doubles): out[0] = dF/d noise_var, out[1..6] its terms -1/2 n DY / s2, 1/2 sum Y^2 / s2^2, -sum c^2 / s2,
+ *   1/2 DY psi0 / s2^2, -1/2 DY tr(Ki psi2) / s2^2, -tr(dS psi2) / s2^2 (added in this order), out[7] = g_psi0 = -1/2 DY / s2.
+ * (g_psi1 = Y alpha^T / noise_var is one dsdgp_gemm.)  One workgroup, every sum in a fixed order; asynchronous. */
+int dsdgp_collapsed_adjoints(dsdgp_ctx* ctx, int32_t M, int64_t n, int32_t DY, const double* Si, const double* Ki, const double* KpK,
+                             const double* psi2, const double* alpha, const double* c, const double* Y, const double* psi0,
+                             double noise_var, double* g_psi2, double* d_Kuu, double* out);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
