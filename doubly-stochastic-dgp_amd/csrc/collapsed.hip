@@ -22,19 +22,6 @@ __global__ __launch_bounds__(CL_T) void k_scale_copy(int trans, int m, int n, co
   B[(int64_t)i * ldb + j] = a / div + (i == j ? diag_add : 0.0);
 }
 
-// sum over the workgroup of x, every thread receives it: thread t's value enters at leaf t of a fixed tree
-__device__ __forceinline__ double cl_block_sum(double x, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = x;
-  __syncthreads();
-  for (int h = CL_T / 2; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // one workgroup.  out[0] = the bound, out[1 .. 6] its terms (layers.py:443-448):
 //   -1/2 N D log(2 pi s2),  -D sum log diag(LB),  -1/2 sum Y^2 / s2,  1/2 sum c^2,  -1/2 D psi0 / s2,  1/2 D tr(G) / s2
 __global__ __launch_bounds__(CL_T) void k_collapsed_bound(int M, int64_t n, int DY, const double* __restrict__ LB, int64_t ldb,
@@ -50,10 +37,10 @@ __global__ __launch_bounds__(CL_T) void k_collapsed_bound(int M, int64_t n, int 
   }
   for (int e = tid; e < M * DY; e += CL_T) cc = fma(c[e], c[e], cc);
   for (int64_t e = tid; e < n * DY; e += CL_T) yy = fma(Y[e], Y[e], yy);
-  ld = cl_block_sum(ld, red);
-  tr = cl_block_sum(tr, red);
-  cc = cl_block_sum(cc, red);
-  yy = cl_block_sum(yy, red);
+  ld = block_sum<CL_T>(ld, red);
+  tr = block_sum<CL_T>(tr, red);
+  cc = block_sum<CL_T>(cc, red);
+  yy = block_sum<CL_T>(yy, red);
   if (tid != 0) return;
   const double Dy = (double)DY, ND = (double)n * Dy;
   const double t1 = -0.5 * ND * log(2.0 * M_PI * s2), t2 = -Dy * ld, t3 = -0.5 * yy / s2, t4 = 0.5 * cc;
@@ -110,10 +97,10 @@ __global__ __launch_bounds__(CL_T) void k_collapsed_adjoints(int M, int64_t n, i
   }
   for (int e = tid; e < M * DY; e += CL_T) cc = fma(c[e], c[e], cc);
   for (int64_t e = tid; e < n * DY; e += CL_T) yy = fma(Y[e], Y[e], yy);
-  tk = cl_block_sum(tk, red);
-  ts = cl_block_sum(ts, red);
-  cc = cl_block_sum(cc, red);
-  yy = cl_block_sum(yy, red);
+  tk = block_sum<CL_T>(tk, red);
+  ts = block_sum<CL_T>(ts, red);
+  cc = block_sum<CL_T>(cc, red);
+  yy = block_sum<CL_T>(yy, red);
   if (tid != 0) return;
   const double s4 = s2 * s2;
   const double t1 = -0.5 * (double)n * Dy / s2, t2 = 0.5 * yy / s4, t3 = -cc / s2, t4 = 0.5 * Dy * (psi0[0] / s4);

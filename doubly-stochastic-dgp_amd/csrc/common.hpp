@@ -200,6 +200,21 @@ __device__ __forceinline__ double sum_wave(double x) {
   return __hiloint2double(hi, lo);
 }
 
+// sum over a workgroup of T threads (a power of two) of x, every thread receives it: thread t's value enters at leaf t of a fixed tree
+// over red[T] (LDS), so the same values give the same bits.  The leading barrier lets calls follow each other on one array.
+template <int T>
+__device__ __forceinline__ double block_sum(double x, double* red) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = x;
+  __syncthreads();
+  for (int h = T / 2; h >= 1; h >>= 1) {
+    if (tid < h) red[tid] += red[tid + h];
+    __syncthreads();
+  }
+  return red[0];
+}
+
 // broadcast of lane `L` (compile-time constant) of a double through two v_readlane_b32 (far cheaper than the
 // ds_bpermute pair behind __shfl)
 template <int L>

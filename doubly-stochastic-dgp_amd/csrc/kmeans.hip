@@ -341,14 +341,9 @@ __global__ __launch_bounds__(KM_T) void k_km_update(const double* __restrict__ X
   }
   double q = 0.0;
   for (int d = tid; d < D; d += KM_T) q = fma(zrow[d], zrow[d], q);
-  red[tid] = q;
-  __syncthreads();
-  for (int h = KM_T / 2; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
+  q = block_sum<KM_T>(q, red);
   if (tid == 0) {
-    zn[m] = red[0];
+    zn[m] = q;
     ever[m] = 1;
   }
 }
@@ -373,13 +368,8 @@ __global__ __launch_bounds__(1024) void k_km_inertia(const double* __restrict__ 
   const int tid = threadIdx.x;
   double s = 0.0;
   for (int64_t r = tid; r < n; r += 1024) s += dmin[r];
-  red[tid] = s;
-  __syncthreads();
-  for (int h = 512; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  if (tid == 0) out[0] = red[0];
+  s = block_sum<1024>(s, red);
+  if (tid == 0) out[0] = s;
 }
 
 static inline int km_pow2_lanes(int D, int lo) {      // the power of two >= min(D, 64), at least lo

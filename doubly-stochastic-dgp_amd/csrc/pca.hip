@@ -299,14 +299,9 @@ __global__ __launch_bounds__(PN_T) void k_pca_norm(const double* __restrict__ A,
     const double a = A[e];
     if (sweep == 0 || i != j) s = fma(a, a, s);
   }
-  red[tid] = s;
-  __syncthreads();
-  for (int h = PN_T / 2; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
+  s = block_sum<PN_T>(s, red);
   if (tid != 0) return;
-  const double nrm = sqrt(red[0]);
+  const double nrm = sqrt(s);
   if (sweep == 0) {
     dst[0] = nrm;
     return;

@@ -9,8 +9,9 @@
 //   E_rij = h_r + L_ri + L_rj + sum_d t_rd (z_id - z_jd)^2,    h_r = 1/2 sum_d log(l_d^2 w_rd),  L_ri = -1/2 sum_d w_rd (mu_rd - z_id)^2,
 //   t_rd = (w_rd - l_d^-2) / 4
 // (for s >= 0 every term is <= 0: nothing overflows, a far pair underflows to +0).  k_psi_rows writes the per-row tables (w, t, h),
-// k_psi_cross the n x M table L together with psi1 (same form with w = 1 / (l^2 + s)) — both in psi_tables.hpp — and k_psi2 — the hot path, n M (M + 1) / 2
-// exponentials — sums exp(E) over the rows.
+// k_psi_cross the n x M table L together with psi1 (same form with w = 1 / (l^2 + s)) — both launched by psi_front, the front end this
+// call shares with its reverse pass (psi_tables.hpp) — and k_psi2 — the hot path, n M (M + 1) / 2 exponentials — sums exp(E) over the
+// rows.  The row splits and the scratch layout are psi_plan.hpp's.
 //
 // k_psi2.  Only the 16 x 16 tiles (I, J), I >= J, on or below the diagonal are formed.  A workgroup of four waves owns a tile and a split
 // of the rows; wave w owns the tile rows i = w, w + 4, w + 8, w + 12 and all 16 columns j.  sum_d t_rd delta_ijd^2 is a small-K product
@@ -23,7 +24,51 @@
 // four 16-lane groups are combined by sum_groups; a split writes its partial tile, k_psi2_reduce adds the partials in ascending split
 // order, scales by v^2 and writes the entry and its mirror image (a diagonal tile is mirrored from its lower half: psi2 is exactly
 // symmetric).  No floating-point atomics: the summation order depends on (n, M, D) alone.
-#include "psi_tables.hpp"      // the per-row tables k_psi_rows / k_psi_cross and the PS_ constants, shared with psi_grad.hip
+#include "psi_tables.hpp"      // the front end and the plan, shared with psi_grad.hip
+
+// one thread per row: w1 = 1 / (l^2 + s), w2 = 1 / (l^2 + 2 s), t = (w2 - l^-2) / 4 (columns D .. Dq - 1 zero), h1, h2
+__global__ __launch_bounds__(PS_T) void k_psi_rows(const double* __restrict__ s, const double* __restrict__ ls2, int64_t n, int D, int Dq,
+                                                   double variance, double* __restrict__ W1, double* __restrict__ W2,
+                                                   double* __restrict__ T, double* __restrict__ H1, double* __restrict__ H2,
+                                                   double* __restrict__ psi0) {
+  const int64_t r = (int64_t)blockIdx.x * PS_T + threadIdx.x;
+  if (r == 0 && psi0) psi0[0] = (double)n * variance;
+  if (r >= n) return;
+  double h1 = 0.0, h2 = 0.0;
+  for (int d = 0; d < D; ++d) {
+    const double l2 = ls2[d], sv = s ? s[r * D + d] : 0.0;
+    const double w1 = 1.0 / (l2 + sv), w2 = 1.0 / (l2 + 2.0 * sv);
+    W1[r * D + d] = w1;
+    W2[r * D + d] = w2;
+    T[r * Dq + d] = 0.25 * (w2 - 1.0 / l2);
+    h1 += log(l2 * w1);
+    h2 += log(l2 * w2);
+  }
+  for (int d = D; d < Dq; ++d) T[r * Dq + d] = 0.0;
+  H1[r] = 0.5 * h1;
+  H2[r] = 0.5 * h2;
+}
+
+// entry (r, i): psi1 = v exp(h1_r - 1/2 sum_d w1_rd (mu_rd - z_id)^2),  L = -1/2 sum_d w2_rd (mu_rd - z_id)^2
+__global__ __launch_bounds__(PS_T) void k_psi_cross(const double* __restrict__ mu, const double* __restrict__ Z,
+                                                    const double* __restrict__ W1, const double* __restrict__ W2,
+                                                    const double* __restrict__ H1, int64_t n, int M, int D, double variance,
+                                                    double* __restrict__ psi1, int64_t ld1, double* __restrict__ Ltab) {
+  const int64_t total = n * M, stride = (int64_t)gridDim.x * PS_T;
+  for (int64_t e = (int64_t)blockIdx.x * PS_T + threadIdx.x; e < total; e += stride) {
+    const int64_t r = e / M;
+    const int i = (int)(e - r * M);
+    const double *pm = mu + r * D, *pz = Z + (int64_t)i * D, *p1 = W1 + r * D, *p2 = W2 + r * D;
+    double a1 = 0.0, a2 = 0.0;
+    for (int d = 0; d < D; ++d) {
+      const double df = pm[d] - pz[d], q = df * df;
+      a1 = fma(p1[d], q, a1);
+      a2 = fma(p2[d], q, a2);
+    }
+    if (psi1) psi1[r * ld1 + i] = variance * exp(H1[r] - 0.5 * a1);
+    if (Ltab) Ltab[e] = -0.5 * a2;
+  }
+}
 
 // tile t of the lower triangle -> (I, J), I >= J
 __device__ __forceinline__ void ps_tile(int t, int& I, int& J) {
@@ -121,8 +166,9 @@ __global__ __launch_bounds__(PS_T) void k_psi2_reduce(const double* __restrict__
   psi2[(int64_t)j * ld2 + i] = v;
 }
 
-extern "C" int dsdgp_rbf_expectations(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu,
-                                      const double* s, int64_t n, double* psi0, double* psi1, int64_t ld1, double* psi2, int64_t ld2) {
+int psi_front(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu, const double* s, int64_t n,
+              bool reverse, bool want1, bool want2, bool want_dZ, const std::function<int()>& own_checks, const char* scope,
+              double* psi0, double* psi1, int64_t ld1, PsiFront& F) {
   DS_CHECK_ARG(ctx && kern && Z && mu);
   if (kern->kind != DSDGP_KERN_RBF || kern->has_white) {
     dsdgp_set_error("%s:%d: the kernel expectations have a closed form for a plain RBF kernel only (kind %d, has_white %d)", __FILE__,
@@ -132,54 +178,53 @@ extern "C" int dsdgp_rbf_expectations(dsdgp_ctx* ctx, const dsdgp_kernel* kern, 
   DS_CHECK_ARG(M >= 1 && M <= PS_MAX_M);
   DS_CHECK_ARG(n >= 1 && n <= 0x7fffffff);
   DS_CHECK_ARG(kern->input_dim >= 1 && kern->input_dim <= PS_MAX_D && kern->lengthscales);
-  DS_CHECK_ARG(!psi1 || ld1 >= M);
-  DS_CHECK_ARG(!psi2 || ld2 >= M);
-  hipStream_t st = ctx->stream;
-  const int D = kern->input_dim, Dq = (int)round_up(D, 4);
-  // the row splits: by (n, M) alone, so the bits do not depend on the device
-  const int nt1 = ceil_div(M, PS_TILE), ntiles = nt1 * (nt1 + 1) / 2;
-  int64_t want = ceil_div(PS_TARGET_WG, ntiles);
-  const int64_t most = ceil_div(n, PS_MIN_ROWS);
-  if (want > most) want = most;
-  const int64_t rows_per_split = round_up(ceil_div(n, want), 16);
-  const int nsplit = ceil_div(n, rows_per_split);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += (size_t)round_up((int64_t)bytes, 256); return at; };
-  const size_t nd = (size_t)n * D * 8;
-  const size_t o_ls = take((size_t)D * 8), o_w1 = take(nd), o_w2 = take(nd), o_t = take((size_t)n * Dq * 8), o_h1 = take((size_t)n * 8);
-  const size_t o_h2 = take((size_t)n * 8), o_l = take(psi2 ? (size_t)n * M * 8 : 0);
-  const size_t o_part = take(psi2 ? (size_t)nsplit * ntiles * PS_TILE * PS_TILE * 8 : 0);
-  if (off > PS_SCRATCH_CAP) {
+  DS_TRY(own_checks());
+  const int D = kern->input_dim, nl = reverse ? 2 : 1;
+  const PsiPlan& P = F.plan = reverse ? psi_plan_reverse(n, M, D, want1, want2, want_dZ) : psi_plan_forward(n, M, D, want2);
+  if (P.total > PS_SCRATCH_CAP) {
     dsdgp_set_error("%s:%d: the row tables of n = %lld, M = %d, D = %d need %zu bytes of scratch, above the cap of %zu: pass the rows in "
-                    "batches and add the results", __FILE__, __LINE__, (long long)n, M, D, off, PS_SCRATCH_CAP);
+                    "batches and add the results", __FILE__, __LINE__, (long long)n, M, D, P.total, PS_SCRATCH_CAP);
     return DSDGP_ERR_UNSUPPORTED;
   }
-  void* scr;
-  DS_TRY(ctx_scratch(ctx, off, &scr));
-  char* base = (char*)scr;
-  double *ls2 = (double*)(base + o_ls), *W1 = (double*)(base + o_w1), *W2 = (double*)(base + o_w2), *T = (double*)(base + o_t);
-  double *H1 = (double*)(base + o_h1), *H2 = (double*)(base + o_h2), *Ltab = psi2 ? (double*)(base + o_l) : nullptr;
-  double* part = (double*)(base + o_part);
-  std::vector<double> l2(D);
+  DS_TRY(ctx_scratch(ctx, P.total, (void**)&F.base));
+  F.ls2 = F.at(P.ls), F.W1 = F.at(P.W1), F.W2 = F.at(P.W2), F.T = F.at(P.T), F.H1 = F.at(P.H1), F.H2 = F.at(P.H2), F.Ltab = F.at(P.L);
+  if (reverse) psi1 = F.at(P.A), ld1 = M;
+  std::vector<double> l2(nl * D);
   for (int d = 0; d < D; ++d) {
     const double l = kern->lengthscales[kern->ard ? d : 0];
     l2[d] = l * l;
+    if (reverse) l2[D + d] = l;
   }
-  DS_TRY(ctx_upload(ctx, ls2, l2.data(), (size_t)D * 8));
+  DS_TRY(ctx_upload(ctx, F.ls2, l2.data(), (size_t)nl * D * 8));
   const double v = kern->variance;
-  ProfScope prof(ctx, "psi");
-  DS_LAUNCH(k_psi_rows, dim3(ceil_div(n, PS_T)), dim3(PS_T), 0, st, s, ls2, n, D, Dq, v, W1, W2, T, H1, H2, psi0);
-  if (psi1 || psi2) {
-    int64_t blocks = ((int64_t)n * M + PS_T - 1) / PS_T;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    DS_LAUNCH(k_psi_cross, dim3((unsigned)blocks), dim3(PS_T), 0, st, mu, Z, W1, W2, H1, n, (int)M, D, v, psi1, ld1, Ltab);
+  F.prof.emplace(ctx, scope);
+  DS_LAUNCH(k_psi_rows, dim3(ceil_div(n, PS_T)), dim3(PS_T), 0, ctx->stream, s, F.ls2, n, D, P.Dq, v, F.W1, F.W2, F.T, F.H1, F.H2, psi0);
+  if (want1 || want2) {
+    const int64_t blocks = std::min<int64_t>(((int64_t)n * M + PS_T - 1) / PS_T, 1 << 20);
+    DS_LAUNCH(k_psi_cross, dim3((unsigned)blocks), dim3(PS_T), 0, ctx->stream, mu, Z, F.W1, F.W2, F.H1, n, (int)M, D, v, psi1, ld1, F.Ltab);
   }
+  return DSDGP_OK;
+}
+
+extern "C" int dsdgp_rbf_expectations(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu,
+                                      const double* s, int64_t n, double* psi0, double* psi1, int64_t ld1, double* psi2, int64_t ld2) {
+  PsiFront F;
+  auto own_checks = [&]() -> int {
+    DS_CHECK_ARG(!psi1 || ld1 >= M);
+    DS_CHECK_ARG(!psi2 || ld2 >= M);
+    return DSDGP_OK;
+  };
+  DS_TRY(psi_front(ctx, kern, Z, M, mu, s, n, false, psi1, psi2, false, own_checks, "psi", psi0, psi1, ld1, F));
   if (psi2) {
+    const PsiPlan& P = F.plan;
+    const double v = kern->variance;
+    double* part = F.at(P.part);
     {
       ProfScope p2(ctx, "psi2");
-      DS_LAUNCH(k_psi2, dim3(ntiles, nsplit), dim3(PS_T), 0, st, Z, T, H2, Ltab, n, (int)M, D, Dq, rows_per_split, part);
+      DS_LAUNCH(k_psi2, dim3(P.ntiles, P.nsplit), dim3(PS_T), 0, ctx->stream, Z, F.T, F.H2, F.Ltab, n, (int)M, kern->input_dim, P.Dq,
+                P.rows_per_split, part);
     }
-    DS_LAUNCH(k_psi2_reduce, dim3(ntiles), dim3(PS_T), 0, st, part, nsplit, ntiles, (int)M, v * v, psi2, ld2);
+    DS_LAUNCH(k_psi2_reduce, dim3(P.ntiles), dim3(PS_T), 0, ctx->stream, part, P.nsplit, P.ntiles, (int)M, v * v, psi2, ld2);
   }
   DS_HIP(hipGetLastError());
   return DSDGP_OK;

@@ -2,7 +2,7 @@
 //   psi0 = n v,  psi1[r, i],  psi2[i, j] = sum_r v^2 exp(E_rij)
 // the adjoints of mu, s (n x D), Z (M x D), the kernel variance v and the lengthscales l_d.  Notation of psi.hip:
 //   l2 = l^2,  w1 = 1 / (l2 + s),  w2 = 1 / (l2 + 2 s),  t = (w2 - 1 / l2) / 4,  delta_rid = mu_rd - z_id,  Delta_ijd = z_id - z_jd,
-//   E_rij = h_r + L_ri + L_rj + sum_d t_rd Delta_ijd^2  (the forward's exponent, from the forward's own row tables, psi_tables.hpp).
+//   E_rij = h_r + L_ri + L_rj + sum_d t_rd Delta_ijd^2  (the forward's exponent, from the forward's own row tables: psi_front, psi.hip).
 // psi1 part, A_ri = g_psi1_ri psi1_ri, a1_r = sum_i A_ri;  psi2 part, Gs = (g_psi2 + g_psi2^T) / 2, Q_rij = Gs_ij v^2 exp(E_rij),
 //   q_ri = sum_j Q_rij,  a_r = sum_i q_ri,  P_rd = sum_ij Q_rij Delta_ijd^2,  S_id = sum_j Delta_ijd sum_r Q_rij t_rd:
 //   d_mu_rd = -w1 sum_i A delta - 2 w2 sum_i q delta
@@ -32,11 +32,7 @@
 // O(n M D) part of d_Z over chunks of rows (r ascending); k_psig_zsum adds the chunks, then the splits of S, in ascending order;
 // k_psig_kern (one workgroup) sums the rows' terms of d_v and d_l2 (a thread its rows in ascending order, then a fixed tree).  No
 // floating-point atomics: every summation order depends on (n, M, D) alone.
-#include "psi_tables.hpp"
-
-#define PG_MAX_D PS_KC      // one chunk of the forward's delta^2 operand
-#define PG_Z_ROWS 256       // fewest rows of a chunk of k_psig_z
-#define PG_Z_CHUNKS 256     // most chunks
+#include "psi_tables.hpp"      // psi_front: the checks, the plan (psi_plan.hpp) and the forward's row tables
 
 // Gs[i][j] = v^2 (g[i][j] + g[j][i]) / 2
 __global__ __launch_bounds__(PS_T) void k_psig_sym(const double* __restrict__ g, int64_t ldg, int M, double var2, double* __restrict__ Gs) {
@@ -265,19 +261,6 @@ __global__ __launch_bounds__(PS_T) void k_psig_zsum(const double* __restrict__ Z
   d_Z[e] = a + 4.0 * b;
 }
 
-// sum over the workgroup of x, every thread receives it: thread t's value enters at leaf t of a fixed tree
-__device__ __forceinline__ double pg_block_sum(double x, double* red) {
-  const int tid = threadIdx.x;
-  __syncthreads();
-  red[tid] = x;
-  __syncthreads();
-  for (int h = PS_T / 2; h >= 1; h >>= 1) {
-    if (tid < h) red[tid] += red[tid + h];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 // one workgroup: d_kern[0] = n g_psi0 + sum_r AV_r / v;  d_kern[1 + d] = 2 l_d sum_r C_rd (added over d, ascending, without ARD)
 __global__ __launch_bounds__(PS_T) void k_psig_kern(const double* __restrict__ Crow, const double* __restrict__ AV,
                                                     const double* __restrict__ ls, int64_t n, int D, int ard, double variance, double g0,
@@ -286,13 +269,13 @@ __global__ __launch_bounds__(PS_T) void k_psig_kern(const double* __restrict__ C
   const int tid = threadIdx.x;
   double a = 0.0;
   for (int64_t r = tid; r < n; r += PS_T) a += AV[r];
-  a = pg_block_sum(a, red);
+  a = block_sum<PS_T>(a, red);
   if (tid == 0) d_kern[0] = (double)n * g0 + a / variance;
   double tot = 0.0;
   for (int d = 0; d < D; ++d) {
     double x = 0.0;
     for (int64_t r = tid; r < n; r += PS_T) x += Crow[r * D + d];
-    x = pg_block_sum(x, red);
+    x = block_sum<PS_T>(x, red);
     const double dl = 2.0 * ls[d] * x;
     if (ard) {
       if (tid == 0) d_kern[1 + d] = dl;
@@ -306,86 +289,41 @@ __global__ __launch_bounds__(PS_T) void k_psig_kern(const double* __restrict__ C
 extern "C" int dsdgp_rbf_expectations_grad(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* mu,
                                            const double* s, int64_t n, double g_psi0, const double* g_psi1, int64_t ldg1,
                                            const double* g_psi2, int64_t ldg2, double* d_mu, double* d_s, double* d_Z, double* d_kern) {
-  DS_CHECK_ARG(ctx && kern && Z && mu);
-  if (kern->kind != DSDGP_KERN_RBF || kern->has_white) {
-    dsdgp_set_error("%s:%d: the kernel expectations have a closed form for a plain RBF kernel only (kind %d, has_white %d)", __FILE__,
-                    __LINE__, kern->kind, kern->has_white);
-    return DSDGP_ERR_UNSUPPORTED;
-  }
-  DS_CHECK_ARG(M >= 1 && M <= PS_MAX_M);
-  DS_CHECK_ARG(n >= 1 && n <= 0x7fffffff);
-  DS_CHECK_ARG(kern->input_dim >= 1 && kern->input_dim <= PS_MAX_D && kern->lengthscales);
-  DS_CHECK_ARG(!g_psi1 || ldg1 >= M);
-  DS_CHECK_ARG(!g_psi2 || ldg2 >= M);
-  if (kern->input_dim > PG_MAX_D) {
-    dsdgp_set_error("%s:%d: the reverse pass of the kernel expectations takes input_dim <= %d (one chunk of the forward's operand), "
-                    "not %d", __FILE__, __LINE__, PG_MAX_D, kern->input_dim);
-    return DSDGP_ERR_UNSUPPORTED;
-  }
+  PsiFront F;
+  auto own_checks = [&]() -> int {
+    DS_CHECK_ARG(!g_psi1 || ldg1 >= M);
+    DS_CHECK_ARG(!g_psi2 || ldg2 >= M);
+    if (kern->input_dim > PG_MAX_D) {
+      dsdgp_set_error("%s:%d: the reverse pass of the kernel expectations takes input_dim <= %d (one chunk of the forward's operand), "
+                      "not %d", __FILE__, __LINE__, PG_MAX_D, kern->input_dim);
+      return DSDGP_ERR_UNSUPPORTED;
+    }
+    return DSDGP_OK;
+  };
+  DS_TRY(psi_front(ctx, kern, Z, M, mu, s, n, true, g_psi1, g_psi2, d_Z, own_checks, "psi_grad", nullptr, nullptr, 0, F));
   hipStream_t st = ctx->stream;
-  const int D = kern->input_dim, Dq = (int)round_up(D, 4);
-  // the row splits of the hot kernel and the row chunks of d_Z: by (n, M) alone, so the bits do not depend on the device
-  const int nt1 = ceil_div(M, PS_TILE);
-  int64_t want = ceil_div(PS_TARGET_WG, nt1);
-  const int64_t most = ceil_div(n, PS_MIN_ROWS);
-  if (want > most) want = most;
-  const int64_t rows_per_split = round_up(ceil_div(n, want), 16);
-  const int nsplit = ceil_div(n, rows_per_split);
-  int64_t zwant = ceil_div(n, PG_Z_ROWS);
-  if (zwant > PG_Z_CHUNKS) zwant = PG_Z_CHUNKS;
-  const int64_t rows_per_chunk = ceil_div(n, zwant);
-  const int nchunk = ceil_div(n, rows_per_chunk);
-  const bool rows_out = d_mu || d_s || d_kern;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t at = off; off += (size_t)round_up((int64_t)bytes, 256); return at; };
-  const size_t nd = (size_t)n * D * 8, nm = (size_t)n * M * 8;
-  const size_t o_ls = take((size_t)2 * D * 8), o_w1 = take(nd), o_w2 = take(nd), o_t = take((size_t)n * Dq * 8), o_h1 = take((size_t)n * 8);
-  const size_t o_h2 = take((size_t)n * 8), o_l = take(g_psi2 ? nm : 0), o_a = take(g_psi1 ? nm : 0), o_q = take(g_psi2 ? nm : 0);
-  const size_t o_gs = take(g_psi2 ? (size_t)M * M * 8 : 0), o_pp = take(g_psi2 ? (size_t)nt1 * nd : 0);
-  const size_t o_sp = take(g_psi2 && d_Z ? (size_t)nsplit * M * D * 8 : 0), o_zp = take(d_Z ? (size_t)nchunk * M * D * 8 : 0);
-  const size_t o_c = take(nd), o_av = take((size_t)n * 8);
-  if (off > PS_SCRATCH_CAP) {
-    dsdgp_set_error("%s:%d: the row tables of n = %lld, M = %d, D = %d need %zu bytes of scratch, above the cap of %zu: pass the rows in "
-                    "batches and add the results", __FILE__, __LINE__, (long long)n, M, D, off, PS_SCRATCH_CAP);
-    return DSDGP_ERR_UNSUPPORTED;
-  }
-  void* scr;
-  DS_TRY(ctx_scratch(ctx, off, &scr));
-  char* base = (char*)scr;
-  auto at = [&](size_t o) { return (double*)(base + o); };
-  double *ls2 = at(o_ls), *ls = ls2 + D, *W1 = at(o_w1), *W2 = at(o_w2), *T = at(o_t), *H1 = at(o_h1), *H2 = at(o_h2);
-  double *Ltab = g_psi2 ? at(o_l) : nullptr, *A = g_psi1 ? at(o_a) : nullptr, *qv = g_psi2 ? at(o_q) : nullptr, *Gs = at(o_gs);
-  double *Ppart = at(o_pp), *Spart = g_psi2 && d_Z ? at(o_sp) : nullptr, *Zpart = at(o_zp), *Crow = at(o_c), *AV = at(o_av);
-  std::vector<double> l2(2 * D);
-  for (int d = 0; d < D; ++d) {
-    const double l = kern->lengthscales[kern->ard ? d : 0];
-    l2[d] = l * l;
-    l2[D + d] = l;
-  }
-  DS_TRY(ctx_upload(ctx, ls2, l2.data(), (size_t)2 * D * 8));
+  const PsiPlan& P = F.plan;
+  const int D = kern->input_dim, nt1 = P.nt1;
   const double v = kern->variance;
-  ProfScope prof(ctx, "psi_grad");
-  DS_LAUNCH(k_psi_rows, dim3(ceil_div(n, PS_T)), dim3(PS_T), 0, st, s, ls2, n, D, Dq, v, W1, W2, T, H1, H2, (double*)nullptr);
-  if (g_psi1 || g_psi2) {
-    int64_t blocks = ((int64_t)n * M + PS_T - 1) / PS_T;
-    if (blocks > (1 << 20)) blocks = 1 << 20;
-    DS_LAUNCH(k_psi_cross, dim3((unsigned)blocks), dim3(PS_T), 0, st, mu, Z, W1, W2, H1, n, (int)M, D, v, A, (int64_t)M, Ltab);
-  }
+  double *ls = F.ls2 + D, *A = F.at(P.A), *qv = F.at(P.q), *Gs = F.at(P.Gs), *Ppart = F.at(P.Ppart), *Spart = F.at(P.Spart);
+  double *Zpart = F.at(P.Zpart), *Crow = F.at(P.Crow), *AV = F.at(P.AV);
   if (g_psi2) {
     DS_LAUNCH(k_psig_sym, dim3(ceil_div(M * M, PS_T)), dim3(PS_T), 0, st, g_psi2, ldg2, (int)M, v * v, Gs);
     ProfScope p2(ctx, "psi2_grad");
     if (D <= 16)
-      DS_LAUNCH(k_psi2_grad<1>, dim3(nt1, nsplit), dim3(PS_T), 0, st, Z, T, H2, Ltab, Gs, n, (int)M, D, Dq, rows_per_split, qv, Ppart, Spart);
+      DS_LAUNCH(k_psi2_grad<1>, dim3(nt1, P.g_nsplit), dim3(PS_T), 0, st, Z, F.T, F.H2, F.Ltab, Gs, n, (int)M, D, P.Dq, P.g_rows_per_split, qv,
+                Ppart, Spart);
     else
-      DS_LAUNCH(k_psi2_grad<2>, dim3(nt1, nsplit), dim3(PS_T), 0, st, Z, T, H2, Ltab, Gs, n, (int)M, D, Dq, rows_per_split, qv, Ppart, Spart);
+      DS_LAUNCH(k_psi2_grad<2>, dim3(nt1, P.g_nsplit), dim3(PS_T), 0, st, Z, F.T, F.H2, F.Ltab, Gs, n, (int)M, D, P.Dq, P.g_rows_per_split, qv,
+                Ppart, Spart);
   }
-  if (rows_out)
-    DS_LAUNCH(k_psig_row, dim3(ceil_div(n * D, PS_T)), dim3(PS_T), 0, st, mu, Z, W1, W2, ls2, A, g_psi1, ldg1, qv, Ppart, nt1, n, (int)M, D,
+  if (d_mu || d_s || d_kern)
+    DS_LAUNCH(k_psig_row, dim3(ceil_div(n * D, PS_T)), dim3(PS_T), 0, st, mu, Z, F.W1, F.W2, F.ls2, A, g_psi1, ldg1, qv, Ppart, nt1, n, (int)M, D,
               d_mu, d_s, Crow, AV);
   if (d_Z) {
-    DS_LAUNCH(k_psig_z, dim3(ceil_div(M * D, PS_T), nchunk), dim3(PS_T), 0, st, mu, Z, W1, W2, A, g_psi1, ldg1, qv, n, (int)M, D,
-              rows_per_chunk, Zpart);
-    DS_LAUNCH(k_psig_zsum, dim3(ceil_div(M * D, PS_T)), dim3(PS_T), 0, st, Zpart, nchunk, Spart, nsplit, (int)M, D, d_Z);
+    DS_LAUNCH(k_psig_z, dim3(ceil_div(M * D, PS_T), P.nchunk), dim3(PS_T), 0, st, mu, Z, F.W1, F.W2, A, g_psi1, ldg1, qv, n, (int)M, D,
+              P.rows_per_chunk, Zpart);
+    DS_LAUNCH(k_psig_zsum, dim3(ceil_div(M * D, PS_T)), dim3(PS_T), 0, st, Zpart, P.nchunk, Spart, P.g_nsplit, (int)M, D, d_Z);
   }
   if (d_kern) DS_LAUNCH(k_psig_kern, dim3(1), dim3(PS_T), 0, st, Crow, AV, ls, n, D, kern->ard ? 1 : 0, v, g_psi0, d_kern);
   DS_HIP(hipGetLastError());

@@ -59,6 +59,67 @@ class Context:
             else np.ascontiguousarray(arr, dtype=np.float64)
         return self.torch.as_tensor(a).to(f"cuda:{self.device}")
 
+    def as_device(self, a):
+        """a as a contiguous float64 tensor on the device: a tensor is converted only where it has to be, anything else is uploaded"""
+        return a.to(device=f"cuda:{self.device}", dtype=self.torch.float64).contiguous() if hasattr(a, "data_ptr") else self.to_device(a)
+
+    # The dense primitives the collapsed layer composes, on tensors: every m, n, k comes from a .shape, every leading dimension from a
+    # .stride(0), and an operand of the wrong dtype, device, layout or shape is a ValueError before the call, not an access out of bounds
+    def _p(self, what, t, shape, packed=False):
+        """(pointer, leading dimension) of the float64 tensor t on this device.  shape: what t's must be (None: any); its rows have unit
+        stride; packed: no padding between them either (the library takes no leading dimension for this operand)"""
+        ok = hasattr(t, "data_ptr") and t.dtype == self.torch.float64 and t.is_cuda and t.device.index == self.device
+        ok = ok and t.dim() == len(shape) and t.numel() > 0 and all(w is None or w == h for w, h in zip(shape, t.shape))
+        ok = ok and (t.is_contiguous() if packed or t.dim() == 1 else (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1])
+        if not ok:
+            raise ValueError(f"{what}: expected a float64 tensor of shape {shape} on cuda:{self.device}, rows of unit stride"
+                             f"{' and packed' if packed else ''}; got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        return C.c_void_p(t.data_ptr()), t.stride(0)
+
+    def gram(self, spec, X, X2, jitter, out):                # out = K(X, X2); X2 None: K(X, X) + jitter I
+        m, n2, D = X.shape[0], 0 if X2 is None else X2.shape[0], spec.input_dim
+        x2 = None if X2 is None else self._p("gram: X2", X2, (n2, D), True)[0]
+        _lib.check(self.lib.dsdgp_gram(self.handle, C.byref(spec), self._p("gram: X", X, (m, D), True)[0], m, x2, n2, jitter,
+                                       *self._p("gram: out", out, (m, n2 or m))))
+
+    def potrf(self, A):                                      # A <- its lower Cholesky factor; CholeskyError if A is not positive definite
+        (a, lda), n = self._p("potrf: A", A, (A.shape[0], A.shape[0])), A.shape[0]
+        _lib.check(self.lib.dsdgp_potrf(self.handle, 1, n, a, lda, lda * n, C.byref(C.c_int(0))))
+
+    def trsm(self, L, B, trans=0):                           # B <- L^-1 B, with trans L^-T B; L lower triangular
+        m, n = B.shape
+        _lib.check(self.lib.dsdgp_trsm(self.handle, trans, m, n, *self._p("trsm: L", L, (m, m)), *self._p("trsm: B", B, (m, n))))
+
+    def gemm(self, ta, tb, alpha, A, B, beta, out):          # out <- alpha op(A) op(B) + beta out, op the transpose with ta / tb
+        (m, n), k = out.shape, A.shape[0 if ta else 1]
+        _lib.check(self.lib.dsdgp_gemm(self.handle, ta, tb, m, n, k, alpha, *self._p("gemm: A", A, (k, m) if ta else (m, k)),
+                                       *self._p("gemm: B", B, (n, k) if tb else (k, n)), beta, *self._p("gemm: out", out, (m, n))))
+
+    def scale_copy(self, A, B, trans=0, div=1.0, diag_add=0.0):      # B <- op(A) / div + diag_add I
+        m, n = B.shape
+        _lib.check(self.lib.dsdgp_scale_copy(self.handle, trans, m, n, *self._p("scale_copy: A", A, (n, m) if trans else (m, n)), div,
+                                             diag_add, *self._p("scale_copy: B", B, (m, n))))
+
+    def collapsed_bound(self, LB, G, c, Y, psi0, s2, out):   # out (7): the bound and its six terms
+        M, (n, DY), p = LB.shape[0], Y.shape, lambda k, t, shape: self._p("collapsed_bound: " + k, t, shape, True)[0]
+        _lib.check(self.lib.dsdgp_collapsed_bound(self.handle, M, n, DY, *self._p("collapsed_bound: LB", LB, (M, M)),
+                                                  *self._p("collapsed_bound: G", G, (M, M)), p("c", c, (M, DY)), p("Y", Y, (n, DY)),
+                                                  p("psi0", psi0, (1,)), s2, p("out", out, (7,))))
+
+    def collapsed_var(self, tmp1, tmp2, kdiag, var):         # var (ns, DY) from tmp1 = L^-1 K(Z, X*) and tmp2 = LB^-1 tmp1, both (M, ns)
+        (M, ns), DY = tmp1.shape, var.shape[1]
+        _lib.check(self.lib.dsdgp_collapsed_var(self.handle, M, ns, DY, *self._p("collapsed_var: tmp1", tmp1, (M, ns)),
+                                                *self._p("collapsed_var: tmp2", tmp2, (M, ns)), kdiag,
+                                                self._p("collapsed_var: var", var, (ns, DY), True)[0]))
+
+    def collapsed_adjoints(self, Si, Ki, KpK, psi2, alpha, c, Y, psi0, s2, g_psi2, d_Kuu, out):      # g_psi2, d_Kuu (M, M), out (8)
+        M, (n, DY), p = Si.shape[0], Y.shape, lambda k, t, shape: self._p("collapsed_adjoints: " + k, t, shape, True)[0]
+        MM, MD = (M, M), (M, DY)
+        _lib.check(self.lib.dsdgp_collapsed_adjoints(self.handle, M, n, DY, p("Si", Si, MM), p("Ki", Ki, MM), p("KpK", KpK, MM),
+                                                     p("psi2", psi2, MM), p("alpha", alpha, MD), p("c", c, MD), p("Y", Y, (n, DY)),
+                                                     p("psi0", psi0, (1,)), s2, p("g_psi2", g_psi2, MM), p("d_Kuu", d_Kuu, MM),
+                                                     p("out", out, (8,))))
+
     def prof_enable(self, on=True):
         _lib.check(self.lib.dsdgp_prof_enable(self.handle, int(on)))
 

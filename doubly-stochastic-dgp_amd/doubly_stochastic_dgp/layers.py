@@ -2,10 +2,13 @@
 attributes (`q_mu`, `q_sqrt`, `feature.Z`, `kern`, `mean_function`, `num_outputs`, `white`) and methods
 (`conditional_ND`, `conditional_SND`, `sample_from_conditional`, `KL`), and of the collapsed layers `Collapsed_Layer`, `SGPR_Layer`
 (layers.py:296-307, 345-367, 371-525).  All arithmetic runs in libdsdgp (HIP)."""
+import ctypes as C
+
 import numpy as np
 
-from . import settings
-from .gpflow_compat import InducingPoints, Parameter, Parameterized, split_kernel
+from . import _lib, settings
+from .engine import Context, Engine, ptr
+from .gpflow_compat import Gaussian, InducingPoints, Parameter, Parameterized, split_kernel
 from .utils import reparameterize
 
 
@@ -100,8 +103,6 @@ class SVGP_Layer(Layer):
         if self._model_engine is not None:
             return self._model_engine[0]
         if self._standalone_engine is None:
-            from .engine import Engine
-            from .gpflow_compat import Gaussian
             object.__setattr__(self, "_standalone_engine", Engine([self], Gaussian(), self.white))
         return self._standalone_engine
 
@@ -126,7 +127,6 @@ class SVGP_Layer(Layer):
 
 def _rbf_spec(kern, what):
     """(KernelSpec, its lengthscale array — keep it alive) of a plain RBF kernel; NotImplementedError, saying why, for any other"""
-    from . import _lib
     stat, white = split_kernel(kern)
     if stat.kind != "rbf" or white is not None:
         raise NotImplementedError(f"{what}: the expectations of the kernel under a Gaussian input have a closed form here for a "
@@ -137,23 +137,30 @@ def _rbf_spec(kern, what):
     return spec, ls
 
 
+def _expectation_inputs(what, kern, Z, X_mean, X_var):
+    """(context, KernelSpec, its lengthscale array, Z, X_mean, X_var) of kernel_expectations[_grad]: float64 device tensors, shapes checked"""
+    spec, ls = _rbf_spec(kern, what)
+    ctx = Context.get()
+    Zd, mu, s = ctx.as_device(Z), ctx.as_device(X_mean), None if X_var is None else ctx.as_device(X_var)
+    if mu.dim() != 2 or Zd.dim() != 2 or mu.shape[1] != spec.input_dim or Zd.shape[1] != spec.input_dim or \
+            (s is not None and tuple(s.shape) != tuple(mu.shape)):
+        raise ValueError(f"{what}: Z must be (M, D), X_mean and X_var (N, D), D the kernel's input_dim")
+    return ctx, spec, ls, Zd, mu, s
+
+
+def _to_host(ctx, res, scalars):
+    """the dict of device tensors res, once the device is done: numpy arrays, and numbers under the keys in scalars"""
+    ctx.sync()
+    return {k: float(v.cpu().numpy()[0]) if k in scalars else v.cpu().numpy() for k, v in res.items()}
+
+
 def kernel_expectations(kern, Z, X_mean, X_var=None, on_device=False):
     """The expectations of an RBF kernel under the diagonal Gaussians N(X_mean[n], diag(X_var[n])) — GPflow 1.1.1's
     expectation(DiagonalGaussian, kern), expectation(DiagonalGaussian, (kern, Z)) and the sum over rows of
     expectation(DiagonalGaussian, (kern, Z), (kern, Z)) as layers.py:415-417 uses them — on the device (dsdgp_rbf_expectations):
     (psi0 scalar, psi1 (N, M), psi2 (M, M)).  Z (M, D), X_mean, X_var (N, D): numpy arrays or device tensors; X_var=None is zero
     variance.  on_device: return device tensors (psi0 of shape (1,)) without waiting for them.  The same arguments give the same bits."""
-    import ctypes as C
-    from . import _lib
-    from .engine import Context, ptr
-    spec, ls = _rbf_spec(kern, "kernel_expectations")
-    ctx = Context.get()
-    dev = lambda a: a.contiguous() if hasattr(a, "data_ptr") else ctx.to_device(np.asarray(a, dtype=np.float64))
-    Zd, mu = dev(Z), dev(X_mean)
-    s = None if X_var is None else dev(X_var)
-    if mu.dim() != 2 or Zd.dim() != 2 or mu.shape[1] != spec.input_dim or Zd.shape[1] != spec.input_dim or \
-            (s is not None and tuple(s.shape) != tuple(mu.shape)):
-        raise ValueError("kernel_expectations: Z must be (M, D), X_mean and X_var (N, D), D the kernel's input_dim")
+    ctx, spec, ls, Zd, mu, s = _expectation_inputs("kernel_expectations", kern, Z, X_mean, X_var)
     N, M = mu.shape[0], Zd.shape[0]
     psi0, psi1, psi2 = ctx.empty(1), ctx.empty(N, M), ctx.empty(M, M)
     _lib.check(ctx.lib.dsdgp_rbf_expectations(ctx.handle, C.byref(spec), ptr(Zd), M, ptr(mu), ptr(s), N, ptr(psi0), ptr(psi1), M,
@@ -170,19 +177,9 @@ def kernel_expectations_grad(kern, Z, X_mean, X_var, g_psi0, g_psi1, g_psi2, on_
     `X_mean`, `X_var` (N, D), `Z` (M, D), `variance` (a number), `lengthscales` (D entries with ARD, else one).  X_var=None is zero
     variance; `X_var` is then the derivative at zero variance.  Arguments as for `kernel_expectations`; on_device: device tensors
     (`variance` of shape (1,)) without waiting for them.  The same arguments give the same bits."""
-    import ctypes as C
-    from . import _lib
-    from .engine import Context, ptr
-    spec, ls = _rbf_spec(kern, "kernel_expectations_grad")
-    ctx = Context.get()
-    dev = lambda a: a.contiguous() if hasattr(a, "data_ptr") else ctx.to_device(np.asarray(a, dtype=np.float64))
-    Zd, mu = dev(Z), dev(X_mean)
-    s = None if X_var is None else dev(X_var)
-    g1 = None if g_psi1 is None else dev(g_psi1)
-    g2 = None if g_psi2 is None else dev(g_psi2)
-    if mu.dim() != 2 or Zd.dim() != 2 or mu.shape[1] != spec.input_dim or Zd.shape[1] != spec.input_dim or \
-            (s is not None and tuple(s.shape) != tuple(mu.shape)):
-        raise ValueError("kernel_expectations_grad: Z must be (M, D), X_mean and X_var (N, D), D the kernel's input_dim")
+    ctx, spec, ls, Zd, mu, s = _expectation_inputs("kernel_expectations_grad", kern, Z, X_mean, X_var)
+    g1 = None if g_psi1 is None else ctx.as_device(g_psi1)
+    g2 = None if g_psi2 is None else ctx.as_device(g_psi2)
     N, M, D = mu.shape[0], Zd.shape[0], mu.shape[1]
     if (g1 is not None and tuple(g1.shape) != (N, M)) or (g2 is not None and tuple(g2.shape) != (M, M)):
         raise ValueError("kernel_expectations_grad: g_psi1 must be (N, M) and g_psi2 (M, M)")
@@ -191,12 +188,7 @@ def kernel_expectations_grad(kern, Z, X_mean, X_var, g_psi0, g_psi1, g_psi2, on_
     _lib.check(ctx.lib.dsdgp_rbf_expectations_grad(ctx.handle, C.byref(spec), ptr(Zd), M, ptr(mu), ptr(s), N, float(g_psi0), ptr(g1), M,
                                                    ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k)))
     out = dict(X_mean=d_mu, X_var=d_s, Z=d_Z, variance=d_k[:1], lengthscales=d_k[1:])
-    if on_device:
-        return out
-    ctx.sync()
-    out = {k: v.cpu().numpy() for k, v in out.items()}
-    out["variance"] = float(out["variance"][0])
-    return out
+    return out if on_device else _to_host(ctx, out, ("variance",))
 
 
 class Collapsed_Layer(Layer):
@@ -247,15 +239,10 @@ class SGPR_Layer(Collapsed_Layer):
     def set_data(self, X_mean, X_var, Y, lik_variance):
         """X_mean, X_var (N, D_in) — numpy or device tensors, X_var may be None — Y (N, D_Y) and the noise variance.  Runs the
         expectations and both factorisations; CholeskyError if Kuu or AAT + I is not positive definite (the layer then holds no data)."""
-        import ctypes as C
         object.__setattr__(self, "_factors", None)
-        from . import _lib
-        from .engine import Context, ptr
         ctx = Context.get()
-        lib, h = ctx.lib, ctx.handle
-        dev = lambda a: a.contiguous() if hasattr(a, "data_ptr") else ctx.to_device(np.asarray(a, dtype=np.float64))
-        mu, Yd = dev(X_mean), dev(Y)
-        s = None if X_var is None else dev(X_var)
+        mu, Yd = ctx.as_device(X_mean), ctx.as_device(Y)
+        s = None if X_var is None else ctx.as_device(X_var)
         N, D = mu.shape
         M, DY = self.num_inducing, Yd.shape[1]
         if Yd.shape[0] != N or (s is not None and tuple(s.shape) != (N, D)) or D != self.feature.Z.shape[1]:
@@ -266,19 +253,18 @@ class SGPR_Layer(Collapsed_Layer):
         psi0, psi1, psi2 = kernel_expectations(self.kern, Z, mu, s, on_device=True)
         L, G, B, T = ctx.empty(M, M), ctx.empty(M, M), ctx.empty(M, M), psi2
         psi2_kept = ctx.empty(M, M)                  # the first solve overwrites psi2; bound_gradients reads it
-        _lib.check(lib.dsdgp_scale_copy(h, 0, M, M, ptr(psi2), M, 1.0, 0.0, ptr(psi2_kept), M))
-        info = C.c_int(0)
-        _lib.check(lib.dsdgp_gram(h, C.byref(spec), ptr(Z), M, None, 0, float(settings.jitter), ptr(L), M))
-        _lib.check(lib.dsdgp_potrf(h, 1, M, ptr(L), M, M * M, C.byref(info)))             # L = chol(Kuu)
-        _lib.check(lib.dsdgp_trsm(h, 0, M, M, ptr(L), M, ptr(T), M))                      # tmp = L^-1 psi2
-        _lib.check(lib.dsdgp_scale_copy(h, 1, M, M, ptr(T), M, 1.0, 0.0, ptr(G), M))      # tmp^T
-        _lib.check(lib.dsdgp_trsm(h, 0, M, M, ptr(L), M, ptr(G), M))                      # G = L^-1 psi2 L^-T = s2 AAT
-        _lib.check(lib.dsdgp_scale_copy(h, 0, M, M, ptr(G), M, s2, 1.0, ptr(B), M))       # B = AAT + I
-        _lib.check(lib.dsdgp_potrf(h, 1, M, ptr(B), M, M * M, C.byref(info)))             # LB = chol(B)
+        ctx.scale_copy(psi2, psi2_kept)
+        ctx.gram(spec, Z, None, settings.jitter, L)
+        ctx.potrf(L)                                 # L = chol(Kuu)
+        ctx.trsm(L, T)                               # tmp = L^-1 psi2
+        ctx.scale_copy(T, G, trans=1)                # tmp^T
+        ctx.trsm(L, G)                               # G = L^-1 psi2 L^-T = s2 AAT
+        ctx.scale_copy(G, B, div=s2, diag_add=1.0)   # B = AAT + I
+        ctx.potrf(B)                                 # LB = chol(B)
         c = ctx.empty(M, DY)
-        _lib.check(lib.dsdgp_gemm(h, 1, 0, M, DY, N, 1.0 / s2, ptr(psi1), M, ptr(Yd), DY, 0.0, ptr(c), DY))    # psi1^T Y / s2
-        _lib.check(lib.dsdgp_trsm(h, 0, M, DY, ptr(L), M, ptr(c), DY))
-        _lib.check(lib.dsdgp_trsm(h, 0, M, DY, ptr(B), M, ptr(c), DY))                    # c = LB^-1 L^-1 psi1^T Y / s2
+        ctx.gemm(1, 0, 1.0 / s2, psi1, Yd, 0.0, c)   # psi1^T Y / s2
+        ctx.trsm(L, c)
+        ctx.trsm(B, c)                               # c = LB^-1 L^-1 psi1^T Y / s2
         Collapsed_Layer.set_data(self, mu, s, Yd, s2)
         object.__setattr__(self, "_factors", dict(ctx=ctx, spec=spec, ls=ls, Z=Z, L=L, LB=B, G=G, c=c, psi0=psi0, N=N, DY=DY, s2=s2,
                                                   kdiag=float(spec.variance), psi1=psi1, psi2=psi2_kept))
@@ -290,13 +276,10 @@ class SGPR_Layer(Collapsed_Layer):
 
     def bound_terms(self):
         """(bound, its six terms) of layers.py:443-448 as the device assembled them."""
-        from . import _lib
-        from .engine import ptr
         f = self._need_factors()
-        ctx, M = f["ctx"], self.num_inducing
+        ctx = f["ctx"]
         out = ctx.empty(7)
-        _lib.check(ctx.lib.dsdgp_collapsed_bound(ctx.handle, M, f["N"], f["DY"], ptr(f["LB"]), M, ptr(f["G"]), M, ptr(f["c"]),
-                                                 ptr(self._Y), ptr(f["psi0"]), f["s2"], ptr(out)))
+        ctx.collapsed_bound(f["LB"], f["G"], f["c"], self._Y, f["psi0"], f["s2"], out)
         ctx.sync()
         o = out.cpu().numpy()
         return float(o[0]), o[1:].copy()
@@ -316,76 +299,60 @@ class SGPR_Layer(Collapsed_Layer):
         and they reach the inputs, Z and the kernel through the reverse pass of the expectations (dsdgp_rbf_expectations_grad): once
         with (g_psi0, g_psi1, g_psi2), and once more for Kuu = K(Z, Z) + jitter I, which is psi1 at X_mean = Z with zero variance —
         g_psi1 = d_Kuu, and both of its input adjoints belong to Z (the jitter is a constant).  The same data give the same bits."""
-        import ctypes as C
-        from . import _lib
-        from .engine import ptr
         f = self._need_factors()
         ctx, M, DY, N, s2 = f["ctx"], self.num_inducing, f["DY"], f["N"], f["s2"]
-        lib, h, spec = ctx.lib, ctx.handle, f["spec"]
+        Z, L, LB, c, psi0, psi2, Y = f["Z"], f["L"], f["LB"], f["c"], f["psi0"], f["psi2"], self._Y
+        zeros = ctx.torch.zeros(M, M, dtype=ctx.torch.float64, device=Z.device)
+        Li, W, Si, Ki, tmp, KpK = (ctx.empty(M, M) for _ in range(6))
+        ctx.scale_copy(zeros, Li, diag_add=1.0)      # I
+        ctx.trsm(L, Li)                              # L^-1
+        ctx.scale_copy(Li, W)
+        ctx.trsm(LB, W)                              # LB^-1 L^-1
+        ctx.gemm(1, 0, 1.0, W, W, 0.0, Si)           # Sigma^-1
+        ctx.gemm(1, 0, 1.0, Li, Li, 0.0, Ki)         # Kuu^-1
+        ctx.gemm(0, 0, 1.0, Ki, psi2, 0.0, tmp)
+        ctx.gemm(0, 0, 1.0, tmp, Ki, 0.0, KpK)       # Kuu^-1 psi2 Kuu^-1
+        alpha = ctx.empty(M, DY)
+        ctx.scale_copy(c, alpha)
+        ctx.trsm(LB, alpha, trans=1)
+        ctx.trsm(L, alpha, trans=1)                  # alpha = L^-T LB^-T c
+        g1, g2, dK, out, bound = ctx.empty(N, M), ctx.empty(M, M), ctx.empty(M, M), ctx.empty(8), ctx.empty(7)
+        ctx.gemm(0, 1, 1.0 / s2, Y, alpha, 0.0, g1)  # Y alpha^T / s2
+        ctx.collapsed_adjoints(Si, Ki, KpK, psi2, alpha, c, Y, psi0, s2, g2, dK, out)
+        ctx.collapsed_bound(LB, f["G"], c, Y, psi0, s2, bound)
+        spec = f["spec"]
         D = int(spec.input_dim)
         nls = D if spec.ard else 1
-        run = lambda rc: _lib.check(rc)
-        zeros = ctx.torch.zeros(M, M, dtype=ctx.torch.float64, device=f["Z"].device)
-        Li, W, Si, Ki, tmp, KpK = (ctx.empty(M, M) for _ in range(6))
-        run(lib.dsdgp_scale_copy(h, 0, M, M, ptr(zeros), M, 1.0, 1.0, ptr(Li), M))                 # I
-        run(lib.dsdgp_trsm(h, 0, M, M, ptr(f["L"]), M, ptr(Li), M))                                # L^-1
-        run(lib.dsdgp_scale_copy(h, 0, M, M, ptr(Li), M, 1.0, 0.0, ptr(W), M))
-        run(lib.dsdgp_trsm(h, 0, M, M, ptr(f["LB"]), M, ptr(W), M))                                # LB^-1 L^-1
-        run(lib.dsdgp_gemm(h, 1, 0, M, M, M, 1.0, ptr(W), M, ptr(W), M, 0.0, ptr(Si), M))          # Sigma^-1
-        run(lib.dsdgp_gemm(h, 1, 0, M, M, M, 1.0, ptr(Li), M, ptr(Li), M, 0.0, ptr(Ki), M))        # Kuu^-1
-        run(lib.dsdgp_gemm(h, 0, 0, M, M, M, 1.0, ptr(Ki), M, ptr(f["psi2"]), M, 0.0, ptr(tmp), M))
-        run(lib.dsdgp_gemm(h, 0, 0, M, M, M, 1.0, ptr(tmp), M, ptr(Ki), M, 0.0, ptr(KpK), M))      # Kuu^-1 psi2 Kuu^-1
-        alpha = ctx.empty(M, DY)
-        run(lib.dsdgp_scale_copy(h, 0, M, DY, ptr(f["c"]), DY, 1.0, 0.0, ptr(alpha), DY))
-        run(lib.dsdgp_trsm(h, 1, M, DY, ptr(f["LB"]), M, ptr(alpha), DY))
-        run(lib.dsdgp_trsm(h, 1, M, DY, ptr(f["L"]), M, ptr(alpha), DY))                           # alpha = L^-T LB^-T c
-        g1, g2, dK, out, bound = ctx.empty(N, M), ctx.empty(M, M), ctx.empty(M, M), ctx.empty(8), ctx.empty(7)
-        run(lib.dsdgp_gemm(h, 0, 1, N, M, DY, 1.0 / s2, ptr(self._Y), DY, ptr(alpha), DY, 0.0, ptr(g1), M))      # Y alpha^T / s2
-        run(lib.dsdgp_collapsed_adjoints(h, M, N, DY, ptr(Si), ptr(Ki), ptr(KpK), ptr(f["psi2"]), ptr(alpha), ptr(f["c"]), ptr(self._Y),
-                                         ptr(f["psi0"]), s2, ptr(g2), ptr(dK), ptr(out)))
-        run(lib.dsdgp_collapsed_bound(h, M, N, DY, ptr(f["LB"]), M, ptr(f["G"]), M, ptr(f["c"]), ptr(self._Y), ptr(f["psi0"]), s2,
-                                      ptr(bound)))
         d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(1 + nls)
         k_mu, k_Z, k_k = ctx.empty(M, D), ctx.empty(M, D), ctx.empty(1 + nls)
-        run(lib.dsdgp_rbf_expectations_grad(h, C.byref(spec), ptr(f["Z"]), M, ptr(self._X_mean), ptr(self._X_var), N, -0.5 * DY / s2,
-                                            ptr(g1), M, ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k)))
-        run(lib.dsdgp_rbf_expectations_grad(h, C.byref(spec), ptr(f["Z"]), M, ptr(f["Z"]), None, M, 0.0, ptr(dK), M, None, 0,
-                                            ptr(k_mu), None, ptr(k_Z), ptr(k_k)))
+        grad = lambda *args: _lib.check(ctx.lib.dsdgp_rbf_expectations_grad(ctx.handle, C.byref(spec), ptr(Z), M, *args))
+        grad(ptr(self._X_mean), ptr(self._X_var), N, -0.5 * DY / s2, ptr(g1), M, ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k))
+        grad(ptr(Z), None, M, 0.0, ptr(dK), M, None, 0, ptr(k_mu), None, ptr(k_Z), ptr(k_k))
         d_Z = d_Z + (k_Z + k_mu)                     # element-wise sums of the two calls' results, on the context's stream
         d_k = d_k + k_k
         res = dict(bound=bound[:1], Z=d_Z, variance=d_k[:1], lengthscales=d_k[1:], lik_variance=out[:1], X_mean=d_mu, X_var=d_s)
-        if on_device:
-            return res
-        ctx.sync()
-        res = {k: v.cpu().numpy() for k, v in res.items()}
-        for k in ("bound", "variance", "lik_variance"):
-            res[k] = float(res[k][0])
-        return res
+        return res if on_device else _to_host(ctx, res, ("bound", "variance", "lik_variance"))
 
     # layers.py:483-525
     def conditional_ND(self, Xnew, full_cov=False):
-        import ctypes as C
-        from . import _lib
-        from .engine import ptr
         f = self._need_factors()
         ctx, M, DY = f["ctx"], self.num_inducing, f["DY"]
-        lib, h = ctx.lib, ctx.handle
-        Xs = Xnew.contiguous() if hasattr(Xnew, "data_ptr") else ctx.to_device(np.asarray(Xnew, dtype=np.float64))
+        Xs = ctx.as_device(Xnew)
         ns = Xs.shape[0]
         tmp1, tmp2, mean = ctx.empty(M, ns), ctx.empty(M, ns), ctx.empty(ns, DY)
-        _lib.check(lib.dsdgp_gram(h, C.byref(f["spec"]), ptr(f["Z"]), M, ptr(Xs), ns, 0.0, ptr(tmp1), ns))       # K(Z, X*)
-        _lib.check(lib.dsdgp_trsm(h, 0, M, ns, ptr(f["L"]), M, ptr(tmp1), ns))
-        _lib.check(lib.dsdgp_scale_copy(h, 0, M, ns, ptr(tmp1), ns, 1.0, 0.0, ptr(tmp2), ns))
-        _lib.check(lib.dsdgp_trsm(h, 0, M, ns, ptr(f["LB"]), M, ptr(tmp2), ns))
-        _lib.check(lib.dsdgp_gemm(h, 1, 0, ns, DY, M, 1.0, ptr(tmp2), ns, ptr(f["c"]), DY, 0.0, ptr(mean), DY))
+        ctx.gram(f["spec"], f["Z"], Xs, 0.0, tmp1)   # K(Z, X*)
+        ctx.trsm(f["L"], tmp1)
+        ctx.scale_copy(tmp1, tmp2)
+        ctx.trsm(f["LB"], tmp2)
+        ctx.gemm(1, 0, 1.0, tmp2, f["c"], 0.0, mean)
         if full_cov:
             K = ctx.empty(ns, ns)
-            _lib.check(lib.dsdgp_gram(h, C.byref(f["spec"]), ptr(Xs), ns, None, 0, 0.0, ptr(K), ns))
-            _lib.check(lib.dsdgp_gemm(h, 1, 0, ns, ns, M, 1.0, ptr(tmp2), ns, ptr(tmp2), ns, 1.0, ptr(K), ns))
-            _lib.check(lib.dsdgp_gemm(h, 1, 0, ns, ns, M, -1.0, ptr(tmp1), ns, ptr(tmp1), ns, 1.0, ptr(K), ns))
+            ctx.gram(f["spec"], Xs, None, 0.0, K)
+            ctx.gemm(1, 0, 1.0, tmp2, tmp2, 1.0, K)
+            ctx.gemm(1, 0, -1.0, tmp1, tmp1, 1.0, K)
             ctx.sync()
             return mean.cpu().numpy(), np.tile(K.cpu().numpy()[:, :, None], [1, 1, DY])       # layers.py:518-519: a copy per output
         var = ctx.empty(ns, DY)
-        _lib.check(lib.dsdgp_collapsed_var(h, M, ns, DY, ptr(tmp1), ns, ptr(tmp2), ns, f["kdiag"], ptr(var)))
+        ctx.collapsed_var(tmp1, tmp2, f["kdiag"], var)
         ctx.sync()
         return mean.cpu().numpy(), var.cpu().numpy()

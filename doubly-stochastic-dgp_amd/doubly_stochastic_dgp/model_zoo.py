@@ -194,7 +194,8 @@ class DGP_Collapsed(DGP_Base):
         if X is not None or Y is not None:
             raise ValueError("DGP_Collapsed: the bound is that of the whole training set (model_zoo.py:54); no minibatch is taken")
         if with_grad:
-            raise NotImplementedError("DGP_Collapsed: no reverse pass is built through the kernel expectations")
+            raise NotImplementedError("DGP_Collapsed: the reverse pass through the inner layers' engine is not connected to the adjoints of "
+                                      "the last layer's inputs (compute_log_likelihood_gradients: X_mean, X_var); see training.ScipyOptimizer")
         self._set_data(zs=zs)
         bound = self.layers[-1].build_likelihood()
         KL = sum(layer.KL() for layer in self.layers[:-1])
@@ -221,5 +222,6 @@ class DGP_Collapsed(DGP_Base):
         return g["bound"] - KL, pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
 
     def train_step(self, *args, **kwargs):
-        raise NotImplementedError("DGP_Collapsed: no reverse pass is built through the kernel expectations — train a DGP and read "
-                                  "the collapsed bound through DGP_Collapsed.from_dgp(model)")
+        raise NotImplementedError("DGP_Collapsed: the reverse pass through the inner layers' engine is not connected to the adjoints of "
+                                  "the last layer's inputs — fit the collapsed layer with training.ScipyOptimizer, or train a DGP and "
+                                  "read the collapsed bound through DGP_Collapsed.from_dgp(model)")

@@ -143,6 +143,30 @@ def test_outputs_are_optional(ctx):
     assert _same_bits(a1.cpu().numpy(), p1w) and _same_bits(a2.cpu().numpy(), p2w)
 
 
+def test_float32_and_strided_tensors_are_converted_not_reinterpreted(ctx):
+    """n = 17, M = 5, D = 3: a float32 device tensor for X_mean and a transposed (non-contiguous) view for Z give the bits of the
+    float64 contiguous copies of the same values, in the expectations and in their reverse pass."""
+    import torch
+    from doubly_stochastic_dgp.gpflow_compat import RBF
+    from doubly_stochastic_dgp.layers import kernel_expectations, kernel_expectations_grad
+    rng = np.random.default_rng(7)
+    n, M, D = 17, 5, 3
+    mu32 = ctx.to_device(rng.standard_normal((n, D))).to(torch.float32)
+    Zt = ctx.to_device(rng.standard_normal((D, M))).t()
+    s, g1, g2 = rng.uniform(0.0, 0.8, (n, D)), rng.standard_normal((n, M)), rng.standard_normal((M, M))
+    assert mu32.dtype == torch.float32 and not Zt.is_contiguous() and tuple(Zt.shape) == (M, D)
+    mu64, Zc = mu32.to(torch.float64), Zt.contiguous()
+    kern = RBF(D, variance=1.7, lengthscales=np.array([0.9, 1.4, 2.0]), ARD=True)
+    got, want = kernel_expectations(kern, Zt, mu32, s), kernel_expectations(kern, Zc, mu64, s)
+    assert got[0] == want[0] and _same_bits(got[1], want[1]) and _same_bits(got[2], want[2])
+    assert np.all(np.isfinite(want[1])) and np.all(want[2] > 0.0)
+    got = kernel_expectations_grad(kern, Zt, mu32, s, -0.7, g1, g2)
+    want = kernel_expectations_grad(kern, Zc, mu64, s, -0.7, g1, g2)
+    for k in ("X_mean", "X_var", "Z", "lengthscales"):
+        assert _same_bits(got[k], want[k]) and np.all(np.isfinite(want[k])) and np.any(want[k] != 0.0), k
+    assert got["variance"] == want["variance"]
+
+
 def test_error_codes(ctx):
     c = PC.inputs("n15")
     n, M = c["mu"].shape[0], c["Z"].shape[0]
