@@ -479,6 +479,7 @@ extern "C" int dsdgp_multiclass_readout(dsdgp_ctx* ctx, const double* mean, cons
 extern "C" int dsdgp_model_layer_conditional(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean,
                                              double* var) {
   DS_CHECK_ARG(m && X && mean && var && l >= 0 && l < m->desc.L && n > 0);
+  m->saved = false;      // (the GEMM-formulated pass works in the scratch the saved pass left its operands in)
   if (!m->prepared) DS_TRY(prepare_async(m));
   LayerState& St = m->L[l];
   const LayerDev& v = St.dev;

@@ -138,7 +138,7 @@ extern "C" int dsdgp_model_natgrad_step(dsdgp_model* m, int32_t l, double gamma,
   DS_LAUNCH(k_ng_mu, dim3(ceil_div(v.D_out * v.M, 4)), dim3(256), 0, ctx->stream, m->layers_dev, l, m->theta, 1);
   DS_LAUNCH(k_ng_write, dim3(nb), dim3(256), 0, ctx->stream, m->layers_dev, l, m->theta);
   DS_HIP(hipGetLastError());
-  m->prepared = false;
+  m->prepared = m->saved = false;
   m->q_dirty = (m->q_dirty == -1 || m->q_dirty == l) ? l : -2;     // Z and the kernel hyper-parameters are untouched: kuu_valid stays
   if (info) {
     std::vector<double> sc(2 * v.D_out);
@@ -195,6 +195,7 @@ static int run_gemms(dsdgp_ctx* ctx, std::vector<GemmProblem>& probs, GemmProble
 extern "C" int dsdgp_model_layer_conditional_full(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean,
                                                   double* var) {
   DS_CHECK_ARG(m && X && mean && var && l >= 0 && l < m->desc.L && n > 0);
+  m->saved = false;
   if (!m->prepared) DS_TRY(prepare_async(m));
   dsdgp_ctx* ctx = m->ctx;
   LayerState& St = m->L[l];

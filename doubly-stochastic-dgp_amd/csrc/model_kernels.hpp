@@ -350,6 +350,16 @@ __global__ __launch_bounds__(256) void k_lik_elbo(int kind, const double* __rest
   }
 }
 
+// The caller's adjoints of a scalar J in the last layer's mean / var (dsdgp_model_backward_adjoints) as the reverse pass reads its seed:
+// the adjoints of loss = -J, where k_lik_elbo and the MultiClass kernels leave theirs
+__global__ void k_seed_adjoints(const double* __restrict__ dmean, const double* __restrict__ dvar, int64_t count,
+                                double* __restrict__ lik_dmean, double* __restrict__ lik_dvar) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+    lik_dmean[i] = -dmean[i];
+    lik_dvar[i] = -dvar[i];
+  }
+}
+
 // per-sample quadrature weights applied to per-row values (R = S*n rows) and the (R x K) adjoints (MultiClass + DGP_Quad)
 __global__ void k_scale_by_sample(const double* __restrict__ sw, int64_t n, int S, int K, int64_t R, double* __restrict__ ve,
                                   double* __restrict__ dmean, double* __restrict__ dvar) {

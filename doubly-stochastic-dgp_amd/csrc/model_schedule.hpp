@@ -37,6 +37,7 @@ static int prepare_async(dsdgp_model* m, bool with_grad = false, bool side = fal
                          const HeadGather* hg = nullptr) {
   dsdgp_ctx* ctx = m->ctx;
   const int L = m->desc.L;
+  m->saved = false;
   DS_TRY(join_prep(m));
   const bool keep_kuu = m->track_theta && m->kuu_valid;
   // dsdgp_model_track_theta and no change since an evaluation that produced everything this one needs: the factor AND the
@@ -228,6 +229,7 @@ static int forward_layers(dsdgp_model* m, const double* X, int64_t n, int S, con
   // Mp <= 256: the larger instances read the factor transposed, which exists for q_sqrt only.
   const bool wf_ok = !m->desc.white && !save && m->force.white_fwd != 0;
   m->last_deferred = false;
+  m->saved = false;
   if (wf_ok) DS_TRY(join_prep(m));          // V, nL come from the parameter products (side stream in the overlapped schedule)
   for (int l = 0; l < L; ++l) {
     LayerState& St = m->L[l];
@@ -687,26 +689,15 @@ static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
   return end_unfused(m, ctx->stream, m->layers_dev + gfirst, L - gfirst, kl_weight);
 }
 
-// minibatch to gather before the evaluation (dsdgp_model_train_step_minibatch): rows idx[0..n) of the resident data
-struct GatherSrc {
-  const double *Xs, *Ys;
-  const int64_t* idx;
-};
-static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
-                     const int64_t* zstride, uint64_t seed, double data_scale, double kl_weight, int with_grad, double* out,
-                     const GatherSrc* gs) {
-  DS_CHECK_ARG(m && out && ((X && Y) || gs));
-  DS_CHECK_ARG(!zs || zstride);
-  DS_CHECK_ARG(!m->sample_w || S == m->sample_w_S);
-  if (with_grad) {
-    DS_CHECK_ARG(m->grad != nullptr);
-  }
+// The N(0,1) draws of the inner layers that no explicit zs covers, ahead of the factorisation they do not depend on: in spare block
+// columns of the fused head launch (*hr filled for prepare_async, *z_head), else — overlapped schedule — on the side stream while Ku is
+// factorised (*z_side: the caller waits for ev_z behind prepare_async).  Neither: forward_layers draws them itself.
+static int inner_draws(dsdgp_model* m, int64_t n, int S, const double* const* zs, uint64_t seed, bool ovl, HeadRand* hrp, bool* z_head_p,
+                       bool* z_side_p) {
   dsdgp_ctx* ctx = m->ctx;
   const int L = m->desc.L;
-  // fresh N(0,1) draws do not depend on the parameters: generate them on the side stream while Ku is factorised
   bool z_side = false, z_head = false;
-  const bool ovl = overlap_on(m, n, S);
-  HeadRand hr{};
+  HeadRand& hr = *hrp;
   if (m->head_ok) {
     // ... or, with the fused head launch, in spare block columns of that launch (no second stream, no events)
     hr.seed = seed;
@@ -727,6 +718,39 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
       }
     if (z_side) DS_HIP(hipEventRecord(m->ev_z, m->side));
   }
+  *z_head_p = z_head; *z_side_p = z_side;
+  return DSDGP_OK;
+}
+// the value (and the likelihood parameter's gradient) where the reverse pass's ending has not produced it: m->fin
+static int finish_value(dsdgp_model* m) {
+  if (!m->fin.done) {
+    DS_TRY(join_prep(m));   // KL values
+    DS_TRY(launch_finalize(m, m->ctx->stream));
+  }
+  m->prepared = true;
+  return DSDGP_OK;
+}
+
+// minibatch to gather before the evaluation (dsdgp_model_train_step_minibatch): rows idx[0..n) of the resident data
+struct GatherSrc {
+  const double *Xs, *Ys;
+  const int64_t* idx;
+};
+static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
+                     const int64_t* zstride, uint64_t seed, double data_scale, double kl_weight, int with_grad, double* out,
+                     const GatherSrc* gs) {
+  DS_CHECK_ARG(m && out && ((X && Y) || gs));
+  DS_CHECK_ARG(!zs || zstride);
+  DS_CHECK_ARG(!m->sample_w || S == m->sample_w_S);
+  if (with_grad) {
+    DS_CHECK_ARG(m->grad != nullptr);
+  }
+  dsdgp_ctx* ctx = m->ctx;
+  const int L = m->desc.L;
+  bool z_side = false, z_head = false;
+  const bool ovl = overlap_on(m, n, S);
+  HeadRand hr{};
+  DS_TRY(inner_draws(m, n, S, zs, seed, ovl, &hr, &z_head, &z_side));
   HeadGather hg{};
   if (gs) {
     DS_CHECK_ARG(n > 0 && n <= m->n_max);
@@ -789,12 +813,7 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
     DS_TRY(backward_layers(m, n, S, kl_weight));
     m->grad_pruned = !m->desc.white && (m->grad_first > 0 || m->grad_q_only);
   }
-  if (!m->fin.done) {
-    DS_TRY(join_prep(m));   // KL values
-    DS_TRY(launch_finalize(m, ctx->stream));
-  }
-  m->prepared = true;
-  return DSDGP_OK;
+  return finish_value(m);
 }
 
 extern "C" int dsdgp_model_elbo(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S,
@@ -802,6 +821,77 @@ extern "C" int dsdgp_model_elbo(dsdgp_model* m, const double* X, const double* Y
                                 double kl_weight, int with_grad, double* out) {
   DS_CHECK_ARG(X && Y);
   return elbo_impl(m, X, Y, n, S, zs, zstride, seed, data_scale, kl_weight, with_grad, out, nullptr);
+}
+
+// Vector-Jacobian product of the layers (model_zoo.py:52-57: the collapsed bound differentiated through the inner layers).  The forward
+// half: the front of elbo_impl(with_grad = 1) — draws, prepare with the gradient-side products, chains with save — and no likelihood
+// (lik_Y null: neither the fused last launch of layer_last.hip nor the likelihood-in-epilogue instance is taken), no sample of the last layer.
+static int vjp_refusals(const char* who, const dsdgp_model* m) {
+  if (m->bucket_fn) {
+    dsdgp_set_error("%s: a bucket callback is set (dsdgp_model_set_bucket_callback); the vector-Jacobian product is single-process", who);
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  if (m->sample_w) {
+    dsdgp_set_error("%s: quadrature sample weights are set (dsdgp_model_set_sample_weights); the caller's adjoints carry their own weights", who);
+    return DSDGP_ERR_UNSUPPORTED;
+  }
+  if (!m->desc.white && (m->grad_first > 0 || m->grad_q_only)) {
+    dsdgp_set_error("%s: the reverse pass is restricted to layers >= %d%s (dsdgp_model_set_grad_first_layer / _q_only)", who, m->grad_first,
+                    m->grad_q_only ? ", (q_mu, q_sqrt) only" : "");
+    return DSDGP_ERR_BAD_ARG;
+  }
+  return DSDGP_OK;
+}
+extern "C" int dsdgp_model_forward_saved(dsdgp_model* m, const double* X, int64_t n, int32_t S, const double* const* zs,
+                                         const int64_t* zstride, uint64_t seed, double* mean_out, double* var_out) {
+  DS_CHECK_ARG(m && X && m->grad != nullptr);
+  DS_CHECK_ARG(!zs || zstride);
+  DS_CHECK_ARG(n > 0 && n <= m->n_max && S > 0 && S <= m->s_max);
+  DS_TRY(vjp_refusals("dsdgp_model_forward_saved", m));
+  dsdgp_ctx* ctx = m->ctx;
+  bool z_side = false, z_head = false;
+  const bool ovl = overlap_on(m, n, S);
+  HeadRand hr{};
+  DS_TRY(inner_draws(m, n, S, zs, seed, ovl, &hr, &z_head, &z_side));
+  DS_TRY(prepare_async(m, true, ovl, z_head ? &hr : nullptr, nullptr));
+  if (z_side) DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_z, 0));
+  m->fused_last = false;
+  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, true, false, nullptr, nullptr, nullptr, z_side || z_head));
+  const LayerState& last = m->L[m->desc.L - 1];
+  const size_t bytes = (size_t)S * n * last.dev.D_out * sizeof(double);
+  if (mean_out) DS_HIP(hipMemcpyAsync(mean_out, last.mean, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  if (var_out) DS_HIP(hipMemcpyAsync(var_out, last.var, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  m->saved = true; m->saved_n = n; m->saved_S = S;
+  return DSDGP_OK;
+}
+// The reverse half: the last layer's adjoints are the caller's (ADJ_PREP reads them from lik_dmean / lik_dvar, as after MultiClass), no
+// likelihood block takes part in the value (fin.nblocks = 0: lik_part is not read).
+extern "C" int dsdgp_model_backward_adjoints(dsdgp_model* m, const double* dmean, const double* dvar, double kl_weight, double* out) {
+  DS_CHECK_ARG(m && dmean && dvar && out && m->grad != nullptr);
+  if (!m->saved) {
+    dsdgp_set_error("dsdgp_model_backward_adjoints: the model's last evaluation is not a dsdgp_model_forward_saved (another evaluation, a "
+                    "change of theta or an optimiser step since then drops the saved forward pass)");
+    return DSDGP_ERR_BAD_ARG;
+  }
+  DS_TRY(vjp_refusals("dsdgp_model_backward_adjoints", m));
+  dsdgp_ctx* ctx = m->ctx;
+  const int64_t n = m->saved_n;
+  const int S = m->saved_S;
+  m->saved = false;       // consumed, also by a reverse pass that fails half-way
+  const int64_t count = (int64_t)S * n * m->L[m->desc.L - 1].dev.D_out;      // <= s_max n_max D_out, the size of lik_dmean / lik_dvar
+  DS_LAUNCH(k_seed_adjoints, dim3((int)std::min<int64_t>(2048, ceil_div(count, 256))), dim3(256), 0, ctx->stream, dmean, dvar, count,
+            m->lik_dmean, m->lik_dvar);
+  DS_HIP(hipGetLastError());
+  m->fused_last = false;
+  m->fin.nblocks = 0; m->fin.w = 0.0; m->fin.kl_weight = kl_weight; m->fin.with_grad = 1; m->fin.out = out;
+  m->fin.done = false;
+  DS_TRY(backward_layers(m, n, S, kl_weight));
+  m->grad_pruned = false;
+  DS_TRY(finish_value(m));
+  // every ending writes -w * (sum of no partials) * sigmoid(raw) = -0.0 there: the entry is +0.0
+  const int64_t ol = lik_var_offset(m);
+  if (ol >= 0) DS_HIP(hipMemsetAsync(m->grad + ol, 0, sizeof(double), ctx->stream));
+  return DSDGP_OK;
 }
 
 extern "C" int dsdgp_model_set_sample_weights(dsdgp_model* m, const double* w, int32_t S) {
@@ -814,7 +904,7 @@ extern "C" int dsdgp_model_set_sample_weights(dsdgp_model* m, const double* w, i
 // Adam's bias-corrected step size at step t
 static double adam_lr_t(double lr, double b1, double b2, int64_t t) { return lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t)); }
 // theta moved (an optimiser step, the caller's write): nothing prepared from it stands
-static void mark_theta_moved(dsdgp_model* m) { m->prepared = m->kuu_valid = false; m->q_dirty = -2; }
+static void mark_theta_moved(dsdgp_model* m) { m->prepared = m->kuu_valid = m->saved = false; m->q_dirty = -2; }
 
 extern "C" int dsdgp_model_adam_step(dsdgp_model* m, double lr, double beta1, double beta2, double eps, int64_t t) {
   DS_CHECK_ARG(m && m->grad && m->adam_m && m->adam_v && t >= 1);

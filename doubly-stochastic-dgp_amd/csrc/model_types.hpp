@@ -72,6 +72,11 @@ struct dsdgp_model {
   int grad_first = 0;          // dsdgp_model_set_grad_first_layer: reverse mode stops below this layer
   bool grad_pruned = false;    // the gradient buffer holds a pruned reverse pass (entries of the lower layers are stale)
   bool grad_q_only = false;    // dsdgp_model_set_grad_q_only: only the (q_mu, q_sqrt) entries of the layers >= grad_first are wanted
+  // dsdgp_model_forward_saved was the last evaluation: the workspace holds what a reverse pass over saved_n rows x saved_S samples reads
+  // (dsdgp_model_backward_adjoints).  Dropped by prepare_async, forward_layers, mark_theta_moved and the other writers of the workspace.
+  bool saved = false;
+  int64_t saved_n = 0;
+  int saved_S = 0;
   int q_dirty = -2;            // with kuu_valid: -1 nothing changed, l >= 0 only layer l's (q_mu, q_sqrt) changed, -2 unknown / several
   bool side_pending = false;   // parameter-only work (Ku^-1, S_d, KL, U, UU) still running on the side stream
   int n_fwd, n_bwd1, n_bwd2, t_fwd, t_bwd1, t_bwd2, n_w, t_w1, t_w2, t_w3;

@@ -85,6 +85,9 @@ _PROTOS = {
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "dsdgp_model_elbo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_int64), C.c_uint64, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "dsdgp_model_forward_saved": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                            C.c_uint64, C.c_void_p, C.c_void_p]),
+    "dsdgp_model_backward_adjoints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "dsdgp_model_adam_step": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64]),
     "dsdgp_model_train_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_int64), C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_double,

@@ -451,6 +451,51 @@ class Engine:
             raise _lib.CholeskyError(f"Cholesky decomposition was not successful (Kuu pivot {int(out[3])})")
         return out
 
+    def forward_saved(self, X, S, zs=None, seed=0):
+        """dsdgp_model_forward_saved: the forward pass of a gradient evaluation without a likelihood -> (mean, var) of the last layer,
+        device tensors (S, n, D_out).  The reverse pass it keeps its state for is `backward_adjoints`; any other call of this engine in
+        between (an evaluation, an upload of changed parameters, an optimiser step) drops that state.  Asynchronous."""
+        Xd = X if hasattr(X, "data_ptr") else self.ctx.to_device(X)
+        n = Xd.shape[0]
+        self._ensure(n, S)
+        self._upload_if_needed()
+        if getattr(self, "_grad_first", 0) != 0:           # a restriction left by NatGradOptimizer: lifted, as train_step does
+            _lib.check(self.lib.dsdgp_model_set_grad_first_layer(self.model, 0))
+            self._grad_first = 0
+        if getattr(self, "_grad_q_only", False):
+            _lib.check(self.lib.dsdgp_model_set_grad_q_only(self.model, 0))
+            self._grad_q_only = False
+        zp, zst, keep = self._zs_args(zs, S, n)
+        D = self.layers[-1].num_outputs
+        mean, var = self.ctx.empty(S, n, D), self.ctx.empty(S, n, D)
+        _lib.check(self.lib.dsdgp_model_forward_saved(self.model, ptr(Xd), n, S, zp, zst, C.c_uint64(seed), ptr(mean), ptr(var)))
+        self._saved_shape = (self.generation, S, n, D)
+        self._saved_keep = (Xd, keep)       # the reverse pass reads X and the explicit draws again
+        return mean, var
+
+    def backward_adjoints(self, dmean, dvar, kl_weight=1.0, sync=True):
+        """dsdgp_model_backward_adjoints: dmean, dvar (S, n, D_out) are dJ/dmean and dJ/dvar of a scalar J of `forward_saved`'s results.
+        Leaves the gradient of loss = -(J - kl_weight * sum KL) where elbo(with_grad=True) leaves its own (`gradient_dict`, `adam_step`);
+        the likelihood's entry is 0.  Returns out4 = [-kl_weight * sum KL, 0, kl_weight * sum KL, 0] (None with sync=False)."""
+        shape = getattr(self, "_saved_shape", None)
+        if shape is None or shape[0] != self.generation or self._host_dirty:
+            raise _lib.DsdgpError("backward_adjoints: no saved forward pass (forward_saved) is this engine's last evaluation")
+        dm, dv = self.ctx.as_device(dmean), self.ctx.as_device(dvar)
+        for what, t in (("dmean", dm), ("dvar", dv)):       # the library copies S n D_out doubles from each
+            if tuple(t.shape) != shape[1:]:
+                raise ValueError(f"backward_adjoints: {what} has shape {tuple(t.shape)}, the saved forward pass {shape[1:]}")
+        try:
+            _lib.check(self.lib.dsdgp_model_backward_adjoints(self.model, ptr(dm), ptr(dv), float(kl_weight), ptr(self.out4)))
+        finally:
+            self._saved_shape = self._saved_keep = None
+        if not sync:
+            return None
+        self.ctx.sync()
+        out = self.out4.cpu().numpy()
+        if out[3] != 0.0:
+            raise _lib.CholeskyError(f"Cholesky decomposition was not successful (Kuu pivot {int(out[3])})")
+        return out
+
     def _mixture_batch_args(self, Xd, S, zs, Yd=None):
         """What evaluate_batch, quantiles_batch, calibration_batch and classification_batch do ahead of their library call -> (n, zp, zst, keep)"""
         n = Xd.shape[0]

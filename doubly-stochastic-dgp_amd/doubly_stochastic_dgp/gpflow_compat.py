@@ -24,6 +24,11 @@ def positive_forward(x):
     return np.logaddexp(0.0, np.asarray(x, dtype=np.float64)) + SOFTPLUS_LOWER
 
 
+def positive_slope(y):
+    """d positive_forward(x) / dx at the constrained value y: the sigmoid of x, 1 - exp(-(y - 1e-6))"""
+    return -np.expm1(-(np.asarray(y, dtype=np.float64) - SOFTPLUS_LOWER))
+
+
 class Parameter:
     """[UPSTREAM] gpflow.params.Parameter: `.value` / `.read_value()`, assignment through the parent attribute,
     `.trainable` / `.set_trainable()`.  transform in {None, 'positive', 'tril'}."""

@@ -2,12 +2,15 @@
 Its bound is the one of the reference's `_build_likelihood`: the last layer at its exact optimum over the WHOLE training set, the input
 noise of the last hop integrated analytically through the kernel expectations, minus the KL terms of the inner layers.  The inner
 layers run as one device Engine over `layers[:-1]` (`inner_engine()`; S = 1 on the full training set, explicit `zs` accepted); the
-last layer is the host layer loop that `DGP_Base.propagate(full_cov=True)` uses.  No reverse pass is built through the inner layers'
-engine: `train_step`, `AdamOptimizer` and `NatGradOptimizer` raise NotImplementedError — train a `DGP` (Adam plus natural-gradient
-steps), then read the collapsed bound and the predictions of the exactly optimal last layer through `DGP_Collapsed.from_dgp(model)`.
-What the collapsed layer itself owns — its inducing inputs, its kernel, the noise variance — has gradients
-(`compute_log_likelihood_gradients`, the reverse pass of the kernel expectations) and is fitted by `training.ScipyOptimizer`: for a
-one-layer model that is complete sparse-GP-regression training.  There is no engine over ALL
+last layer is the host layer loop that `DGP_Base.propagate(full_cov=True)` uses.  What the collapsed layer itself owns — its
+inducing inputs, its kernel, the noise variance — has gradients (`compute_log_likelihood_gradients`, the reverse pass of the kernel
+expectations); with `inner=True` the adjoints of the last layer's input mean and variance go on through the inner layers' engine
+(`Engine.forward_saved` / `backward_adjoints`, the library's dsdgp_model_forward_saved / dsdgp_model_backward_adjoints), so every
+trainable parameter of every layer has its gradient of the collapsed bound, as TensorFlow gives the reference.  Training is
+`training.ScipyOptimizer` (L-BFGS-B; `inner=True` for all layers) or `training.CollapsedAdamOptimizer` (full-batch Adam).  The
+minibatch machinery of a sampled bound — `train_step`, `AdamOptimizer`, `NatGradOptimizer`, `_build_likelihood(with_grad=True)` —
+still raises NotImplementedError: `supports_gradients` stays False, the bound being that of the whole training set.  A `DGP` trained
+on the sampled bound can also be read as a collapsed model through `DGP_Collapsed.from_dgp(model)`.  There is no engine over ALL
 layers (the collapsed layer has no variational parameters to put into one), so `engine()` and the device-side scoring methods built
 on it (`evaluate`, `predict_quantiles`, `calibration`, `classification_report`) raise NotImplementedError as well: score a collapsed
 model from `predict_y` / `predict_density`."""
@@ -19,7 +22,7 @@ import numpy as np
 from . import _lib
 from .dgp import DGP_Base
 from .gpflow_compat import Gaussian
-from .layers import Collapsed_Layer, SGPR_Layer, concat_input_prop
+from .layers import Collapsed_Layer, SGPR_Layer, _to_host, concat_input_prop
 
 
 class DGP_Collapsed(DGP_Base):
@@ -151,10 +154,11 @@ class DGP_Collapsed(DGP_Base):
             Fin = Fs[l]
         return Fs, Fmeans, Fvars
 
-    def _set_data(self, zs=None):
+    def _set_data(self, zs=None, seed=None):
         """model_zoo.py:48-49, 54-55: the marginal mean and variance of the last layer's inputs at the training set (S = 1) become
         the collapsed layer's data.  One layer: the inputs themselves, zero variance.  The statistics go from the engine to the
-        layer as device tensors (unless the last inner layer propagates inputs: that concatenation is a host copy)."""
+        layer as device tensors (unless the last inner layer propagates inputs: that concatenation is a host copy).  seed: the Philox
+        seed of the hidden layers' draws where zs gives none (None: the model's next)."""
         lik_var = float(self.likelihood.likelihood.variance.value)
         Xd, Yd = self._device_data()
         if len(self.layers) == 1:
@@ -167,7 +171,7 @@ class DGP_Collapsed(DGP_Base):
         self._refresh()
         eng = self.inner_engine()
         zs = list(zs)[:len(self.layers) - 1] if zs is not None else None
-        _, ms, vs = eng.propagate(Xd, 1, zs=zs, seed=self._draw_seed(), want=("mean", "var"))
+        _, ms, vs = eng.propagate(Xd, 1, zs=zs, seed=self._draw_seed() if seed is None else seed, want=("mean", "var"))
         self.layers[-1].set_data(ms[-1][0], vs[-1][0], Yd, lik_var)
 
     # ------------------------------------------------------------------ model_zoo.py:46-50
@@ -194,34 +198,99 @@ class DGP_Collapsed(DGP_Base):
         if X is not None or Y is not None:
             raise ValueError("DGP_Collapsed: the bound is that of the whole training set (model_zoo.py:54); no minibatch is taken")
         if with_grad:
-            raise NotImplementedError("DGP_Collapsed: the reverse pass through the inner layers' engine is not connected to the adjoints of "
-                                      "the last layer's inputs (compute_log_likelihood_gradients: X_mean, X_var); see training.ScipyOptimizer")
+            raise NotImplementedError("DGP_Collapsed._build_likelihood(with_grad=True) would leave a gradient in an engine over all layers, "
+                                      "which a collapsed model does not have; the reverse pass of the collapsed bound through the inner "
+                                      "layers is compute_log_likelihood_gradients(inner=True)")
         self._set_data(zs=zs)
         bound = self.layers[-1].build_likelihood()
         KL = sum(layer.KL() for layer in self.layers[:-1])
         return bound - KL
 
-    def compute_log_likelihood_gradients(self, zs=None):
+    def compute_log_likelihood_gradients(self, zs=None, inner=False):
         """(bound, [(Parameter, gradient), ...], {"X_mean": ..., "X_var": ...}): the bound of `compute_log_likelihood` and its
         gradients with respect to the constrained values of the parameters the collapsed last layer owns — its `feature.Z`,
         `kern.variance` and `kern.lengthscales` — and of the likelihood's `variance` (SGPR_Layer.bound_gradients; each gradient has its
         Parameter's shape).  These four are exact at any depth: the inner layers do not depend on them, and the KL terms do not either.
-        The inner layers' OWN parameters are not covered: the bound reaches them only through the mean and the variance of the last
-        layer's inputs, whose adjoints are the third result, `X_mean` and `X_var` (N, D_in) — where a reverse pass through the inner
-        layers' engine connects.  zs: as for `compute_log_likelihood`."""
+        The bound reaches the inner layers' OWN parameters only through the mean and the variance of the last layer's inputs, whose
+        adjoints are the third result, `X_mean` and `X_var` (N, D_in).  zs: as for `compute_log_likelihood`.
+        inner=True: those adjoints seed the reverse pass of the inner layers' engine (Engine.forward_saved / backward_adjoints, on the
+        hidden layers' draws the bound was evaluated with: the same `zs`, or the same seed), and the list goes on,
+        behind the four pairs, with every trainable parameter of the inner layers in the engine's order — per layer `feature.Z`,
+        `q_mu`, `q_sqrt` (lower-triangular), the kernel's `variance` and `lengthscales`, a White part's `variance`, a trainable Linear
+        mean's `A` and `b` — again the gradient of the bound, the KL terms included, with respect to the constrained value.  A one-layer
+        model has no inner layers: the same four pairs.  NotImplementedError when the last inner layer propagates inputs
+        (`input_prop_dim`): the adjoints of the propagated columns would have to re-enter the layer below."""
         from .gpflow_compat import split_kernel
-        self._set_data(zs=zs)
+        inner = bool(inner) and len(self.layers) > 1
         top = self.layers[-1]
-        g = top.bound_gradients()
+        if inner:
+            if self.layers[-2].input_prop_dim:
+                raise NotImplementedError("DGP_Collapsed.compute_log_likelihood_gradients(inner=True): the last inner layer propagates "
+                                          "inputs (input_prop_dim); the adjoints of the propagated columns of X_mean / X_var would have "
+                                          "to re-enter the layer below, which the engine's reverse pass does not take")
+        seed = self._draw_seed() if inner else None        # (one seed per evaluation either way)
+        self._set_data(zs=zs, seed=seed)
+        if inner:
+            # The bound keeps the statistics of compute_log_likelihood (the engine's forward-only pass: same bits, same four pairs as
+            # without `inner`); the pass that keeps what the reverse pass reads repeats the layers on the same draws.  Its statistics
+            # differ from those by rounding only, and nothing below touches the engine before the reverse pass.
+            eng = self.inner_engine()
+            eng.forward_saved(self._device_data()[0], 1, zs=list(zs)[:len(self.layers) - 1] if zs is not None else None, seed=seed)
+            g = top.bound_gradients(on_device=True)
+            eng.backward_adjoints(g["X_mean"][None], g["X_var"][None], sync=False)
+            g = _to_host(eng.ctx, g, ("bound", "variance", "lik_variance"))
+        else:
+            g = top.bound_gradients()
         KL = sum(layer.KL() for layer in self.layers[:-1])
         stat, _ = split_kernel(top.kern)
         lik = self.likelihood.likelihood
         pairs = [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape))
                  for p, k in ((top.feature.Z, "Z"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales"),
                               (lik.variance, "lik_variance"))]
+        if inner:
+            pairs += self._inner_pairs(eng)
         return g["bound"] - KL, pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
 
+    def inner_parameters(self):
+        """The Parameters of the inner layers in the order of the engine's layout (trainable or not) — per layer `feature.Z`, `q_mu`,
+        `q_sqrt`, the kernel's `variance` and `lengthscales`, a White part's `variance`, and `A`, `b` of a Linear mean that is not a
+        fixed map.  Host only: no engine is built."""
+        from .gpflow_compat import split_kernel
+        out = []
+        for layer in self.layers[:-1]:
+            stat, wk = split_kernel(layer.kern)
+            out += [layer.feature.Z, layer.q_mu, layer.q_sqrt, stat.variance, stat.lengthscales]
+            if wk is not None:
+                out.append(wk.variance)
+            mf = layer.mean_function
+            if mf.kind == "linear" and mf.in_theta():
+                out += [mf.A, mf.b]
+        return out
+
+    def _inner_pairs(self, eng):
+        """[(Parameter, gradient), ...] of the inner layers' trainable parameters from the engine's gradient buffer, which holds
+        d(-bound)/d(unconstrained): sign flipped, a positive parameter's entry divided by d theta / dx (gpflow_compat.positive_slope)."""
+        from .gpflow_compat import positive_slope
+        eng.ctx.sync()
+        out4 = eng.out4.cpu().numpy()
+        if out4[3] != 0.0:
+            raise _lib.CholeskyError(f"Cholesky decomposition was not successful (Kuu pivot {int(out4[3])})")
+        grad = eng.grad.cpu().numpy()
+        lik_p = self.likelihood.likelihood.variance
+        pairs = []
+        for p, off, cnt, kind in eng.entries:
+            if p is lik_p or not p.trainable:
+                continue
+            gp = -grad[off:off + cnt].reshape(p.shape)
+            if kind == "pos":
+                gp = gp / positive_slope(p._value)
+            elif kind == "qsqrt":
+                gp = np.tril(gp)
+            pairs.append((p, gp))
+        return pairs
+
     def train_step(self, *args, **kwargs):
-        raise NotImplementedError("DGP_Collapsed: the reverse pass through the inner layers' engine is not connected to the adjoints of "
-                                  "the last layer's inputs — fit the collapsed layer with training.ScipyOptimizer, or train a DGP and "
-                                  "read the collapsed bound through DGP_Collapsed.from_dgp(model)")
+        raise NotImplementedError("DGP_Collapsed.train_step takes a minibatch step of the sampled bound; the collapsed bound is that of "
+                                  "the whole training set, and its reverse pass through the inner layers is "
+                                  "compute_log_likelihood_gradients(inner=True) — train with training.ScipyOptimizer(inner=True) or "
+                                  "training.CollapsedAdamOptimizer")

@@ -1,6 +1,9 @@
 """[UPSTREAM] gpflow.training.AdamOptimizer mirror: `AdamOptimizer(0.01).minimize(model, maxiter=K)`
 (demos/demo_regression_UCI.ipynb:324).  The step itself (gradient + Adam update) runs in libdsdgp."""
 
+_NO_SAMPLED_GRADIENT = ("{} takes no minibatch step of a sampled bound: there is no reverse pass of one to step along (a DGP_Collapsed "
+                        "trains on its own bound: ScipyOptimizer(inner=True), CollapsedAdamOptimizer)")
+
 
 class AdamOptimizer:
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8):
@@ -8,7 +11,7 @@ class AdamOptimizer:
 
     def minimize(self, model, maxiter=1000):
         if not getattr(model, "supports_gradients", True):
-            raise NotImplementedError(f"{type(model).__name__} builds no reverse pass: there is no gradient to step along")
+            raise NotImplementedError(_NO_SAMPLED_GRADIENT.format(type(model).__name__))
         n = int(maxiter)
         for it in range(n):
             # steps are asynchronous; the last one synchronises and surfaces a failed Kuu factorisation (CholeskyError)
@@ -35,7 +38,7 @@ class NatGradOptimizer:
 
     def minimize(self, model, var_list, maxiter=1, X=None, Y=None, zs=None):
         if not getattr(model, "supports_gradients", True):
-            raise NotImplementedError(f"{type(model).__name__} builds no reverse pass: there is no gradient to step along")
+            raise NotImplementedError(_NO_SAMPLED_GRADIENT.format(type(model).__name__))
         layers = self._layer_indices(model, var_list)
         eng = model.engine()
         for _ in range(int(maxiter)):
@@ -64,31 +67,33 @@ class ScipyOptimizer:
     def __init__(self, method="L-BFGS-B", tol=None, options=None):
         self.method, self.tol, self.options = method, tol, dict(options or {})
 
-    def minimize(self, model, maxiter=1000, zs=None):
-        """returns scipy's OptimizeResult (`fun` = minus the bound); zs: fixed draws for the inner layers, as compute_log_likelihood"""
+    def minimize(self, model, maxiter=1000, zs=None, inner=False):
+        """returns scipy's OptimizeResult (`fun` = minus the bound); zs: fixed draws for the inner layers, as compute_log_likelihood.
+        inner=True: the search is over the trainable parameters of ALL layers — the four above, then `DGP_Collapsed.inner_parameters()`
+        — with the gradients of `compute_log_likelihood_gradients(inner=True)`; of a `q_sqrt` only the lower triangle is a variable."""
         import numpy as np
         import scipy.optimize
         from ._lib import CholeskyError
-        from .gpflow_compat import SOFTPLUS_LOWER, positive_backward, positive_forward, split_kernel
+        from .gpflow_compat import positive_backward, positive_forward, positive_slope, split_kernel
         from .model_zoo import DGP_Collapsed
         if not isinstance(model, DGP_Collapsed):
             raise NotImplementedError(f"ScipyOptimizer fits the collapsed last layer of a DGP_Collapsed; {type(model).__name__} is "
                                       "trained by AdamOptimizer / NatGradOptimizer")
-        top = model.layers[-1]
-        params = [top.feature.Z, split_kernel(top.kern)[0].variance, split_kernel(top.kern)[0].lengthscales,
-                  model.likelihood.likelihood.variance]
-        train = [p for p in params if p.trainable]
+        train, free = _collapsed_variables(model, inner)
         if not train:
-            raise ValueError("ScipyOptimizer: none of the collapsed layer's parameters is trainable")
-        sizes = [int(np.prod(p.shape)) for p in train]
+            raise ValueError("ScipyOptimizer: none of the collapsed layer's parameters is trainable" if not inner else
+                             "ScipyOptimizer: none of the model's parameters is trainable")
+        kw = {"inner": True} if inner else {}
 
         def pack(values):
-            return np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1) for v in values])
+            return np.concatenate([np.asarray(v, dtype=np.float64)[m] for v, m in zip(values, free)])
 
         def assign(x):
             at = 0
-            for p, k in zip(train, sizes):
-                v = x[at:at + k].reshape(p.shape)
+            for p, m in zip(train, free):
+                k = int(np.count_nonzero(m))
+                v = np.zeros(p.shape)
+                v[m] = x[at:at + k]
                 p.assign(positive_forward(v) if p.transform == "positive" else v)
                 at += k
 
@@ -97,7 +102,7 @@ class ScipyOptimizer:
         def objective(x):
             assign(x)
             try:
-                bound, pairs, _ = model.compute_log_likelihood_gradients(zs=zs)
+                bound, pairs, _ = model.compute_log_likelihood_gradients(zs=zs, **kw)
             except CholeskyError:
                 if last[0] is None:
                     raise
@@ -108,7 +113,7 @@ class ScipyOptimizer:
             for p in train:
                 g = grads[id(p)]
                 if p.transform == "positive":
-                    g = g * -np.expm1(-(p.value - SOFTPLUS_LOWER))
+                    g = g * positive_slope(p.value)
                 out.append(-g)
             return -float(bound), pack(out)
 
@@ -118,3 +123,72 @@ class ScipyOptimizer:
         res = scipy.optimize.minimize(objective, x0, jac=True, method=self.method, tol=self.tol, options=options)
         assign(res.x)
         return res
+
+
+def _collapsed_variables(model, inner):
+    """(the trainable Parameters a collapsed model is fitted over, a boolean mask per Parameter of the entries that are variables):
+    the collapsed layer's `feature.Z`, kernel `variance` and `lengthscales` and the likelihood's `variance`; with `inner` the inner
+    layers' as well.  Every entry is a variable, except above the diagonal of a `q_sqrt` (transform "tril")."""
+    import numpy as np
+    from .gpflow_compat import split_kernel
+    top = model.layers[-1]
+    stat = split_kernel(top.kern)[0]
+    params = [top.feature.Z, stat.variance, stat.lengthscales, model.likelihood.likelihood.variance]
+    if inner:
+        params += model.inner_parameters()
+    train = [p for p in params if p.trainable]
+    free = [np.broadcast_to(np.tril(np.ones(p.shape[-2:], dtype=bool)), p.shape) if p.transform == "tril" else np.ones(p.shape, dtype=bool)
+            for p in train]
+    return train, free
+
+
+class CollapsedAdamOptimizer:
+    """Full-batch Adam ascent on the bound of a `DGP_Collapsed` over the trainable parameters of all its layers, with the gradient of
+    `compute_log_likelihood_gradients(inner=True)` — tf.train.AdamOptimizer's rule (m, v, the bias-corrected step size
+    lr sqrt(1 - beta2^t) / (1 - beta1^t), the step lr_t m / (sqrt(v) + epsilon)) in unconstrained space.
+    The inner layers' parameters are stepped on the device, by dsdgp_model_adam_step on the inner engine's own parameter vector, moments
+    and the gradient the reverse pass left there.  The collapsed layer's four — `feature.Z`, kernel `variance` and `lengthscales`, the
+    likelihood's `variance` — are stepped by the same rule on the host and assigned through `Parameter.assign`.  The likelihood's
+    variance is the host's: its entry of the inner engine's gradient is zero, so the device does not move its copy, which is
+    overwritten from the host with the next upload.
+    What moves per step: the adjoints stay on the device; the four host gradients and the bound come down (a few hundred bytes plus
+    Z's M x D); the engine's parameter vector comes down once (`sync_to_host`, because the host assignment below reads the current
+    values) and goes up once (`mark_host_dirty` by the likelihood variance's assignment, which the inner engine also owns) — n_theta
+    doubles each way.  That is the existing coherence machinery, unchanged; it is small beside the N x M work of a step."""
+
+    def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8):
+        self.lr, self.b1, self.b2, self.eps = learning_rate, beta1, beta2, epsilon
+
+    def minimize(self, model, maxiter=1000, zs=None):
+        """returns the bound at the last evaluated point (before the last step); zs as for compute_log_likelihood"""
+        import numpy as np
+        from .gpflow_compat import positive_backward, positive_forward, positive_slope
+        from .model_zoo import DGP_Collapsed
+        if not isinstance(model, DGP_Collapsed):
+            raise NotImplementedError(f"CollapsedAdamOptimizer trains a DGP_Collapsed; {type(model).__name__} is trained by AdamOptimizer")
+        top4, _ = _collapsed_variables(model, False)
+        deep = len(model.layers) > 1
+        # moments and step count of the four live with the model, as the engine's do with the engine: a second call goes on (TF's slots)
+        state = getattr(model, "_collapsed_adam", None)
+        if state is None:
+            state = {"t": 0}
+            object.__setattr__(model, "_collapsed_adam", state)
+        bound = None
+        for _ in range(int(maxiter)):
+            bound, pairs, _adj = model.compute_log_likelihood_gradients(zs=zs, inner=True)
+            grads = {id(p): g for p, g in pairs}
+            if deep:
+                model.inner_engine().adam_step(self.lr, self.b1, self.b2, self.eps)
+            state["t"] += 1
+            lr_t = self.lr * np.sqrt(1.0 - self.b2 ** state["t"]) / (1.0 - self.b1 ** state["t"])
+            for p in top4:
+                pos = p.transform == "positive"
+                g = -grads[id(p)] * (positive_slope(p.value) if pos else 1.0)          # d(-bound)/dx
+                m, v = state.setdefault(id(p), (np.zeros(p.shape), np.zeros(p.shape)))
+                m[...] = self.b1 * m + (1.0 - self.b1) * g
+                v[...] = self.b2 * v + (1.0 - self.b2) * g * g
+                x = (positive_backward(p.value) if pos else p.value) - lr_t * m / (np.sqrt(v) + self.eps)
+                p.assign(positive_forward(x) if pos else x)
+        if deep and bound is not None:
+            model.inner_engine().prepare()      # the last host step reaches the device; a failed factorisation there is raised here
+        return bound

@@ -180,6 +180,29 @@ int dsdgp_model_elbo(dsdgp_model* m, const double* X, const double* Y, int64_t n
                      const double* const* zs, const int64_t* zstride, uint64_t seed, double data_scale,
                      double kl_weight, int with_grad, double* out);
 
+/* Vector-Jacobian product of the layers, in two calls: for a scalar J of the LAST layer's mean and variance that somebody else
+ * evaluates (model_zoo.py:52-57: the collapsed bound of DGP_Collapsed reads the inner layers' last mean and variance — the reference
+ * lets TensorFlow differentiate through them), the gradient of J - kl_weight * sum_l KL_l with respect to theta.
+ *
+ * dsdgp_model_forward_saved: the forward pass of a gradient evaluation (what dsdgp_model_elbo(with_grad = 1) does ahead of its
+ *   likelihood: draws, parameter products, the layers' chains keeping what the reverse pass reads) without a likelihood and without a
+ *   sample of the last layer.  X, n, S, zs, zstride, seed as for dsdgp_model_propagate (zs[L-1] is not read).  mean_out / var_out:
+ *   device, (S*n) x D_out of the last layer, row (s*n+i); either may be NULL (the values stay in the workspace).
+ *   The saved state is the model's until its next call of any kind but dsdgp_model_backward_adjoints: another evaluation
+ *   (propagate, elbo, training step, the mixture entries, layer_conditional*), dsdgp_model_theta_changed, an optimiser step or
+ *   dsdgp_model_prepare drops it.
+ * dsdgp_model_backward_adjoints: dmean / dvar (device, the layout of mean_out / var_out) are dJ/dmean and dJ/dvar.  Runs the reverse
+ *   pass of the saved forward pass and leaves the gradient of  loss = -(J - kl_weight * sum_l KL_l)  in `grad`: layout and sign as
+ *   dsdgp_model_elbo(with_grad = 1) leaves them, a FULL gradient (dsdgp_model_adam_step accepts it).  The likelihood takes no part:
+ *   its parameter's entry of `grad` is +0.0.  out (device, 4 doubles): [-kl_weight * KL_sum, 0, kl_weight * KL_sum, potrf_info].
+ *   The saved state is consumed: one reverse pass per forward pass.
+ * DSDGP_ERR_BAD_ARG: no saved forward pass is the model's last evaluation; the reverse pass is restricted
+ * (dsdgp_model_set_grad_first_layer / _q_only).  DSDGP_ERR_UNSUPPORTED: a bucket callback or quadrature sample weights are set.  A
+ * refused dsdgp_model_backward_adjoints writes nothing. */
+int dsdgp_model_forward_saved(dsdgp_model* m, const double* X, int64_t n, int32_t S, const double* const* zs, const int64_t* zstride,
+                              uint64_t seed, double* mean_out, double* var_out);
+int dsdgp_model_backward_adjoints(dsdgp_model* m, const double* dmean, const double* dvar, double kl_weight, double* out);
+
 /* DGP_Quad (dgp.py:129-166): replace the Monte-Carlo mean over the S propagated samples of dsdgp_model_elbo by the
  * weighted sum  sum_s w[s] (.)  (Gauss-Hermite weights, summing to one).  w: device, S doubles, borrowed until cleared;
  * NULL restores the mean.  dsdgp_model_elbo then requires its S argument to equal this S. */
