@@ -2,6 +2,8 @@
 #pragma once
 #include "common.hpp"
 
+#define XCH 64   // columns of x/l the chain kernels stage per chunk; inputs wider than this take the WIDE instances
+
 // SVGP_Layer.conditional_ND + reparameterize (layers.py:178-219, utils.py:40-41), fused.
 struct LayerFwdArgs {
   const double* X;   // (Rin x D_in) row-major inputs (for layer 0: the N minibatch rows, shared by all S samples)
@@ -127,7 +129,11 @@ int layer_fwd_sm_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, int Mp, int kern_
 int layer_bwd_sm_launch(dsdgp_ctx* ctx, const LayerBwdArgs& a, int Mp, int kern_kind, int white);
 // the last layer of a training step as one launch (layer_last.hip): forward chain + Gaussian likelihood + reverse mode of the same row block
 int layer_last_built(int Mp, int D_in, int D_out);
-int layer_last_waves(int Mp);
+// THE decision whether a last layer is inside the fused launch's scope, taken once at forward time (last_chain_fusable skips the forward
+// chain on it) and only asserted at launch.  `a`: the forward arguments; the backward side as it is known by then: hyp_rows = rows of
+// hyp_part per row block (sm_hyp_parts / row blocks), the backward chain's d_split (bwd_d_split), whether E is wanted (no algebraic
+// dl/dKu assembly).
+int layer_last_fusable(const LayerFwdArgs& a, int Mp, int kern_kind, int hyp_rows, int bwd_d_split, int want_E);
 int layer_last_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, const LayerBwdArgs& b, int Mp, int kern_kind, int hyp_rows);
 int sm_cs_built(int Mp);     // the split-M backward chain has a Csave instance for this padded inducing count
 int64_t sm_hyp_parts(int64_t ld, int Mp, int D_in);   // number of hyp_part rows the split-M backward writes for ld padded rows

@@ -66,52 +66,22 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 5 : 4)) void k_layer_last(const
   const bool rin = r < a.ldA, rvalid = r < a.Rin;
 
   // ------------------------------------------------------------------ forward half (k_layer_fwd_sm, D_out = 1)
-  if (a.XT1) {
-    for (int idx = tid; idx < 16 * (Din + 1); idx += NW * 64) {
-      const int j = idx >> 4, rr = idx & 15;
-      const int64_t rw = r0 + rr;
-      if (rw < a.ldA) a.XT1[(int64_t)j * a.ldA + rw] = (rw < a.Rin) ? (j < Din ? a.X[rw * Din + j] : 1.0) : 0.0;
-    }
-  }
-  for (int idx = tid; idx < 16 * Din; idx += NW * 64) {
-    const int rr = idx / Din, j = idx % Din;
-    int64_t row = r0 + rr;
-    if (row > a.Rin - 1) row = a.Rin - 1;
-    xs[rr * (Din + 1) + j] = a.X[row * Din + j] * ils[j];
-  }
+  if (a.XT1) store_xt1<NW>(a, r0, tid);
+  stage_x_over_l<NW>(a.X, ils, xs, Din, 0, Din, r0, a.Rin, tid);
   __syncthreads();
   {
     d4 r2[2];
     sqdist_narrow<2, MPB, NW>(a.Zs, xs, Din, wave, g, c, true, red_s1, r2);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int ib = q ? ib1 : ib0;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int m = 16 * ib + g + 4 * t;
-        const double kv = kern_val<KIND>(r2[q][t], s2);
-        actb[m * 16 + c] = (m < a.M) ? kv : 0.0;
-      }
-    }
+    kuf_tile_store<KIND, false>(r2[0], s2, a.M, actb, ib0, g, c);
+    kuf_tile_store<KIND, false>(r2[1], s2, a.M, actb, ib1, g, c);
   }
   __syncthreads();
   d4 acc[2];
   acc[0] = acc[1] = (d4){0, 0, 0, 0};
   chain_range2<Mp, false>(a.LinvT, actb, ib0, ib1, MPB, g, c, acc[0], acc[1]);           // a1 = Lu^-1 k (layers.py:186)
-  {
-    double p = 0.0;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) p = fma(acc[q][t], acc[q][t], p);
-    p = sum_groups(p);
-    if (g == 0) red_s1[wave * 16 + c] = p;
-  }
+  sumsq_partial<2>(acc, red_s1, wave, g, c, true);
   __syncthreads();
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) actb[(16 * (q ? ib1 : ib0) + g + 4 * t) * 16 + c] = acc[q][t];
+  acc_to_act<false, 2, MPB, NW>(acc, actb, wave, g, c);
   __syncthreads();
   acc[0] = acc[1] = (d4){0, 0, 0, 0};
   chain_range2<Mp, true>(a.Linv, actb, ib0, ib1, MPB, g, c, acc[0], acc[1]);             // a = Lu^-T a1 (layers.py:188)
@@ -138,15 +108,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 5 : 4)) void k_layer_last(const
   d4 cacc[2];
   cacc[0] = cacc[1] = (d4){0, 0, 0, 0};
   chain_range2<Mp, true>(a.Tp, actb, ib0, ib1, MPB, g, c, cacc[0], cacc[1]);             // c = q_sqrt^T a
-  {
-    double p = 0.0;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) p = fma(cacc[q][t], cacc[q][t], p);
-    p = sum_groups(p);
-    if (g == 0) red_s2[wave * 16 + c] = p;
-  }
+  sumsq_partial<2>(cacc, red_s2, wave, g, c, true);
   __syncthreads();        // partials published; every wave is done reading `a` from LDS
   // mean / var of the 16 rows, Gaussian variational expectations and their adjoints: lanes 0 .. 15 of wave 0, one row each
   if (wave == 0) {
@@ -191,16 +153,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 5 : 4)) void k_layer_last(const
   }
   // c -> LDS (the B operand of the next product); `a` to global memory for the weight-gradient products — from the registers, now:
   // the accumulators are re-used below
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) actb[(16 * (q ? ib1 : ib0) + g + 4 * t) * 16 + c] = cacc[q][t];
-  if (rin) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) a.Asave[(int64_t)(16 * (q ? ib1 : ib0) + g + 4 * t) * a.ldA + r] = rvalid ? acc[q][t] : 0.0;
-  }
+  acc_to_act<false, 2, MPB, NW>(cacc, actb, wave, g, c);
+  if (rin) acc_to_global<2, MPB, NW>(acc, a.Asave, a.ldA, r, rvalid, wave, g);
   __syncthreads();
 
   // ------------------------------------------------------------------ reverse half (k_layer_bwd_sm, D_out = 1, no E)
@@ -222,13 +176,9 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 5 : 4)) void k_layer_last(const
     }
   }
   __syncthreads();        // c fully consumed -> abar in its place
+  acc_to_act<false, 2, MPB, NW>(y, actb, wave, g, c);
 #pragma unroll
-  for (int q = 0; q < 2; ++q)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      actb[(16 * (q ? ib1 : ib0) + g + 4 * t) * 16 + c] = y[q][t];
-      acc[q][t] = -2.0 * vd * acc[q][t];             // kbar = Ku^-1 abar - 2 g a: the product below accumulates onto -2 g a
-    }
+  for (int q = 0; q < 2; ++q) acc[q] = -2.0 * vd * acc[q];      // kbar = Ku^-1 abar - 2 g a: the product below accumulates onto -2 g a
   __syncthreads();
   chain_dense2<Mp, MPB>(b.Kinv, actb, ib0, ib1, g, c, acc[0], acc[1]);
   // recompute the Kuf tile for GW = kbar * dk/dr2 (x / l is still staged)
@@ -237,110 +187,15 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 ? 5 : 4)) void k_layer_last(const
   __syncthreads();        // the distance code's scratch lives where the dX partials go
   double svar = 0.0;
 #pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int ib = q ? ib1 : ib0;
+  for (int q = 0; q < 2; ++q)
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int m = 16 * ib + g + 4 * t;
-      double k, dk;
-      kern_val_grad<KIND>(r2[q][t], s2, k, dk);
-      const bool ok = rvalid && (m < b.M);
-      const double kbar = acc[q][t];
-      svar += ok ? kbar * k : 0.0;
-      acc[q][t] = ok ? kbar * dk : 0.0;
-    }
-  }
-  svar = sum_wave(svar);
-  const double gk = sum_wave((rvalid && g == 0 && wave == 0) ? vd : 0.0);
-  double* hp = b.hyp_part + ((int64_t)blockIdx.x * hyp_rows + wave) * (Din + 2);
-  if (lane == 0) {
-    hp[0] = svar / s2;
-    hp[1] = gk;
-  }
+    for (int t = 0; t < 4; ++t) acc[q][t] = kbar_to_w<KIND>(acc[q][t], r2[q][t], s2, rvalid && (16 * (q ? ib1 : ib0) + g + 4 * t < b.M), svar);
+  double* hp = hyp_part_row(b, hyp_rows, wave);
+  hyp_head_store(svar, vd, s2, rvalid, hp, wave, lane);
   // the reduction plan counts hyp_rows partial rows per row block (the waves of the unfused backward instance): the surplus reads zero
   for (int e = tid; e < (hyp_rows - NW) * (Din + 2); e += NW * 64) b.hyp_part[((int64_t)blockIdx.x * hyp_rows + NW) * (Din + 2) + e] = 0.0;
-  {
-    const int jn = Din;
-    const bool single = 16 * jn <= NW * 64;
-    double pre_z = 0.0, pre_var = 1.0;
-    if (b.MBp && single && tid < 16 * jn) {
-      const int j = tid / 16, cc = tid % 16;
-      const int64_t row = r0 + cc;
-      const int d = j - b.prop;
-      if (row < b.Rin && d >= 0) {
-        pre_z = b.zp[(row / b.n_inner) * b.zp_s + (row % b.n_inner) * b.zp_n + d * b.zp_d];
-        pre_var = b.varp[row * b.Dp + d];
-      }
-    }
-    double w1 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) w1 += acc[q][t];
-    w1 = sum_groups(w1);
-    for (int kk = 0; kk < jn; kk += 16) {
-      d4 wz = (d4){0, 0, 0, 0}, z2 = (d4){0, 0, 0, 0};
-      const int jc = (kk + c < jn) ? kk + c : jn - 1;
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int ib = q ? ib1 : ib0;
-        double zv[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) zv[t] = b.Zs[(int64_t)(16 * ib + g + 4 * t) * Din + jc];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          wz = mfma_f64(zv[t], acc[q][t], wz);
-          z2 = mfma_f64(zv[t] * zv[t], acc[q][t], z2);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int j = kk + g + 4 * t;
-        const bool in = j < jn;
-        const double xv = xs[c * (jn + 1) + (in ? j : jn - 1)];
-        if ((b.dX || b.MBp) && in) redx[(wave * jn + j) * 16 + c] = fma(xv, w1, -wz[t]);
-        double sl = fma(xv * xv, w1, fma(-2.0 * xv, wz[t], z2[t]));
-        sl += dpp_or_zero<0x111, 0xf>(sl);
-        sl += dpp_or_zero<0x112, 0xf>(sl);
-        sl += dpp_or_zero<0x114, 0xf>(sl);
-        sl += dpp_or_zero<0x118, 0xf>(sl);
-        if (c == 15 && in) hp[2 + j] = -2.0 * ils[j] * sl;
-      }
-    }
-    if (b.dX || b.MBp) {
-      __syncthreads();
-      for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
-        const int j = b.MBp ? idx / 16 : idx % jn, cc = b.MBp ? idx % 16 : idx / jn;
-        const int64_t row = r0 + cc;
-        if (row < b.Rin) {
-          double sx = 0.0;
-#pragma unroll
-          for (int w = 0; w < NW; ++w) sx += redx[(w * jn + j) * 16 + cc];
-          double dx = 2.0 * ils[j] * sx;
-          if (b.MBp) {
-            const int d = j - b.prop;
-            if (d >= 0) {
-              const double zv = single ? pre_z : b.zp[(row / b.n_inner) * b.zp_s + (row % b.n_inner) * b.zp_n + d * b.zp_d];
-              const double vv = single ? pre_var : b.varp[row * b.Dp + d];
-              b.MBp[(int64_t)d * b.ldA + row] = dx;
-              b.VBp[(int64_t)d * b.ldA + row] = dx * zv * 0.5 * rsqrt(vv + b.jitter);
-            }
-          } else {
-            b.dX[row * Din + j] = dx;
-          }
-        } else if (b.MBp && row < b.ldA && j >= b.prop) {
-          b.MBp[(int64_t)(j - b.prop) * b.ldA + row] = 0.0;
-          b.VBp[(int64_t)(j - b.prop) * b.ldA + row] = 0.0;
-        }
-      }
-    }
-  }
-  if (rin) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) b.GW[(int64_t)(16 * (q ? ib1 : ib0) + g + 4 * t) * b.ldA + r] = acc[q][t];
-  }
+  input_side_epilogue<2, MPB, NW, false>(b, acc, xs, redx, hp, r0, tid, wave, g, c, true);
+  if (rin) acc_to_global<2, MPB, NW>(acc, b.GW, b.ldA, r, true, wave, g);
 }
 
 template <int MPB, int NW, int KIND>
@@ -355,13 +210,17 @@ static int last_go(dsdgp_ctx* ctx, const LayerFwdArgs& a, const LayerBwdArgs& b,
 
 // shapes this launch exists for (the caller checks the model-level conditions: layer position, likelihood, gradient set)
 int layer_last_built(int Mp, int D_in, int D_out) { return (Mp == 128 || Mp == 256) && D_out == 1 && D_in <= 16; }
-// waves per row block of the instance for this padded inducing count
-int layer_last_waves(int Mp) { return Mp == 128 ? 4 : 8; }
+int layer_last_fusable(const LayerFwdArgs& a, int Mp, int kern_kind, int hyp_rows, int bwd_d_split, int want_E) {
+  const int waves = Mp == 128 ? 4 : 8;      // per row block of the instance: each writes one row of hyp_part, the surplus rows are zeroed
+  return layer_last_built(Mp, a.D_in, a.D_out) && (kern_kind == DSDGP_KERN_RBF || kern_kind == DSDGP_KERN_MATERN52) && hyp_rows >= waves &&
+         a.lik_Y && a.Asave && !a.Csave && !a.F && a.rep == 1 && !a.qmu_ld && a.mean_kind == DSDGP_MEAN_ZERO && a.d_split <= 1 &&
+         bwd_d_split <= 1 && !want_E;
+}
 
+// The backward block's Csave / mean_kind are the forward block's (one LayerState) and the adjoint prologue is an inner layer's: a block
+// that says otherwise was not built for this launch, which reads none of the three
 int layer_last_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, const LayerBwdArgs& b, int Mp, int kern_kind, int hyp_rows) {
-  if (!layer_last_built(Mp, a.D_in, a.D_out) || hyp_rows < layer_last_waves(Mp) || !a.lik_Y || !a.Asave || a.rep != 1 || a.F || b.E ||
-      a.Csave || b.Csave || a.d_split > 1 || b.d_split > 1 || b.up_dF ||
-      a.mean_kind != DSDGP_MEAN_ZERO || b.mean_kind != DSDGP_MEAN_ZERO) {
+  if (!layer_last_fusable(a, Mp, kern_kind, hyp_rows, b.d_split, b.E != nullptr) || b.Csave || b.up_dF || b.mean_kind != a.mean_kind) {
     dsdgp_set_error("layer_last: launch outside the fused last layer's scope (internal)");
     return DSDGP_ERR_UNSUPPORTED;
   }

@@ -5,7 +5,6 @@
 
 #include "layer.hpp"
 
-#define XCH 64
 int layer_fwd_sm_a(dsdgp_ctx*, const LayerFwdArgs&, int, int, int, int);
 int layer_fwd_sm_b(dsdgp_ctx*, const LayerFwdArgs&, int, int, int, int);
 int layer_fwd_sm_c(dsdgp_ctx*, const LayerFwdArgs&, int, int, int, int);

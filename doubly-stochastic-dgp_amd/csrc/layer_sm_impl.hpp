@@ -15,8 +15,6 @@
 
 #include "layer.hpp"
 
-#define XCH 64   // columns of x/l staged per chunk
-
 // Operand order of the chain GEMMs — two variants, chosen per instance (measured, tools/ab_kernels.py):
 //  * D4 (NW >= 8, i.e. Mp >= 512): every weight matrix is read as plain rows W[i][k]: lane (g, c) of the wave that owns output
 //    row-block ib fetches W[16 ib + c][16 kb + 4 g .. + 3] with ONE 32-byte load and feeds its four values to the four MFMAs of
@@ -250,6 +248,18 @@ static inline SmLds sm_lds(int Mp, int D_in, int D_out, int NW, bool wide, int n
   return L;
 }
 
+// Columns [j0, j0 + jn) of x / l of the row block into xs (row stride jn + 1); rows beyond Rin read the last row (clamped).
+template <int NW>
+__device__ __forceinline__ void stage_x_over_l(const double* X, const double* ils, double* xs, int Din, int j0, int jn, int64_t r0,
+                                               int64_t Rin, int tid) {
+  for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
+    const int rr = idx / jn, j = idx % jn;
+    int64_t row = r0 + rr;
+    if (row > Rin - 1) row = Rin - 1;
+    xs[rr * (jn + 1) + j] = X[row * Din + j0 + j] * ils[j0 + j];
+  }
+}
+
 // One staged chunk (jn columns of x / l in xs, row stride jn + 1; Z columns j0 .. j0 + jn) of the MFMA distance form below, any jn:
 // clamped (unconditional) loads, masked afterwards.
 template <int NQ, int MPB, int NW>
@@ -348,12 +358,7 @@ __device__ __forceinline__ void sm_sqdist(const double* __restrict__ zs, const d
   for (int j0 = 0; j0 < Din; j0 += XCH) {
     const int jn = (Din - j0 < XCH) ? Din - j0 : XCH;
     if (j0 > 0) __syncthreads();
-    for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
-      const int rr = idx / jn, j = idx % jn;
-      int64_t row = r0 + rr;
-      if (row > Rin - 1) row = Rin - 1;
-      xs[rr * (jn + 1) + j] = X[row * Din + j0 + j] * ils[j0 + j];
-    }
+    stage_x_over_l<NW>(X, ils, xs, Din, j0, jn, r0, Rin, tid);
     __syncthreads();
     if (act) {
       if ((jn & 15) == 0 && (Din & 3) == 0) {
@@ -387,6 +392,251 @@ __device__ __forceinline__ void sm_sqdist(const double* __restrict__ zs, const d
     }
   }
   sqdist_finish<NQ>(zx, zsq, xx, scratch, wave, g, c, r2);
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Phases shared by the forward chain, the backward chain and the fused last layer (layer_last.hip): ONE copy each.  Lane (g, c) of
+// `wave` holds rows g + 4 t of its Own<MPB, NW> row blocks, column c, in the d4 tiles; `act` = Own<MPB, NW>::active(wave).
+// ------------------------------------------------------------------------------------------------------
+// [X^T ; 1] of this row block for the Z-gradient product of the backward pass (coalesced 128-byte runs along the rows)
+template <int NW>
+__device__ __forceinline__ void store_xt1(const LayerFwdArgs a, int64_t r0, int tid) {
+  const int Din = a.D_in;
+  for (int idx = tid; idx < 16 * (Din + 1); idx += NW * 64) {
+    const int j = idx >> 4, rr = idx & 15;
+    const int64_t r = r0 + rr;
+    if (r < a.ldA) a.XT1[(int64_t)j * a.ldA + r] = (r < a.Rin) ? (j < Din ? a.X[r * Din + j] : 1.0) : 0.0;
+  }
+}
+// Kuf tile (layers.py:184) of row block ib: squared distances -> kernel values -> act, rows beyond M zero
+template <int KIND, bool D4>
+__device__ __forceinline__ void kuf_tile_store(const d4 r2, double s2, int M, double* actb, int ib, int g, int c) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int m = 16 * ib + g + 4 * t;
+    const double kv = kern_val<KIND>(r2[t], s2);      // unconditional: behind `m < M` every exp sat in its own exec branch
+    actb[act_slot<D4>(m) * 16 + c] = (m < M) ? kv : 0.0;
+  }
+}
+// red[wave][c] = sum over the wave's rows of acc^2 (skipped blocks and idle waves hold / publish 0)
+template <int NQ>
+__device__ __forceinline__ void sumsq_partial(const d4 (&acc)[NQ], double* red, int wave, int g, int c, bool act) {
+  double p = 0.0;
+#pragma unroll
+  for (int q = 0; q < NQ; ++q)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) p = fma(acc[q][t], acc[q][t], p);
+  p = sum_groups(p);
+  if (g == 0) red[wave * 16 + c] = act ? p : 0.0;
+}
+// accumulators -> the activation buffer, in place (the caller has passed the barrier behind the last reader)
+template <bool D4, int NQ, int MPB, int NW>
+__device__ __forceinline__ void acc_to_act(const d4 (&acc)[NQ], double* actb, int wave, int g, int c) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int ib = Own<MPB, NW>::ib(wave, q);
+    if (Own<MPB, NW>::skip(ib)) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) actb[out_slot<D4>(ib, g, t) * 16 + c] = acc[q][t];
+  }
+}
+// accumulators -> column r of a global M-major (Mp x ld) buffer; `keep` false stores zeros (pad columns of Asave)
+template <int NQ, int MPB, int NW>
+__device__ __forceinline__ void acc_to_global(const d4 (&acc)[NQ], double* dst, int64_t ld, int64_t r, bool keep, int wave, int g) {
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    const int ib = Own<MPB, NW>::ib(wave, q);
+    if (Own<MPB, NW>::skip(ib)) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) dst[(int64_t)(16 * ib + g + 4 * t) * ld + r] = keep ? acc[q][t] : 0.0;
+  }
+}
+// this wave's row of hyp_part ([sum kbar k / s2 | sum vbar | D_in lengthscale partials]); `hyp_rows` rows per row block
+__device__ __forceinline__ double* hyp_part_row(const LayerBwdArgs a, int hyp_rows, int wave) {
+  return a.hyp_part + ((int64_t)blockIdx.x * hyp_rows + wave) * (a.D_in + 2);
+}
+// Kernel recompute of one element: w = kbar dk/dr2 (0 where !ok: rows beyond M, data rows beyond Rin), svar += kbar k.  Per element,
+// inside the caller's loop over its tiles: the backward chain forms kbar from b, gsum and a there (and stores E), the fused launch has
+// it in its accumulators — and the device code of both keeps the order it had (a whole-tile form cost the white wide Mp = 224
+// backward instance three registers and with them an occupancy step).
+template <int KIND>
+__device__ __forceinline__ double kbar_to_w(double kbar, double r2, double s2, bool ok, double& svar) {
+  double k, dk;
+  kern_val_grad<KIND>(r2, s2, k, dk);
+  svar += ok ? kbar * k : 0.0;
+  return ok ? kbar * dk : 0.0;
+}
+// ... and the head of the wave's hyp_part row: the kernel-variance partial sum kbar k / s2 and sum_d vbar_d (`gsum`, this data row's)
+__device__ __forceinline__ void hyp_head_store(double svar, double gsum, double s2, bool rvalid, double* hp, int wave, int lane) {
+  svar = sum_wave(svar);
+  const double gk = sum_wave((rvalid && (lane >> 4) == 0 && wave == 0) ? gsum : 0.0);
+  if (lane == 0) {
+    hp[0] = svar / s2;
+    hp[1] = gk;
+  }
+}
+// Input side of the reverse pass, from w = kbar dk/dr2 (rows beyond M and skipped blocks hold 0): lengthscale partials -> hp[2 ..],
+// d loss / d X -> dX, or the previous layer's transposed adjoints MBp / VBp with their pad rows; chunked over D_in like the distance
+// computation.  xs holds x / l on entry (narrow instances) or is re-staged per chunk (WIDE); redx: [NW][chunk][16].
+// (layer_gemm.hip has its own input-side epilogue: another thread layout — whole 128-row tiles, no wave ownership — it stays apart.)
+template <int NQ, int MPB, int NW, bool WIDE>
+__device__ __forceinline__ void input_side_epilogue(const LayerBwdArgs a, const d4 (&w)[NQ], double* xs, double* redx, double* hp,
+                                                    int64_t r0, int tid, int wave, int g, int c, bool act) {
+  const int Din = a.D_in, Dout = a.D_out;
+  const double* __restrict__ zs = a.Zs;
+  const double* ils = a.hyp + HYP_ILS;
+  for (int j0 = 0; j0 < Din; j0 += XCH) {
+    const int jn = (Din - j0 < XCH) ? Din - j0 : XCH;
+    if (WIDE) {   // single-chunk kernels: xs still holds x/l staged above
+      __syncthreads();
+      stage_x_over_l<NW>(a.X, ils, xs, Din, j0, jn, r0, a.Rin, tid);
+      __syncthreads();
+    }
+    // epilogue operands of this thread's item (one item per thread when 16 jn <= threads): requested now, they arrive during the
+    // reductions below instead of after the barrier
+    const bool single = 16 * jn <= NW * 64;
+    double pre_mb = 0.0, pre_z = 0.0, pre_var = 1.0;
+    if ((a.dX || a.MBp) && single && tid < 16 * jn) {
+      const int j = a.MBp ? tid / 16 : tid % jn, cc = a.MBp ? tid % 16 : tid / jn;
+      const int64_t row = r0 + cc;
+      if (row < a.Rin) {
+        if (a.mean_kind == DSDGP_MEAN_IDENTITY) pre_mb = a.MB[(int64_t)(j0 + j) * a.ldA + row];
+        const int d = j0 + j - a.prop;
+        if (a.MBp && d >= 0) {
+          pre_z = a.zp[(row / a.n_inner) * a.zp_s + (row % a.n_inner) * a.zp_n + d * a.zp_d];
+          pre_var = a.varp[row * a.Dp + d];
+        }
+      }
+    }
+    // The sums over this wave's inducing rows run on the MFMA pipe, 16 input dimensions at a time.
+    //   WZ[j][c] = sum_m z[m][j] w[m][c],  Z2[j][c] = sum_m z[m][j]^2 w[m][c]   (A = Zs^T tile: lane (g, c) loads row 16 ib + g + 4 t,
+    //   dimension c of the group — 128-byte runs; B = w, which sits in the accumulator layout = the B layout of k-steps t)
+    //   d X partial: sum_m w (x - z) = x W1 - WZ          lengthscale partial: sum_m,c w (x - z)^2 = sum_c (x^2 W1 - 2 x WZ + Z2)
+    // with W1[c] = sum_m w[m][c].  One element-by-element pass per dimension (16 L2 loads, two cross-lane reductions) took
+    // 1.93 M of the 5.2 M clocks of the 784-dimensional first layer of config 4 and 22 K of the 59 K clocks of a D_out = 1 workgroup
+    // of config 2 (profiles/r02_chain_phases.txt); this form 0.41 M and 12 K.
+    double w1 = 0.0;
+    if (act) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) w1 += w[q][t];           // rows beyond M and skipped blocks hold 0
+    }
+    w1 = sum_groups(w1);
+    for (int kk = 0; kk < jn; kk += 16) {
+      d4 wz = (d4){0, 0, 0, 0}, z2 = (d4){0, 0, 0, 0};
+      if (act) {
+        const int jc = (kk + c < jn) ? kk + c : jn - 1;       // clamped (unconditional) loads; dimensions past jn are dropped below
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const int ib = Own<MPB, NW>::ib(wave, q);
+          if (Own<MPB, NW>::skip(ib)) continue;
+          double zv[4];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) zv[t] = zs[(int64_t)(16 * ib + g + 4 * t) * Din + j0 + jc];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) {
+            wz = mfma_f64(zv[t], w[q][t], wz);
+            z2 = mfma_f64(zv[t] * zv[t], w[q][t], z2);
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int j = kk + g + 4 * t;                           // accumulator row = dimension kk + g + 4 t, column c
+        const bool in = j < jn;
+        const double xv = xs[c * (jn + 1) + (in ? j : jn - 1)];
+        if ((a.dX || a.MBp) && in) redx[(wave * jn + j) * 16 + c] = act ? fma(xv, w1, -wz[t]) : 0.0;
+        double sl = act ? fma(xv * xv, w1, fma(-2.0 * xv, wz[t], z2[t])) : 0.0;
+        sl += dpp_or_zero<0x111, 0xf>(sl);                      // sum over the 16 columns of this row of lanes (-> lane c = 15)
+        sl += dpp_or_zero<0x112, 0xf>(sl);
+        sl += dpp_or_zero<0x114, 0xf>(sl);
+        sl += dpp_or_zero<0x118, 0xf>(sl);
+        if (c == 15 && in) hp[2 + j0 + j] = -2.0 * ils[j0 + j] * sl;
+      }
+    }
+    if (a.dX || a.MBp) {
+      __syncthreads();
+      for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
+        // dX is row-major (j fastest); the fused transposed adjoints are M-major (row fastest): keep the stores coalesced
+        const int j = a.MBp ? idx / 16 : idx % jn, cc = a.MBp ? idx % 16 : idx / jn;
+        const int64_t row = r0 + cc;
+        if (row < a.Rin) {
+          double sx = 0.0;
+#pragma unroll
+          for (int wv = 0; wv < NW; ++wv) sx += redx[(wv * jn + j) * 16 + cc];
+          double dx = 2.0 * ils[j0 + j] * sx;
+          if (a.mean_kind == DSDGP_MEAN_IDENTITY) {
+            dx += single ? pre_mb : a.MB[(int64_t)(j0 + j) * a.ldA + row];
+          } else if (a.mean_kind == DSDGP_MEAN_LINEAR) {
+            for (int d = 0; d < Dout; ++d) dx = fma(a.mean_A[(int64_t)(j0 + j) * Dout + d], a.MB[(int64_t)d * a.ldA + row], dx);
+          }
+          if (a.MBp) {
+            const int d = j0 + j - a.prop;
+            if (d >= 0) {
+              const double zv = single ? pre_z : a.zp[(row / a.n_inner) * a.zp_s + (row % a.n_inner) * a.zp_n + d * a.zp_d];
+              const double vv = single ? pre_var : a.varp[row * a.Dp + d];
+              a.MBp[(int64_t)d * a.ldA + row] = dx;
+              a.VBp[(int64_t)d * a.ldA + row] = dx * zv * 0.5 * rsqrt(vv + a.jitter);
+            }
+          } else {
+            a.dX[row * Din + j0 + j] = dx;
+          }
+        } else if (a.MBp && row < a.ldA && j0 + j >= a.prop) {
+          a.MBp[(int64_t)(j0 + j - a.prop) * a.ldA + row] = 0.0;
+          a.VBp[(int64_t)(j0 + j - a.prop) * a.ldA + row] = 0.0;
+        }
+      }
+    }
+  }
+}
+// Adjoint prologue of the backward chain: upstream adjoints of this row block from the adjoint of the next layer's input (see
+// LayerBwdArgs::up_dF).  (row, output) pairs x C chunks of the rep samples over the threads, partials through the (still unused)
+// reduction scratch `redx` (`scratch` doubles), fixed summation order.
+template <int NW>
+__device__ __forceinline__ void adjoint_prologue(const LayerBwdArgs a, double* redx, int scratch, int64_t r0, int tid) {
+  const int Dout = a.D_out;
+  const int npair = 16 * Dout, T = NW * 64;
+  const int cap = scratch / (2 * npair);
+  int C = T / npair;
+  if (C > a.up_rep) C = a.up_rep;
+  if (C > cap) C = cap;
+  if (C < 1) C = 1;
+  for (int e = tid; e < npair * C; e += T) {
+    const int pair = e % npair, ch = e / npair;
+    const int rr = pair / Dout, d = pair - rr * Dout;
+    const int64_t rw = r0 + rr;
+    double ms = 0.0, vs = 0.0;
+    if (rw < a.Rin) {
+      const int s_lo = ch * a.up_rep / C, s_hi = (ch + 1) * a.up_rep / C;
+      for (int s = s_lo; s < s_hi; ++s) {
+        const int64_t orow = (int64_t)s * a.Rin + rw;
+        const double f = a.up_dF[orow * a.up_ld + a.up_off + d];
+        ms += f;
+        vs = fma(f, a.up_z[(orow / a.up_n_inner) * a.up_zs + (orow % a.up_n_inner) * a.up_zn + d * a.up_zd], vs);
+      }
+    }
+    redx[2 * e] = ms;
+    redx[2 * e + 1] = vs;
+  }
+  __syncthreads();
+  for (int pair = tid; pair < npair; pair += T) {
+    const int rr = pair / Dout, d = pair - rr * Dout;
+    const int64_t rw = r0 + rr;
+    double ms = 0.0, vs = 0.0;
+    for (int ch = 0; ch < C; ++ch) {
+      ms += redx[2 * (ch * npair + pair)];
+      vs += redx[2 * (ch * npair + pair) + 1];
+    }
+    if (rw < a.Rin) {
+      a.MBw[(int64_t)d * a.ldA + rw] = ms;
+      a.VBw[(int64_t)d * a.ldA + rw] = vs * 0.5 * rsqrt(a.up_var[rw * Dout + d] + a.up_jitter);
+    } else if (rw < a.ldA) {
+      a.MBw[(int64_t)d * a.ldA + rw] = 0.0;
+      a.VBw[(int64_t)d * a.ldA + rw] = 0.0;
+    }
+  }
+  __syncthreads();       // (waits for the stores; the lines of this row block are read below by this workgroup only)
 }
 
 // debug aid of the phase-clock launches.  The stamps are s_memrealtime (constant 100 MHz, one time base for the whole chip): s_memtime
@@ -454,54 +704,26 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves<MPB, NW, WIDE, LIK>())) voi
   FWD_STAMP(0);
 
   // [X^T ; 1] of this block for the Z-gradient product of the backward pass (coalesced 128-byte runs along the rows)
-  if (a.XT1 && blockIdx.y == 0) {
-    for (int idx = tid; idx < 16 * (Din + 1); idx += NW * 64) {
-      const int j = idx >> 4, rr = idx & 15;
-      const int64_t r = r0 + rr;
-      if (r < a.ldA) a.XT1[(int64_t)j * a.ldA + r] = (r < a.Rin) ? (j < Din ? a.X[r * Din + j] : 1.0) : 0.0;
-    }
-  }
+  if (a.XT1 && blockIdx.y == 0) store_xt1<NW>(a, r0, tid);
   // --- Kuf tile (layers.py:184): own row-blocks -> act
-  if constexpr (!WIDE) {
-    // D_in <= XCH: one staging pass, distances accumulated element by element (fewest live registers)
-    for (int idx = tid; idx < 16 * Din; idx += NW * 64) {
-      const int rr = idx / Din, j = idx % Din;
-      int64_t row = r0 + rr;
-      if (row > a.Rin - 1) row = a.Rin - 1;
-      xs[rr * (Din + 1) + j] = a.X[row * Din + j] * ils[j];
-    }
-    __syncthreads();
-    // distances on the MFMA pipe (|z|^2 + |x|^2 - 2 z.x, see sm_sqdist): the element-by-element form — one L1 / L2 load and one FMA per
-    // (inducing row, data row, dimension) and lane — was 17 K of the 61 K clocks of a D_out = 1 workgroup at config 2
+  {
     d4 r2[NQ];
-    sqdist_narrow<NQ, MPB, NW>(a.Zs, xs, Din, wave, g, c, act, red_s1, r2);
+    if constexpr (!WIDE) {
+      // D_in <= XCH: one staging pass
+      stage_x_over_l<NW>(a.X, ils, xs, Din, 0, Din, r0, a.Rin, tid);
+      __syncthreads();
+      // distances on the MFMA pipe (|z|^2 + |x|^2 - 2 z.x, see sm_sqdist): the element-by-element form — one L1 / L2 load and one FMA
+      // per (inducing row, data row, dimension) and lane — was 17 K of the 61 K clocks of a D_out = 1 workgroup at config 2
+      sqdist_narrow<NQ, MPB, NW>(a.Zs, xs, Din, wave, g, c, act, red_s1, r2);
+    } else {
+      sm_sqdist<NQ, MPB, NW>(a.Zs, a.X, ils, xs, Din, r0, a.Rin, tid, wave, g, c, act, red_s1, r2);
+    }
     if (act) {
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const int ib = Own<MPB, NW>::ib(wave, q);
         if (Own<MPB, NW>::skip(ib)) continue;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int m = 16 * ib + g + 4 * t;
-          const double kv = kern_val<KIND>(r2[q][t], s2);      // unconditional: behind `m < M` every exp sat in its own exec branch
-          actb[act_slot<D4>(m) * 16 + c] = (m < a.M) ? kv : 0.0;
-        }
-      }
-    }
-  } else {
-    d4 r2[NQ];
-    sm_sqdist<NQ, MPB, NW>(a.Zs, a.X, ils, xs, Din, r0, a.Rin, tid, wave, g, c, act, red_s1, r2);
-    if (act) {
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        const int ib = Own<MPB, NW>::ib(wave, q);
-        if (Own<MPB, NW>::skip(ib)) continue;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int m = 16 * ib + g + 4 * t;
-          const double kv = kern_val<KIND>(r2[q][t], s2);      // unconditional: behind `m < M` every exp sat in its own exec branch
-          actb[act_slot<D4>(m) * 16 + c] = (m < a.M) ? kv : 0.0;
-        }
+        kuf_tile_store<KIND, D4>(r2[q], s2, a.M, actb, ib, g, c);
       }
     }
   }
@@ -526,16 +748,10 @@ __global__ __launch_bounds__(NW * 64, (fwd_min_waves<MPB, NW, WIDE, LIK>())) voi
       }
     }
   }
-  {
-    double p = 0.0;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-#pragma unroll
-      for (int t = 0; t < 4; ++t) p = fma(acc[q][t], acc[q][t], p);
-    p = sum_groups(p);
-    if (g == 0) red_s1[wave * 16 + c] = act ? p : 0.0;
-  }
+  sumsq_partial<NQ>(acc, red_s1, wave, g, c, act);
   __syncthreads();   // every wave has finished reading k before a1 overwrites it in place
+  // (this store and the one of `a` below stay inline, not acc_to_act: with the call the Mp = 64 wide likelihood instance spills 8 bytes
+  // and the white Mp = 384 instances drop from 174 / 189 to 150 / 165 VGPRs, another occupancy step — profiles/chain_phases_refactor.md)
   if (act) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -786,6 +1002,9 @@ __global__ __launch_bounds__(NW * 64, (bwd_min_waves<MPB, NW, WIDE, CS>())) void
   constexpr bool D4 = (MPB > 16);
   constexpr bool ILV = D4 || (MPB >= 16);   // interleave the NQ row-block chains inside the k loop (measured: helps from NQ = 4)
   const int Din = a.D_in, Dout = a.D_out;
+  // (tid >> 6, not DS_WAVE_ID as in the other two kernels: not tried in this change — the index moves to an SGPR and with it the address
+  // arithmetic of every instance, on top of the register differences profiles/chain_phases_refactor.md already lists; the one
+  // run-time k range below, the white paired product, reads the index through the macro itself)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, c = lane & 15;
   const double* __restrict__ zs = a.Zs;
@@ -799,51 +1018,7 @@ __global__ __launch_bounds__(NW * 64, (bwd_min_waves<MPB, NW, WIDE, CS>())) void
   const int64_t r = r0 + c;
   const bool rin = r < a.ldA, rvalid = r < a.Rin;
   BWD_STAMP(0);
-  if (a.up_dF) {
-    // upstream adjoints of this row block from the adjoint of the next layer's input (see LayerBwdArgs::up_dF).  (row, output) pairs
-    // x C chunks of the rep samples over the threads, partials through the (still unused) reduction scratch, fixed summation order.
-    const int npair = 16 * Dout, T = NW * 64;
-    const int cap = (L.total - L.red) / (2 * npair);
-    int C = T / npair;
-    if (C > a.up_rep) C = a.up_rep;
-    if (C > cap) C = cap;
-    if (C < 1) C = 1;
-    for (int e = tid; e < npair * C; e += T) {
-      const int pair = e % npair, ch = e / npair;
-      const int rr = pair / Dout, d = pair - rr * Dout;
-      const int64_t rw = r0 + rr;
-      double ms = 0.0, vs = 0.0;
-      if (rw < a.Rin) {
-        const int s_lo = ch * a.up_rep / C, s_hi = (ch + 1) * a.up_rep / C;
-        for (int s = s_lo; s < s_hi; ++s) {
-          const int64_t orow = (int64_t)s * a.Rin + rw;
-          const double f = a.up_dF[orow * a.up_ld + a.up_off + d];
-          ms += f;
-          vs = fma(f, a.up_z[(orow / a.up_n_inner) * a.up_zs + (orow % a.up_n_inner) * a.up_zn + d * a.up_zd], vs);
-        }
-      }
-      redx[2 * e] = ms;
-      redx[2 * e + 1] = vs;
-    }
-    __syncthreads();
-    for (int pair = tid; pair < npair; pair += T) {
-      const int rr = pair / Dout, d = pair - rr * Dout;
-      const int64_t rw = r0 + rr;
-      double ms = 0.0, vs = 0.0;
-      for (int ch = 0; ch < C; ++ch) {
-        ms += redx[2 * (ch * npair + pair)];
-        vs += redx[2 * (ch * npair + pair) + 1];
-      }
-      if (rw < a.Rin) {
-        a.MBw[(int64_t)d * a.ldA + rw] = ms;
-        a.VBw[(int64_t)d * a.ldA + rw] = vs * 0.5 * rsqrt(a.up_var[rw * Dout + d] + a.up_jitter);
-      } else if (rw < a.ldA) {
-        a.MBw[(int64_t)d * a.ldA + rw] = 0.0;
-        a.VBw[(int64_t)d * a.ldA + rw] = 0.0;
-      }
-    }
-    __syncthreads();       // (waits for the stores; the lines of this row block are read below by this workgroup only)
-  }
+  if (a.up_dF) adjoint_prologue<NW>(a, redx, L.total - L.red, r0, tid);
   d4 av[NQ], acc[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
@@ -866,14 +1041,7 @@ __global__ __launch_bounds__(NW * 64, (bwd_min_waves<MPB, NW, WIDE, CS>())) void
   }
   // x / l of this row block (needed for the kernel recompute after the chains): requested now so that its latency hides behind them.
   // xs is not touched by anything in between and every path below passes a barrier before reading it.
-  if constexpr (!WIDE) {
-    for (int idx = tid; idx < 16 * Din; idx += NW * 64) {
-      const int rr = idx / Din, j = idx % Din;
-      int64_t row = r0 + rr;
-      if (row > a.Rin - 1) row = a.Rin - 1;
-      xs[rr * (Din + 1) + j] = a.X[row * Din + j] * ils[j];
-    }
-  }
+  if constexpr (!WIDE) stage_x_over_l<NW>(a.X, ils, xs, Din, 0, Din, r0, a.Rin, tid);
   // the first two k-steps of the mean part's upstream adjoints, for the same reason
   const double bv0l = a.MB[(int64_t)g * a.ldA + (rin ? r : 0)];
   const double bv1l = a.MB[(int64_t)(a.DP4 > 4 ? 4 + g : g) * a.ldA + (rin ? r : 0)];
@@ -1211,146 +1379,114 @@ __global__ __launch_bounds__(NW * 64, (bwd_min_waves<MPB, NW, WIDE, CS>())) void
         const int m = 16 * ib + g + 4 * t;
         const double e = WHITE ? bb[q][t] : bb[q][t] - gsum * av[q][t];
         const double kbar = WHITE ? e : e - gsum * av[q][t];
-        const double r2v = r2[q][t];
-        double k, dk;
-        kern_val_grad<KIND>(r2v, s2, k, dk);
-        const bool ok = rvalid && (m < a.M);
-        svar += ok ? kbar * k : 0.0;
-        const double w = ok ? kbar * dk : 0.0;
-        bb[q][t] = w;
+        bb[q][t] = kbar_to_w<KIND>(kbar, r2[q][t], s2, rvalid && (m < a.M), svar);
         // NULL: d loss / d Ku is assembled from the P_d (model.hip, alg_g).  GW is stored at the end of the kernel: a store issued here
         // makes the Z loads of the reductions below wait for its write acknowledgement (vmcnt retires in order).
         if (rin && a.E) a.E[(int64_t)m * a.ldA + r] = e;
       }
     }
   }
-  BWD_STAMP(6);      // kernel recompute, E / GW stores issued
-  svar = sum_wave(svar);
-  const double gk = sum_wave((rvalid && g == 0 && wave == 0) ? gsum : 0.0);
-  double* hp = a.hyp_part + ((int64_t)blockIdx.x * NW + wave) * (Din + 2);
-  if (lane == 0) {
-    hp[0] = svar / s2;
-    hp[1] = gk;
-  }
-  // lengthscale partials and d loss / d X, chunked over D_in like the distance computation
-  for (int j0 = 0; j0 < Din; j0 += XCH) {
-    const int jn = (Din - j0 < XCH) ? Din - j0 : XCH;
-    if (WIDE) {   // single-chunk kernels: xs still holds x/l staged above
-      __syncthreads();
-      for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
-        const int rr = idx / jn, j = idx % jn;
-        int64_t row = r0 + rr;
-        if (row > a.Rin - 1) row = a.Rin - 1;
-        xs[rr * (jn + 1) + j] = a.X[row * Din + j0 + j] * ils[j0 + j];
-      }
-      __syncthreads();
-    }
-    // epilogue operands of this thread's item (one item per thread when 16 jn <= threads): requested now, they arrive during the
-    // reductions below instead of after the barrier
-    const bool single = 16 * jn <= NW * 64;
-    double pre_mb = 0.0, pre_z = 0.0, pre_var = 1.0;
-    if ((a.dX || a.MBp) && single && tid < 16 * jn) {
-      const int j = a.MBp ? tid / 16 : tid % jn, cc = a.MBp ? tid % 16 : tid / jn;
-      const int64_t row = r0 + cc;
-      if (row < a.Rin) {
-        if (a.mean_kind == DSDGP_MEAN_IDENTITY) pre_mb = a.MB[(int64_t)(j0 + j) * a.ldA + row];
-        const int d = j0 + j - a.prop;
-        if (a.MBp && d >= 0) {
-          pre_z = a.zp[(row / a.n_inner) * a.zp_s + (row % a.n_inner) * a.zp_n + d * a.zp_d];
-          pre_var = a.varp[row * a.Dp + d];
-        }
-      }
-    }
-    // The sums over this wave's inducing rows run on the MFMA pipe, 16 input dimensions at a time.
-    //   WZ[j][c] = sum_m z[m][j] w[m][c],  Z2[j][c] = sum_m z[m][j]^2 w[m][c]   (A = Zs^T tile: lane (g, c) loads row 16 ib + g + 4 t,
-    //   dimension c of the group — 128-byte runs; B = w, which sits in the accumulator layout = the B layout of k-steps t)
-    //   d X partial: sum_m w (x - z) = x W1 - WZ          lengthscale partial: sum_m,c w (x - z)^2 = sum_c (x^2 W1 - 2 x WZ + Z2)
-    // with W1[c] = sum_m w[m][c].  One element-by-element pass per dimension (16 L2 loads, two cross-lane reductions) took
-    // 1.93 M of the 5.2 M clocks of the 784-dimensional first layer of config 4 and 22 K of the 59 K clocks of a D_out = 1 workgroup
-    // of config 2 (profiles/r02_chain_phases.txt); this form 0.41 M and 12 K.
-    double w1 = 0.0;
-    if (act) {
-#pragma unroll
-      for (int q = 0; q < NQ; ++q)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) w1 += bb[q][t];           // rows beyond M and skipped blocks hold 0
-    }
-    w1 = sum_groups(w1);
-    for (int kk = 0; kk < jn; kk += 16) {
-      d4 wz = (d4){0, 0, 0, 0}, z2 = (d4){0, 0, 0, 0};
-      if (act) {
-        const int jc = (kk + c < jn) ? kk + c : jn - 1;       // clamped (unconditional) loads; dimensions past jn are dropped below
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          const int ib = Own<MPB, NW>::ib(wave, q);
-          if (Own<MPB, NW>::skip(ib)) continue;
-          double zv[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) zv[t] = zs[(int64_t)(16 * ib + g + 4 * t) * Din + j0 + jc];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            wz = mfma_f64(zv[t], bb[q][t], wz);
-            z2 = mfma_f64(zv[t] * zv[t], bb[q][t], z2);
-          }
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int j = kk + g + 4 * t;                           // accumulator row = dimension kk + g + 4 t, column c
-        const bool in = j < jn;
-        const double xv = xs[c * (jn + 1) + (in ? j : jn - 1)];
-        if ((a.dX || a.MBp) && in) redx[(wave * jn + j) * 16 + c] = act ? fma(xv, w1, -wz[t]) : 0.0;
-        double sl = act ? fma(xv * xv, w1, fma(-2.0 * xv, wz[t], z2[t])) : 0.0;
-        sl += dpp_or_zero<0x111, 0xf>(sl);                      // sum over the 16 columns of this row of lanes (-> lane c = 15)
-        sl += dpp_or_zero<0x112, 0xf>(sl);
-        sl += dpp_or_zero<0x114, 0xf>(sl);
-        sl += dpp_or_zero<0x118, 0xf>(sl);
-        if (c == 15 && in) hp[2 + j0 + j] = -2.0 * ils[j0 + j] * sl;
-      }
-    }
-    if (a.dX || a.MBp) {
-      __syncthreads();
-      for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
-        // dX is row-major (j fastest); the fused transposed adjoints are M-major (row fastest): keep the stores coalesced
-        const int j = a.MBp ? idx / 16 : idx % jn, cc = a.MBp ? idx % 16 : idx / jn;
+  BWD_STAMP(6);      // kernel recompute, E stores issued
+  double* hp = hyp_part_row(a, NW, wave);
+  hyp_head_store(svar, gsum, s2, rvalid, hp, wave, lane);
+  // Input side: input_side_epilogue, for every instance but one.  The 4-wave Mp = 128 narrow instance (pinned at 96 VGPRs, see
+  // bwd_min_waves) spills 48 / 56 bytes (RBF / Matern52) instead of 40 / 44 with the call, whatever the form of its parameters, and
+  // the backward chains of config 2 then take 156.2 instead of 153.9 us per step (profiles/chain_phases_refactor.md): it keeps
+  // the same code inline (xs holds x / l, no re-staging; the function carries the comments).  A change to the function goes in here too.
+  if constexpr (!(NW == 4 && MPB == 8 && !WIDE && !CS)) {
+    input_side_epilogue<NQ, MPB, NW, WIDE>(a, bb, xs, redx, hp, r0, tid, wave, g, c, act);
+  } else {
+    for (int j0 = 0; j0 < Din; j0 += XCH) {
+      const int jn = (Din - j0 < XCH) ? Din - j0 : XCH;
+      const bool single = 16 * jn <= NW * 64;
+      double pre_mb = 0.0, pre_z = 0.0, pre_var = 1.0;
+      if ((a.dX || a.MBp) && single && tid < 16 * jn) {
+        const int j = a.MBp ? tid / 16 : tid % jn, cc = a.MBp ? tid % 16 : tid / jn;
         const int64_t row = r0 + cc;
         if (row < a.Rin) {
-          double sx = 0.0;
+          if (a.mean_kind == DSDGP_MEAN_IDENTITY) pre_mb = a.MB[(int64_t)(j0 + j) * a.ldA + row];
+          const int d = j0 + j - a.prop;
+          if (a.MBp && d >= 0) {
+            pre_z = a.zp[(row / a.n_inner) * a.zp_s + (row % a.n_inner) * a.zp_n + d * a.zp_d];
+            pre_var = a.varp[row * a.Dp + d];
+          }
+        }
+      }
+      double w1 = 0.0;
+      if (act) {
 #pragma unroll
-          for (int w = 0; w < NW; ++w) sx += redx[(w * jn + j) * 16 + cc];
-          double dx = 2.0 * ils[j0 + j] * sx;
-          if (a.mean_kind == DSDGP_MEAN_IDENTITY) {
-            dx += single ? pre_mb : a.MB[(int64_t)(j0 + j) * a.ldA + row];
-          } else if (a.mean_kind == DSDGP_MEAN_LINEAR) {
-            for (int d = 0; d < Dout; ++d) dx = fma(a.mean_A[(int64_t)(j0 + j) * Dout + d], a.MB[(int64_t)d * a.ldA + row], dx);
-          }
-          if (a.MBp) {
-            const int d = j0 + j - a.prop;
-            if (d >= 0) {
-              const double zv = single ? pre_z : a.zp[(row / a.n_inner) * a.zp_s + (row % a.n_inner) * a.zp_n + d * a.zp_d];
-              const double vv = single ? pre_var : a.varp[row * a.Dp + d];
-              a.MBp[(int64_t)d * a.ldA + row] = dx;
-              a.VBp[(int64_t)d * a.ldA + row] = dx * zv * 0.5 * rsqrt(vv + a.jitter);
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+          for (int t = 0; t < 4; ++t) w1 += bb[q][t];           // rows beyond M and skipped blocks hold 0
+      }
+      w1 = sum_groups(w1);
+      for (int kk = 0; kk < jn; kk += 16) {
+        d4 wz = (d4){0, 0, 0, 0}, z2 = (d4){0, 0, 0, 0};
+        if (act) {
+          const int jc = (kk + c < jn) ? kk + c : jn - 1;       // clamped (unconditional) loads; dimensions past jn are dropped below
+#pragma unroll
+          for (int q = 0; q < NQ; ++q) {
+            const int ib = Own<MPB, NW>::ib(wave, q);
+            if (Own<MPB, NW>::skip(ib)) continue;
+            double zv[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) zv[t] = zs[(int64_t)(16 * ib + g + 4 * t) * Din + j0 + jc];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              wz = mfma_f64(zv[t], bb[q][t], wz);
+              z2 = mfma_f64(zv[t] * zv[t], bb[q][t], z2);
             }
-          } else {
-            a.dX[row * Din + j0 + j] = dx;
           }
-        } else if (a.MBp && row < a.ldA && j0 + j >= a.prop) {
-          a.MBp[(int64_t)(j0 + j - a.prop) * a.ldA + row] = 0.0;
-          a.VBp[(int64_t)(j0 + j - a.prop) * a.ldA + row] = 0.0;
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int j = kk + g + 4 * t;                           // accumulator row = dimension kk + g + 4 t, column c
+          const bool in = j < jn;
+          const double xv = xs[c * (jn + 1) + (in ? j : jn - 1)];
+          if ((a.dX || a.MBp) && in) redx[(wave * jn + j) * 16 + c] = act ? fma(xv, w1, -wz[t]) : 0.0;
+          double sl = act ? fma(xv * xv, w1, fma(-2.0 * xv, wz[t], z2[t])) : 0.0;
+          sl += dpp_or_zero<0x111, 0xf>(sl);                      // sum over the 16 columns of this row of lanes (-> lane c = 15)
+          sl += dpp_or_zero<0x112, 0xf>(sl);
+          sl += dpp_or_zero<0x114, 0xf>(sl);
+          sl += dpp_or_zero<0x118, 0xf>(sl);
+          if (c == 15 && in) hp[2 + j0 + j] = -2.0 * ils[j0 + j] * sl;
+        }
+      }
+      if (a.dX || a.MBp) {
+        __syncthreads();
+        for (int idx = tid; idx < 16 * jn; idx += NW * 64) {
+          const int j = a.MBp ? idx / 16 : idx % jn, cc = a.MBp ? idx % 16 : idx / jn;
+          const int64_t row = r0 + cc;
+          if (row < a.Rin) {
+            double sx = 0.0;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sx += redx[(w * jn + j) * 16 + cc];
+            double dx = 2.0 * ils[j0 + j] * sx;
+            if (a.mean_kind == DSDGP_MEAN_IDENTITY) {
+              dx += single ? pre_mb : a.MB[(int64_t)(j0 + j) * a.ldA + row];
+            } else if (a.mean_kind == DSDGP_MEAN_LINEAR) {
+              for (int d = 0; d < Dout; ++d) dx = fma(a.mean_A[(int64_t)(j0 + j) * Dout + d], a.MB[(int64_t)d * a.ldA + row], dx);
+            }
+            if (a.MBp) {
+              const int d = j0 + j - a.prop;
+              if (d >= 0) {
+                const double zv = single ? pre_z : a.zp[(row / a.n_inner) * a.zp_s + (row % a.n_inner) * a.zp_n + d * a.zp_d];
+                const double vv = single ? pre_var : a.varp[row * a.Dp + d];
+                a.MBp[(int64_t)d * a.ldA + row] = dx;
+                a.VBp[(int64_t)d * a.ldA + row] = dx * zv * 0.5 * rsqrt(vv + a.jitter);
+              }
+            } else {
+              a.dX[row * Din + j0 + j] = dx;
+            }
+          } else if (a.MBp && row < a.ldA && j0 + j >= a.prop) {
+            a.MBp[(int64_t)(j0 + j - a.prop) * a.ldA + row] = 0.0;
+            a.VBp[(int64_t)(j0 + j - a.prop) * a.ldA + row] = 0.0;
+          }
         }
       }
     }
   }
-  if (act && rin) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const int ib = Own<MPB, NW>::ib(wave, q);
-      if (Own<MPB, NW>::skip(ib)) continue;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) a.GW[(int64_t)(16 * ib + g + 4 * t) * a.ldA + r] = bb[q][t];
-    }
-  }
+  if (act && rin) acc_to_global<NQ, MPB, NW>(bb, a.GW, a.ldA, r, true, wave, g);
   BWD_STAMP(7);      // hyper-parameter partials, dX / transposed adjoints, GW
 }
 

@@ -197,20 +197,27 @@ static int randn_async(dsdgp_ctx* ctx, uint64_t seed, uint64_t stream, int64_t c
   return DSDGP_OK;
 }
 
+// LayerBwdArgs::d_split of a backward chain over nblk row blocks. Few of them (the N-row first layer, small shards): up to four
+// workgroups per row block share the d-loop. Only from Mp = 512 (bwd_split = 2 forces it everywhere, 0 disables): every workgroup of a
+// split repeats the chain's prologue and epilogue phases. 63-row-block first layer of config 2 (M = 128): +57 us with the
+// __threadfence() hand-over of round 2, still +6 us per step with the fence-free sc1 hand-over of round 3 (cutting the upper layer's
+// weight-gradient task list over both streams to use the shortened chain: +10..+20 us); -0.9 ms on the 32-row-block, 30-output first
+// layer of config 4 (M = 512)
+static int bwd_d_split(const dsdgp_model* m, const LayerState& St, int64_t nblk) {
+  const bool want = m->force.bwd_split >= 2 || (m->force.bwd_split == 1 && St.dev.Mp > 256);
+  return (want && St.bpart) ? chain_d_split(nblk, St.dev.D_out) : 1;
+}
 // Whether the last layer's forward chain, the Gaussian likelihood and its reverse pass run as ONE launch (layer_last.hip) in this step.
-// `a`: the forward arguments as forward_layers built them.
+// Here: the properties of the model and the step; the launch's scope, backward side included, is layer_last_fusable's (layer.hpp).
 static bool last_chain_fusable(const dsdgp_model* m, const LayerState& St, const LayerFwdArgs& a) {
   const LayerDev& v = St.dev;
-  const int L = m->desc.L;
-  if (m->force.last_fuse == 0 || m->desc.white || St.gemm || L < 2) return false;
-  if (!layer_last_built(v.Mp, v.D_in, v.D_out) || !v.alg_g || !v.need_tpt) return false;
-  if (!a.lik_Y || !a.Asave || a.Csave || a.F || a.rep != 1 || a.d_split > 1 || a.qmu_ld) return false;
-  if (a.mean_kind != DSDGP_MEAN_ZERO) return false;
-  if (m->grad_q_only && m->grad_first == L - 1) return false;     // that layer runs no backward chain at all
-  if (m->force.bwd_split >= 2) return false;
+  // (bwd_split = 2 forces split chains everywhere: a D_out = 1 chain has nothing to split, d_split alone would not say so)
+  if (m->force.last_fuse == 0 || m->force.bwd_split >= 2 || !v.need_tpt || m->desc.white || St.gemm || m->desc.L < 2) return false;
+  if (m->grad_q_only && m->grad_first == m->desc.L - 1) return false;     // that layer runs no backward chain at all
   static const bool timing = getenv("DSDGP_FWD_TIMING") || getenv("DSDGP_BWD_TIMING");      // the phase clocks are the two chains'
-  if (timing) return false;
-  return ceil_div(a.Rin, 16) >= m->force.last_min_blocks;
+  if (timing || ceil_div(a.Rin, 16) < m->force.last_min_blocks) return false;
+  const int hyp_rows = (int)(sm_hyp_parts(a.ldA, v.Mp, v.D_in) / (a.ldA / 16));
+  return layer_last_fusable(a, v.Mp, v.kern_kind, hyp_rows, bwd_d_split(m, St, a.ldA / 16), !v.alg_g);
 }
 
 // dgp.py:61-76 propagate
@@ -495,14 +502,7 @@ static BwdSchedule bwd_schedule(const dsdgp_model* m, int64_t n, int S) {
     y.chain = !(s.q_only && l == g);
     const bool prologue = !produced && !last && y.chain && m->force.adj_fuse != 0 && !St.c_used && !St.gemm && sm_adj_fusable(v.Mp, nblk, v.D_in, v.D_out);
     y.adj = produced ? ADJ_PRODUCER : (prologue ? ADJ_PROLOGUE : ADJ_PREP);
-    // few row blocks (the N-row first layer, small shards): spread the d-loop over up to four workgroups per row block.
-    // Only from Mp = 512 (bwd_split = 2 forces it everywhere, 0 disables): every workgroup of a split repeats the chain's prologue
-    // and epilogue phases.  63-row-block first layer of config 2 (M = 128): +57 us with the __threadfence() hand-over of
-    // round 2, still +6 us per step with the fence-free sc1 hand-over of round 3 (cutting the upper layer's weight-gradient
-    // task list over both streams to use the shortened chain: +10..+20 us); -0.9 ms on the 32-row-block, 30-output first
-    // layer of config 4 (M = 512)
-    const bool want = m->force.bwd_split >= 2 || (m->force.bwd_split == 1 && v.Mp > 256);
-    y.d_split = (want && St.bpart) ? chain_d_split(nblk, v.D_out) : 1;
+    y.d_split = bwd_d_split(m, St, nblk);
     // the lowest layer of the reverse pass keeps its products on the main stream: nothing is left to run them under, and the
     // join then waits for side-stream work that finished long ago instead of for a just-in-time signal
     const bool on_main = s.overlap && l == g && L - g > 1;

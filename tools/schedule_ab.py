@@ -46,6 +46,12 @@ CASES = {
     "L3.grad_first1": dict(N=100, D=3, M=20, S=3, L=3, grad_first=1),
     "L3.grad_q_only": dict(N=100, D=3, M=20, S=3, L=3, grad_first=1, q_only=True),
     "L3.M50.buckets": dict(N=130, D=5, M=50, S=2, L=3, buckets=True),
+    # chain instances the cases above do not reach: the 8-wave fused last layer (S N >= 4 Mp: algebraic assembly), the WIDE instances
+    # (D > 64; "L2.wide" is a narrow one) at 4 and 8 waves, and the 32-byte operand order of Mp > 256
+    "L2.M256.fused": dict(N=300, D=5, M=256, S=4, L=2),
+    "L2.wide65": dict(N=80, D=65, M=30, S=2, L=2),
+    "L2.wide65.M128": dict(N=80, D=65, M=128, S=2, L=2),
+    "L2.Mp320": dict(N=128, D=3, M=310, S=2, L=2),
 }
 SETTINGS = {
     "default": {},
