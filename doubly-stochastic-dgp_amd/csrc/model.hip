@@ -13,6 +13,7 @@ int gram_launch(dsdgp_ctx* ctx, int kind, const double* X, int64_t n, const doub
 #define SOFTPLUS_LOWER 1e-6  // [UPSTREAM] gpflow.transforms.positive
 
 #include "model_plan.hpp"       // split-K plan of the weight-gradient products (pure host code)
+#include "prepare_plan.hpp"     // what a prepare recomputes: validity record and plan (pure host code)
 #include "model_types.hpp"      // descriptors, policies
 #include "model_layout.hpp"     // workspace layout
 #include "model_kernels.hpp"    // device kernels (transforms, KL, likelihoods, reduction, assembly, tail)
@@ -309,7 +310,6 @@ extern "C" int dsdgp_model_create(dsdgp_ctx* ctx, const dsdgp_model_desc* desc, 
   DS_HIP(hipEventCreateWithFlags(&m->ev_prep_side, evf));
   DS_HIP(hipEventCreateWithFlags(&m->ev_z, evf));
   DS_HIP(hipEventCreateWithFlags(&m->ev_kinv, evf));
-  m->prepared = false;
   m->plan_n = -1;
   m->plan_S = -1;
   *out = m;
@@ -391,20 +391,18 @@ extern "C" int dsdgp_model_set_grad_q_only(dsdgp_model* m, int32_t on) {
 
 extern "C" int dsdgp_model_track_theta(dsdgp_model* m, int enable) {
   DS_CHECK_ARG(m != nullptr);
-  m->track_theta = enable != 0;
-  m->kuu_valid = false;
-  m->q_dirty = -2;
+  m->ps.set_track_theta(enable != 0);
   return DSDGP_OK;
 }
 extern "C" int dsdgp_model_theta_changed(dsdgp_model* m) {
   DS_CHECK_ARG(m != nullptr);
-  mark_theta_moved(m);
+  m->ps.theta_moved();
   return DSDGP_OK;
 }
 
 extern "C" int dsdgp_model_layer_kl(dsdgp_model* m, int32_t l, double* out) {
   DS_CHECK_ARG(m && out && l >= 0 && l < m->desc.L);
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(ensure_prepared(m));
   DS_LAUNCH(k_kl_final, dim3(1), dim3(256), 0, m->ctx->stream, m->layers_dev, m->desc.L);
   DS_HIP(hipGetLastError());
   DS_HIP(hipMemcpyAsync(out, m->L[l].dev.klv, sizeof(double), hipMemcpyDeviceToDevice, m->ctx->stream));
@@ -424,7 +422,7 @@ extern "C" int dsdgp_model_layer_matrix(dsdgp_model* m, int32_t l, int32_t which
     dsdgp_set_error("dsdgp_model_layer_matrix: layer %d keeps no Lu (it is written back for white = True models only)", l);
     return DSDGP_ERR_UNSUPPORTED;
   }
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(ensure_prepared(m));
   DS_TRY(join_prep(m));
   const double* src = which == DSDGP_MAT_LU ? v.Kp : which == DSDGP_MAT_LUINV ? v.Linv : which == DSDGP_MAT_LUINVT ? v.LinvT : v.Kinv;
   const size_t row = (size_t)v.Mp * sizeof(double);
@@ -479,8 +477,8 @@ extern "C" int dsdgp_multiclass_readout(dsdgp_ctx* ctx, const double* mean, cons
 extern "C" int dsdgp_model_layer_conditional(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean,
                                              double* var) {
   DS_CHECK_ARG(m && X && mean && var && l >= 0 && l < m->desc.L && n > 0);
-  m->saved = false;      // (the GEMM-formulated pass works in the scratch the saved pass left its operands in)
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  m->ps.workspace_overwritten();      // (the GEMM-formulated pass works in the scratch the saved pass left its operands in)
+  DS_TRY(ensure_prepared(m));
   LayerState& St = m->L[l];
   const LayerDev& v = St.dev;
   LayerFwdArgs a{};

@@ -119,7 +119,7 @@ extern "C" int dsdgp_model_natgrad_step(dsdgp_model* m, int32_t l, double gamma,
   const int64_t MM = (int64_t)v.Mp * v.Mp;
   const int nb = (int)std::min<int64_t>(1024, ceil_div(v.D_out * MM, 256));
   // Tp / qmu must reflect the current theta
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(ensure_prepared(m));
   DS_LAUNCH(k_ng_prep, dim3(nb), dim3(256), 0, ctx->stream, m->layers_dev, l, m->grad);
   DS_HIP(hipGetLastError());
   if (St.big) DS_TRY(bigchol_run(ctx, St.big_ngT));
@@ -138,8 +138,7 @@ extern "C" int dsdgp_model_natgrad_step(dsdgp_model* m, int32_t l, double gamma,
   DS_LAUNCH(k_ng_mu, dim3(ceil_div(v.D_out * v.M, 4)), dim3(256), 0, ctx->stream, m->layers_dev, l, m->theta, 1);
   DS_LAUNCH(k_ng_write, dim3(nb), dim3(256), 0, ctx->stream, m->layers_dev, l, m->theta);
   DS_HIP(hipGetLastError());
-  m->prepared = m->saved = false;
-  m->q_dirty = (m->q_dirty == -1 || m->q_dirty == l) ? l : -2;     // Z and the kernel hyper-parameters are untouched: kuu_valid stays
+  m->ps.q_moved(l);
   if (info) {
     std::vector<double> sc(2 * v.D_out);
     DS_HIP(hipMemcpyAsync(sc.data(), v.ngScal, sc.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -195,8 +194,8 @@ static int run_gemms(dsdgp_ctx* ctx, std::vector<GemmProblem>& probs, GemmProble
 extern "C" int dsdgp_model_layer_conditional_full(dsdgp_model* m, int32_t l, const double* X, int64_t n, double* mean,
                                                   double* var) {
   DS_CHECK_ARG(m && X && mean && var && l >= 0 && l < m->desc.L && n > 0);
-  m->saved = false;
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  m->ps.workspace_overwritten();
+  DS_TRY(ensure_prepared(m));
   dsdgp_ctx* ctx = m->ctx;
   LayerState& St = m->L[l];
   const LayerDev& v = St.dev;

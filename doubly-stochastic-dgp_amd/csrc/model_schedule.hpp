@@ -1,4 +1,5 @@
-// Launch schedule of one evaluation: prepare (Ku, factor, parameter products; main / side stream), forward layers (dgp.py:61-76), upload
+// Launch schedule of one evaluation: prepare (Ku, factor, parameter products; main / side stream — what of them is redone is decided
+// once, by prep_plan of prepare_plan.hpp, from the validity record dsdgp_model::ps), forward layers (dgp.py:61-76), upload
 // of the split-K plan (ensure_plan; the arithmetic is model_plan.hpp), reverse pass — its decisions taken once (BwdSchedule, bwd_schedule),
 // then launches only (backward_layers and its three endings) — ELBO / training step.  Part of the model translation unit.
 #pragma once
@@ -32,21 +33,31 @@ static int join_prep(dsdgp_model* m) {
 // parameter-only rest — Ku^-1, S_d, Lu^-1 q_sqrt, KL and, for a gradient step, U_d = Ku^-1 q_sqrt_d, n = Ku^-1 q_mu and
 // U_d U_d^T — which nothing needs before the backward pass / the final reduction: with `side` it runs on the side stream
 // concurrently with the forward layers and the caller joins (join_prep) where it is first consumed.
-// (`side` = run that part on the side stream.)
+// (`side` = run that part on the side stream.)  What is redone and what stays is prep_plan's decision (prepare_plan.hpp: the reuse
+// rules under dsdgp_model_track_theta); here: its inputs, then the launches it names.
+static_assert(DSDGP_MAX_LAYERS <= 32, "PrepIn::blocked is a 32-bit mask");
+static PrepIn prep_in(const dsdgp_model* m, bool with_grad, bool side) {
+  PrepIn in{with_grad, side, m->desc.L, m->desc.white != 0, m->grad_first, m->head_ok, m->uniform_big, 0u, 0, big_mp(false), m->force.ext_ev != 0};
+  for (int l = 0; l < in.L; ++l) {
+    in.mp_max = std::max(in.mp_max, (int)m->L[l].dev.Mp);
+    if (m->L[l].big) in.blocked |= 1u << l;
+  }
+  return in;
+}
+static int launch_grad_side(dsdgp_ctx* ctx, const LayerState& Sq, hipStream_t st) {      // U_d, n, KS | U_d U_d^T of one layer
+  DS_TRY(gemm_launch(ctx, lq_unks(Sq), Sq.lq_n1, Sq.lq_t1, st));
+  return gemm_launch(ctx, lq_uut(Sq), Sq.lq_n2, Sq.lq_t2, st);
+}
 static int prepare_async(dsdgp_model* m, bool with_grad = false, bool side = false, const HeadRand* hr = nullptr,
                          const HeadGather* hg = nullptr) {
   dsdgp_ctx* ctx = m->ctx;
   const int L = m->desc.L;
-  m->saved = false;
+  m->ps.workspace_overwritten();
   DS_TRY(join_prep(m));
-  const bool keep_kuu = m->track_theta && m->kuu_valid;
-  // dsdgp_model_track_theta and no change since an evaluation that produced everything this one needs: the factor AND the
-  // parameter-side products (Ku^-1, Lu^-1 q_sqrt, KL, ...) stay — a forward-only evaluation at fixed parameters is the chains alone
-  const bool unchanged = keep_kuu && m->q_dirty == -1 && (m->prepared_grad || !with_grad);
-  int mp_max = 0;
-  for (int l = 0; l < L; ++l) mp_max = std::max(mp_max, (int)m->L[l].dev.Mp);
-  bool head_event = false;
-  if (m->head_ok) {
+  const PrepIn in = prep_in(m, with_grad, side);
+  const PrepPlan p = prep_plan(m->ps, in);
+  const int mp_max = in.mp_max;
+  if (p.head) {
     ProfScope ps(ctx, "potrf");
     const size_t lds = head_lds_bytes(mp_max);
     static size_t lds_set = 0;     // the attribute is sticky: one driver call per size
@@ -59,68 +70,53 @@ static int prepare_async(dsdgp_model* m, bool with_grad = false, bool side = fal
     HeadGather gnone{};
     const HeadGather& gq = hg ? *hg : gnone;
     const int nprep = std::max(32, m->prep_blocks / 2);
-    // with a side stream the launch carries the fork event itself (hipExtLaunchKernel attaches it to the dispatch's completion signal):
+    // fork_on_head: with a side stream the launch carries the fork event itself (hipExtLaunchKernel attaches it to the dispatch's completion signal):
     // a separate hipEventRecord puts a marker packet on this stream that the next kernel queues behind (~6 us, profiles/r03_timeline_*)
-    head_event = side && m->force.ext_ev != 0;
     g_dsdgp_launches.fetch_add(1, std::memory_order_relaxed);
     hipExtLaunchKernelGGL(k_head, dim3(1 + nprep + r.nblk + gq.nblk, L), dim3(HEAD_THREADS), (uint32_t)lds, ctx->stream, nullptr,
-                          head_event ? m->ev_fork : nullptr, 0, (const double*)m->theta, (const LayerDev*)m->layers_dev, m->lik_const,
+                          p.fork_on_head ? m->ev_fork : nullptr, 0, (const double*)m->theta, (const LayerDev*)m->layers_dev, m->lik_const,
                           (int64_t)m->desc.off_lik_var, lik_has_param(m->desc.lik_kind) ? 1 : 0, m->desc.jitter, nprep,
-                          keep_kuu ? 1 : 0, m->desc.white ? 1 : 0, getenv("DSDGP_POTRF_TIMING") ? 1 : 0, r, gq);
+                          p.keep_kuu ? 1 : 0, m->desc.white ? 1 : 0, getenv("DSDGP_POTRF_TIMING") ? 1 : 0, r, gq);
     DS_HIP(hipGetLastError());
-  } else if (!unchanged) {
-    DS_LAUNCH(k_prep_kuu, dim3(m->prep_blocks + (keep_kuu ? 0 : m->kuu_blocks), L), dim3(256), 0, ctx->stream, m->theta, m->layers_dev,
+  } else if (p.prep_kuu) {
+    DS_LAUNCH(k_prep_kuu, dim3(m->prep_blocks + (p.kuu_blocks ? m->kuu_blocks : 0), L), dim3(256), 0, ctx->stream, m->theta, m->layers_dev,
                        m->lik_const, m->desc.off_lik_var, lik_has_param(m->desc.lik_kind) ? 1 : 0, m->desc.jitter,
-                       m->prep_blocks, keep_kuu ? 1 : 0);
+                       m->prep_blocks, p.keep_kuu ? 1 : 0);
     DS_HIP(hipGetLastError());
   }
-  if (m->head_ok) {
-    // (factorised inside k_head)
-  } else if (keep_kuu) {
-    // Z and the kernel hyper-parameters are those of the previous evaluation: Lu, Lu^-1, log det stay
-  } else if (m->uniform_big) {
-    DS_TRY(bigchol_run(ctx, m->big_all));
-  } else if (mp_max >= big_mp(false)) {
-    for (int l = 0; l < L; ++l) {
-      if (m->L[l].big) DS_TRY(bigchol_run(ctx, m->L[l].big_k));
-      else DS_TRY(potrf_launch(ctx, m->potrf_items + l, 1, m->L[l].dev.Mp));
-    }
-  } else {
-    DS_TRY(potrf_launch(ctx, m->potrf_items, L, mp_max));
+  switch (p.factor) {
+    case FACTOR_NONE: case FACTOR_IN_HEAD: break;
+    case FACTOR_BATCHED_BLOCKED: DS_TRY(bigchol_run(ctx, m->big_all)); break;
+    case FACTOR_PER_LAYER:
+      for (int l = 0; l < L; ++l) {
+        if (p.blocked >> l & 1) DS_TRY(bigchol_run(ctx, m->L[l].big_k));
+        else DS_TRY(potrf_launch(ctx, m->potrf_items + l, 1, m->L[l].dev.Mp));
+      }
+      break;
+    case FACTOR_ONE_WG_BATCH: DS_TRY(potrf_launch(ctx, m->potrf_items, L, mp_max)); break;
   }
-  if (unchanged) {
-    m->prepared = true;
+  if (p.early) {
+    m->ps.prepare_done(p);
     return DSDGP_OK;
   }
   hipStream_t st = ctx->stream;
-  if (side) {
-    if (!head_event) DS_HIP(hipEventRecord(m->ev_fork, ctx->stream));
+  if (p.fork) {
+    if (!p.fork_on_head) DS_HIP(hipEventRecord(m->ev_fork, ctx->stream));
     DS_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0));
     st = m->side;
   }
   const int klb = mp_max >= 512 ? 512 : NPART;    // M = 512 / 1024: V alone is 8..64 MB per layer — 32 workgroups were latency-bound
-  // only layer lq's (q_mu, q_sqrt) moved since an evaluation that produced everything this one needs: its products alone
-  const int gfirst = (with_grad && !m->desc.white) ? m->grad_first : 0;
-  // The forward-side products (Ku^-1, Lu^-1 q_sqrt, Lu^-1 q_mu, S_d, the KL sums) and the gradient-side ones (U_d, n, U_d U_d^T) are
-  // decided separately: after a natural-gradient step on layer lf the forward side of every other layer is still that of the previous
-  // evaluation, whatever that evaluation did on the gradient side (a pruned natural-gradient evaluation leaves the lower layers' U_d
-  // undone: the Adam evaluation that follows redoes the gradient side of ALL layers, but the forward side of layer lf only — it used to
-  // redo all 17 Lu^-1 q_sqrt_d of a config-5 model as well)
-  const int lf = (keep_kuu && m->q_dirty >= 0) ? m->q_dirty : -1;
-  const int lq = (lf >= 0 && (m->prepared_grad || !with_grad)) ? lf : -1;
-  if (keep_kuu && m->q_dirty == -1) {
-    // nothing moved since the last evaluation (it lacked the gradient side only): the forward side stands as it is
-  } else if (lf >= 0) {
-    LayerState& Sq = m->L[lf];
+  if (p.fwd == REDO_LAYER) {
+    LayerState& Sq = m->L[p.fwd_layer];
     DS_TRY(gemm_launch(ctx, Sq.lq, Sq.lq_nf, Sq.lq_tf, st));
-    DS_LAUNCH(k_kl_part, dim3(klb, 1), dim3(256), 0, st, m->layers_dev + lf);
-  } else {
+    DS_LAUNCH(k_kl_part, dim3(klb, 1), dim3(256), 0, st, m->layers_dev + p.fwd_layer);
+  } else if (p.fwd == REDO_ALL) {
     DS_TRY(gemm_launch(ctx, m->gp_fwd, m->n_fwd, m->t_fwd, st));
     DS_LAUNCH(k_kl_part, dim3(klb, L), dim3(256), 0, st, m->layers_dev);
   }
   DS_HIP(hipGetLastError());
   m->kinv_pending = false;
-  if (side && with_grad && !m->desc.white) {
+  if (p.rec_kinv) {
     // Ku^-1, S_d and Lu^-1 q_sqrt are in the launch above — everything the backward CHAINS read of the side stream's products (the
     // rest — KS_d, U_d, n, U_d U_d^T — feeds the assembly at the end of the step).  The reverse pass waits for THIS event, long since
     // signalled when the forward chains end; the whole side stream's work ends together with the last inner forward chain, and a
@@ -129,32 +125,21 @@ static int prepare_async(dsdgp_model* m, bool with_grad = false, bool side = fal
     DS_HIP(hipEventRecord(m->ev_kinv, m->side));
     m->kinv_pending = true;
   }
-  if (with_grad && !m->desc.white) {
-    if (lq >= 0) {
-      LayerState& Sq = m->L[lq];
-      DS_TRY(gemm_launch(ctx, lq_unks(Sq), Sq.lq_n1, Sq.lq_t1, st));
-      DS_TRY(gemm_launch(ctx, lq_uut(Sq), Sq.lq_n2, Sq.lq_t2, st));
-    } else if (gfirst > 0) {
-      for (int l = gfirst; l < L; ++l) {
-        LayerState& Sq = m->L[l];
-        DS_TRY(gemm_launch(ctx, lq_unks(Sq), Sq.lq_n1, Sq.lq_t1, st));
-        DS_TRY(gemm_launch(ctx, lq_uut(Sq), Sq.lq_n2, Sq.lq_t2, st));
-      }
-    } else {
-      DS_TRY(gemm_launch(ctx, m->gp_bwd1, m->n_bwd1, m->t_bwd1, st));
-      DS_TRY(gemm_launch(ctx, m->gp_bwd2, m->n_bwd2, m->t_bwd2, st));
-    }
+  if (p.grad == REDO_LAYER) DS_TRY(launch_grad_side(ctx, m->L[p.grad_layer], st));
+  else if (p.grad == REDO_FROM) {
+    for (int l = p.grad_layer; l < L; ++l) DS_TRY(launch_grad_side(ctx, m->L[l], st));
+  } else if (p.grad == REDO_ALL) {
+    DS_TRY(gemm_launch(ctx, m->gp_bwd1, m->n_bwd1, m->t_bwd1, st));
+    DS_TRY(gemm_launch(ctx, m->gp_bwd2, m->n_bwd2, m->t_bwd2, st));
   }
-  if (side) {
+  if (p.rec_prep_side) {
     DS_HIP(hipEventRecord(m->ev_prep_side, m->side));
     m->side_pending = true;
   }
-  m->prepared = true;
-  m->prepared_grad = with_grad && gfirst == 0;     // (a partial prepare with_grad required the previous one to have had it)
-  m->kuu_valid = true;
-  m->q_dirty = -1;
+  m->ps.prepare_done(p);
   return DSDGP_OK;
 }
+static int ensure_prepared(dsdgp_model* m) { return m->ps.prepared ? DSDGP_OK : prepare_async(m); }
 
 static int read_info(dsdgp_model* m, int* info) {
   if (!info) return DSDGP_OK;
@@ -236,7 +221,7 @@ static int forward_layers(dsdgp_model* m, const double* X, int64_t n, int S, con
   // Mp <= 256: the larger instances read the factor transposed, which exists for q_sqrt only.
   const bool wf_ok = !m->desc.white && !save && m->force.white_fwd != 0;
   m->last_deferred = false;
-  m->saved = false;
+  m->ps.workspace_overwritten();
   if (wf_ok) DS_TRY(join_prep(m));          // V, nL come from the parameter products (side stream in the overlapped schedule)
   for (int l = 0; l < L; ++l) {
     LayerState& St = m->L[l];
@@ -316,7 +301,7 @@ extern "C" int dsdgp_model_propagate(dsdgp_model* m, const double* X, int64_t n,
                                      double* const* Fvars) {
   DS_CHECK_ARG(m && X);
   DS_CHECK_ARG(!zs || zstride);
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(ensure_prepared(m));
   return forward_layers(m, X, n, S, zs, zstride, seed, false, true, Fs, Fmeans, Fvars);
 }
 
@@ -335,7 +320,7 @@ static int mixture_forward(const char* who, dsdgp_model* m, const double* X, int
                     m->desc.lik_kind);
     return DSDGP_ERR_UNSUPPORTED;
   }
-  if (!m->prepared) DS_TRY(prepare_async(m));
+  DS_TRY(ensure_prepared(m));
   DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
   *last = &m->L[m->desc.L - 1];
   return DSDGP_OK;
@@ -727,7 +712,6 @@ static int finish_value(dsdgp_model* m) {
     DS_TRY(join_prep(m));   // KL values
     DS_TRY(launch_finalize(m, m->ctx->stream));
   }
-  m->prepared = true;
   return DSDGP_OK;
 }
 
@@ -811,7 +795,7 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
   m->fin.done = false;
   if (with_grad) {
     DS_TRY(backward_layers(m, n, S, kl_weight));
-    m->grad_pruned = !m->desc.white && (m->grad_first > 0 || m->grad_q_only);
+    m->ps.grad_evaluated(pass_is_pruned(m->desc.white, m->grad_first, m->grad_q_only));
   }
   return finish_value(m);
 }
@@ -835,7 +819,7 @@ static int vjp_refusals(const char* who, const dsdgp_model* m) {
     dsdgp_set_error("%s: quadrature sample weights are set (dsdgp_model_set_sample_weights); the caller's adjoints carry their own weights", who);
     return DSDGP_ERR_UNSUPPORTED;
   }
-  if (!m->desc.white && (m->grad_first > 0 || m->grad_q_only)) {
+  if (pass_is_pruned(m->desc.white, m->grad_first, m->grad_q_only)) {
     dsdgp_set_error("%s: the reverse pass is restricted to layers >= %d%s (dsdgp_model_set_grad_first_layer / _q_only)", who, m->grad_first,
                     m->grad_q_only ? ", (q_mu, q_sqrt) only" : "");
     return DSDGP_ERR_BAD_ARG;
@@ -861,23 +845,23 @@ extern "C" int dsdgp_model_forward_saved(dsdgp_model* m, const double* X, int64_
   const size_t bytes = (size_t)S * n * last.dev.D_out * sizeof(double);
   if (mean_out) DS_HIP(hipMemcpyAsync(mean_out, last.mean, bytes, hipMemcpyDeviceToDevice, ctx->stream));
   if (var_out) DS_HIP(hipMemcpyAsync(var_out, last.var, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  m->saved = true; m->saved_n = n; m->saved_S = S;
+  m->ps.saved_recorded(n, S);
   return DSDGP_OK;
 }
 // The reverse half: the last layer's adjoints are the caller's (ADJ_PREP reads them from lik_dmean / lik_dvar, as after MultiClass), no
 // likelihood block takes part in the value (fin.nblocks = 0: lik_part is not read).
 extern "C" int dsdgp_model_backward_adjoints(dsdgp_model* m, const double* dmean, const double* dvar, double kl_weight, double* out) {
   DS_CHECK_ARG(m && dmean && dvar && out && m->grad != nullptr);
-  if (!m->saved) {
+  if (!m->ps.saved) {
     dsdgp_set_error("dsdgp_model_backward_adjoints: the model's last evaluation is not a dsdgp_model_forward_saved (another evaluation, a "
                     "change of theta or an optimiser step since then drops the saved forward pass)");
     return DSDGP_ERR_BAD_ARG;
   }
   DS_TRY(vjp_refusals("dsdgp_model_backward_adjoints", m));
   dsdgp_ctx* ctx = m->ctx;
-  const int64_t n = m->saved_n;
-  const int S = m->saved_S;
-  m->saved = false;       // consumed, also by a reverse pass that fails half-way
+  const int64_t n = m->ps.saved_n;
+  const int S = m->ps.saved_S;
+  m->ps.saved_consumed();
   const int64_t count = (int64_t)S * n * m->L[m->desc.L - 1].dev.D_out;      // <= s_max n_max D_out, the size of lik_dmean / lik_dvar
   DS_LAUNCH(k_seed_adjoints, dim3((int)std::min<int64_t>(2048, ceil_div(count, 256))), dim3(256), 0, ctx->stream, dmean, dvar, count,
             m->lik_dmean, m->lik_dvar);
@@ -886,7 +870,7 @@ extern "C" int dsdgp_model_backward_adjoints(dsdgp_model* m, const double* dmean
   m->fin.nblocks = 0; m->fin.w = 0.0; m->fin.kl_weight = kl_weight; m->fin.with_grad = 1; m->fin.out = out;
   m->fin.done = false;
   DS_TRY(backward_layers(m, n, S, kl_weight));
-  m->grad_pruned = false;
+  m->ps.grad_evaluated(false);
   DS_TRY(finish_value(m));
   // every ending writes -w * (sum of no partials) * sigmoid(raw) = -0.0 there: the entry is +0.0
   const int64_t ol = lik_var_offset(m);
@@ -903,12 +887,10 @@ extern "C" int dsdgp_model_set_sample_weights(dsdgp_model* m, const double* w, i
 
 // Adam's bias-corrected step size at step t
 static double adam_lr_t(double lr, double b1, double b2, int64_t t) { return lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t)); }
-// theta moved (an optimiser step, the caller's write): nothing prepared from it stands
-static void mark_theta_moved(dsdgp_model* m) { m->prepared = m->kuu_valid = m->saved = false; m->q_dirty = -2; }
 
 extern "C" int dsdgp_model_adam_step(dsdgp_model* m, double lr, double beta1, double beta2, double eps, int64_t t) {
   DS_CHECK_ARG(m && m->grad && m->adam_m && m->adam_v && t >= 1);
-  if (m->grad_pruned) {
+  if (m->ps.grad_pruned) {
     dsdgp_set_error("dsdgp_model_adam_step: the last gradient was evaluated for layers >= %d only (dsdgp_model_set_grad_first_layer)", m->grad_first);
     return DSDGP_ERR_BAD_ARG;
   }
@@ -918,7 +900,7 @@ extern "C" int dsdgp_model_adam_step(dsdgp_model* m, double lr, double beta1, do
   DS_LAUNCH(k_adam, dim3(nb), dim3(256), 0, m->ctx->stream, m->theta, m->grad, m->adam_m, m->adam_v, m->mask, n,
                      lr_t, beta1, beta2, eps, (const LayerDev*)m->layers_dev, m->desc.L);
   DS_HIP(hipGetLastError());
-  mark_theta_moved(m);
+  m->ps.theta_moved();
   return DSDGP_OK;
 }
 
@@ -929,7 +911,7 @@ static int train_step_impl(dsdgp_model* m, const double* X, const double* Y, int
                            const int64_t* zstride, uint64_t seed, double data_scale, double kl_weight, double lr, double beta1,
                            double beta2, double eps, int64_t t, double* out, const GatherSrc* gs) {
   DS_CHECK_ARG(m && m->grad && m->adam_m && m->adam_v && t >= 1);
-  if (!m->desc.white && (m->grad_first > 0 || m->grad_q_only)) {
+  if (pass_is_pruned(m->desc.white, m->grad_first, m->grad_q_only)) {
     dsdgp_set_error("dsdgp_model_train_step: the reverse pass is restricted to layers >= %d%s (dsdgp_model_set_grad_first_layer / _q_only)",
                     m->grad_first, m->grad_q_only ? ", (q_mu, q_sqrt) only" : "");
     return DSDGP_ERR_BAD_ARG;
@@ -944,6 +926,6 @@ static int train_step_impl(dsdgp_model* m, const double* X, const double* Y, int
   const int rc = elbo_impl(m, X, Y, n, S, zs, zstride, seed, data_scale, kl_weight, 1, out, gs);
   m->fuse_adam.on = 0;
   DS_TRY(rc);
-  mark_theta_moved(m);
+  m->ps.theta_moved();
   return DSDGP_OK;
 }

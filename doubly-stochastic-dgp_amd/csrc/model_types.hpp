@@ -66,18 +66,9 @@ struct dsdgp_model {
   int32_t* gemm_order = nullptr;   // device pool of the longest-processing-time tile lists of the grouped M x M launches (gemm_plan_lpt)
   int64_t gemm_order_cap = 0, gemm_order_used = 0;
   GemmLayerWs gws{};           // scratch of the GEMM-formulated layers (one set per model: the layers run one after the other)
-  bool prepared_grad = false;  // the last prepare also produced U_d, n, U_d U_d^T
-  bool track_theta = false;    // dsdgp_model_track_theta: the caller reports its writes to theta
-  bool kuu_valid = false;      // Lu / Lu^-1 / Ku^-1 belong to the Z and kernel hyper-parameters currently in theta
+  ParamState ps;               // what the device buffers were computed from: written by its transitions only (prepare_plan.hpp)
   int grad_first = 0;          // dsdgp_model_set_grad_first_layer: reverse mode stops below this layer
-  bool grad_pruned = false;    // the gradient buffer holds a pruned reverse pass (entries of the lower layers are stale)
   bool grad_q_only = false;    // dsdgp_model_set_grad_q_only: only the (q_mu, q_sqrt) entries of the layers >= grad_first are wanted
-  // dsdgp_model_forward_saved was the last evaluation: the workspace holds what a reverse pass over saved_n rows x saved_S samples reads
-  // (dsdgp_model_backward_adjoints).  Dropped by prepare_async, forward_layers, mark_theta_moved and the other writers of the workspace.
-  bool saved = false;
-  int64_t saved_n = 0;
-  int saved_S = 0;
-  int q_dirty = -2;            // with kuu_valid: -1 nothing changed, l >= 0 only layer l's (q_mu, q_sqrt) changed, -2 unknown / several
   bool side_pending = false;   // parameter-only work (Ku^-1, S_d, KL, U, UU) still running on the side stream
   int n_fwd, n_bwd1, n_bwd2, t_fwd, t_bwd1, t_bwd2, n_w, t_w1, t_w2, t_w3;
   const double* sample_w = nullptr;   // DGP_Quad quadrature weights (borrowed), NULL = Monte-Carlo mean
@@ -86,7 +77,7 @@ struct dsdgp_model {
   int n_wz = 0, t_wz = 0, kuu_blocks = 32, asm_blocks = 64, prep_blocks = PREP_BLOCKS;
   bool uniform_big = false;     // all layers share M and Mp >= 192: ONE batched multi-workgroup Cholesky for all layers
   BigChol big_all;
-  bool need_hyp_part = false;
+  bool need_hyp_part = false;   // some layer does not fold its Ku-side hyper-parameter partials into k_asm_kbar
   bool tail_ok = false;         // non-white, every D_in <= WIDE_DIN: gradient assembly in k_asm_rows + k_tail (one wave per inducing row)
   struct { int on; double lr_t, b1, b2, eps; } fuse_adam = {0, 0, 0, 0, 0};   // dsdgp_model_train_step: Adam applied inside k_tail
   int mp_max_all = 0, m_max_all = 0;
@@ -101,13 +92,12 @@ struct dsdgp_model {
   bool fused_last = false;      // the last layer's MB / VB were written by the likelihood kernel of this step
   // arguments of the pending k_finalize (value + likelihood-variance gradient): launched on the side stream beside the
   // backward chain when streams overlap, otherwise on the main stream after it
-  struct { int nblocks; double w, kl_weight; int with_grad; double* out; bool done; } fin;   // some layer does not fold its Ku-side hyper-parameter partials into k_asm_kbar
+  struct { int nblocks; double w, kl_weight; int with_grad; double* out; bool done; } fin;
   RedJob* rjobs;       // device: split reductions of every layer, rebuilt when (n, S) changes
   int rjobs_cap, n_red, red_blocks;
   size_t red_lds = 0;
   int64_t plan_n;
   int plan_S;
-  bool prepared;
   // side stream: the weight-gradient products of layer l overlap the backward chain of layer l-1 (disjoint buffers)
   hipStream_t side;
   hipEvent_t ev_bwd[DSDGP_MAX_LAYERS];

@@ -15,6 +15,8 @@ step).  Per (case, setting) the file holds
   launches           dsdgp_launch_count of the evaluation and of each step
   workspace          dsdgp_model_workspace_bytes of the model
   buckets            (bucket case) the (bucket, offset, count) triples the callback was handed
+The walk case holds, per call of its sequence (cNN_<call>_<what>), the result scalars, gradient, theta or propagated arrays, and in
+`launches` the launch count of every call: which launches each state of the model leads to.
 `--compare` exits non-zero unless every array of the two files is equal (np.array_equal; NaNs in the same places count as equal)."""
 import argparse
 import ctypes as C
@@ -52,6 +54,8 @@ CASES = {
     "L2.wide65": dict(N=80, D=65, M=30, S=2, L=2),
     "L2.wide65.M128": dict(N=80, D=65, M=128, S=2, L=2),
     "L2.Mp320": dict(N=128, D=3, M=310, S=2, L=2),
+    # what a prepare keeps (csrc/prepare_plan.hpp): the walk of tests/test_gpu_prepare_walk.py, bits and launch count of every call
+    "L3.M20.walk": dict(N=40, D=3, M=20, S=2, L=3, walk=True),
 }
 SETTINGS = {
     "default": {},
@@ -72,6 +76,43 @@ SETTINGS = {
     "gemm_mp=16": {"DSDGP_FORCE": "gemm_mp=16"},
     "bwd_split+save_c": {"DSDGP_FORCE": "bwd_split=2,save_c=2,cs_min_blocks=0,cs_min_dout=1"},
 }
+
+
+def run_walk(eng, X, Y, zs, S):
+    """V, G, natgrad(last), G, natgrad(0), V, pruned G from layer 1 (q only), G, propagate, Adam step, V, G at explicit draws"""
+    count = eng.lib.dsdgp_launch_count
+    res, launches = {}, []
+    L = len(eng.layers)
+
+    def call(what, fn):
+        i, n0 = len(launches), count()
+        got = fn()
+        eng.ctx.sync()
+        launches.append(count() - n0)
+        for k, v in got.items():
+            res[f"c{i:02d}_{what}_{k}"] = v
+
+    def ev(with_grad, first=0, q_only=False):
+        out4 = eng.elbo(X, Y, S, zs=zs, data_scale=1.0, with_grad=with_grad, grad_from_layer=first, grad_q_only=q_only)
+        return {"out4": np.array(out4), **({"grad": eng.grad.cpu().numpy().copy()} if with_grad else {})}
+
+    def theta_after(fn):
+        fn()
+        eng.ctx.sync()
+        return {"theta": eng.theta.cpu().numpy().copy()}
+
+    def prop():
+        eng.ctx.sync()
+        return {f"{k}{l}": t.cpu().numpy().copy() for k, ts in zip(("F", "mean", "var"), eng.propagate(X, S, zs=zs)) for l, t in enumerate(ts)}
+
+    for what, fn in (("V", lambda: ev(False)), ("G", lambda: ev(True)), ("natgrad_last", lambda: theta_after(lambda: eng.natgrad_step(L - 1, 0.005))),
+                     ("G", lambda: ev(True)), ("natgrad_0", lambda: theta_after(lambda: eng.natgrad_step(0, 0.005))), ("V", lambda: ev(False)),
+                     ("Gq1", lambda: ev(True, 1, True)), ("G", lambda: ev(True)), ("propagate", prop),
+                     ("adam", lambda: theta_after(lambda: eng.adam_step(lr=0.01))), ("V", lambda: ev(False)), ("G", lambda: ev(True))):
+        call(what, fn)
+    res["launches"] = np.array(launches, dtype=np.int64)
+    res["workspace"] = np.array([eng.workspace.numel() - 256])
+    return res
 
 
 def run_case(c):
@@ -96,8 +137,12 @@ def run_case(c):
         layer.q_mu = 0.3 * rng.randn(*layer.q_mu.shape)
         q = np.asarray(layer.q_sqrt.value)
         layer.q_sqrt = q * 0.7 + 0.05 * np.tril(rng.randn(*q.shape))
+        if c.get("walk"):      # well-conditioned, so that the natural-gradient step on an inner layer is not refused
+            layer.q_sqrt = 0.7 * np.tile(np.eye(q.shape[1]), (q.shape[0], 1, 1)) + np.tril(rng.randn(*q.shape)) / q.shape[1]
     zs = [rng.randn(S, N, layer.num_outputs) for layer in model.layers]
     eng = model.engine()
+    if c.get("walk"):
+        return run_walk(eng, X, Y, zs, S)
     handed = []
     if c.get("buckets"):
         def on_bucket(user, bucket, ptr, count, stream):      # no exchange: the step's own results must not depend on the callback
