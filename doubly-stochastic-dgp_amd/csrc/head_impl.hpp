@@ -9,7 +9,7 @@
 #pragma once
 #include "chol_lds.hpp"
 
-#define HEAD_THREADS 512
+// HEAD_THREADS (512): chain_policy.hpp, which sizes the draw blocks by it
 #define HEAD_NW 8
 #define HEAD_MAX_N 128
 #define HEAD_MAX_DIN 16

@@ -1,8 +1,7 @@
 // SVGP_Layer hot path on gfx950: argument blocks of the chain kernels and of the split-K weight-gradient products.
 #pragma once
 #include "common.hpp"
-
-#define XCH 64   // columns of x/l the chain kernels stage per chunk; inputs wider than this take the WIDE instances
+#include "chain_policy.hpp"   // the size rules of these launches (XCH, sm_*, chain_d_split, layer_last_fusable, ...): plain host code
 
 // SVGP_Layer.conditional_ND + reparameterize (layers.py:178-219, utils.py:40-41), fused.
 struct LayerFwdArgs {
@@ -117,8 +116,6 @@ struct LayerBwdArgs {
   double up_jitter;
   double *MBw, *VBw;           // = MB / VB, writable
 };
-// whether the backward chain of this shape can take the adjoint prologue (its LDS reduction scratch holds 2 x 16 x D_out partials)
-int sm_adj_fusable(int Mp, int64_t nblk, int D_in, int D_out);
 
 // jobs_dev: device copy (WgradJob: plan_types.hpp) of `njobs` jobs with task_start filled (64 x 64 tiles, one workgroup per (job, split, tile) task; grouped
 // jobs: one workgroup per (split, 32 x 32 tile) task of the group's outputs)
@@ -127,16 +124,9 @@ int wgrad_launch(dsdgp_ctx* ctx, const WgradJob* jobs_dev, int njobs, int total_
 // chain kernels (layer_sm.hip): the NW waves of a workgroup cooperate on one block of 16 rows
 int layer_fwd_sm_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, int Mp, int kern_kind, int white);
 int layer_bwd_sm_launch(dsdgp_ctx* ctx, const LayerBwdArgs& a, int Mp, int kern_kind, int white);
-// the last layer of a training step as one launch (layer_last.hip): forward chain + Gaussian likelihood + reverse mode of the same row block
-int layer_last_built(int Mp, int D_in, int D_out);
-// THE decision whether a last layer is inside the fused launch's scope, taken once at forward time (last_chain_fusable skips the forward
-// chain on it) and only asserted at launch.  `a`: the forward arguments; the backward side as it is known by then: hyp_rows = rows of
-// hyp_part per row block (sm_hyp_parts / row blocks), the backward chain's d_split (bwd_d_split), whether E is wanted (no algebraic
-// dl/dKu assembly).
-int layer_last_fusable(const LayerFwdArgs& a, int Mp, int kern_kind, int hyp_rows, int bwd_d_split, int want_E);
+// the last layer of a training step as one launch (layer_last.hip): forward chain + Gaussian likelihood + reverse mode of the same row
+// block.  Its scope is layer_last_fusable (chain_policy.hpp), decided at forward time; the launch asserts it on its two argument blocks.
 int layer_last_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, const LayerBwdArgs& b, int Mp, int kern_kind, int hyp_rows);
-int sm_cs_built(int Mp);     // the split-M backward chain has a Csave instance for this padded inducing count
-int64_t sm_hyp_parts(int64_t ld, int Mp, int D_in);   // number of hyp_part rows the split-M backward writes for ld padded rows
 
 // ------------------------------------------------------------------------------------------------------
 // GEMM-formulated layer passes for LARGE inducing counts (layer_gemm.hip; Mp >= 512 by default).
@@ -163,6 +153,5 @@ struct GemmLayerWs {
 };
 #define GL_MAX_GROUPS 4
 int layer_gemm_hyp_parts(int64_t ld, int Mp);
-int layer_gemm_lik_blocks(int64_t Rin, int D_out);
 int layer_fwd_gemm_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, int Mp, int kern_kind, int white, const GemmLayerWs& ws);
 int layer_bwd_gemm_launch(dsdgp_ctx* ctx, const LayerBwdArgs& b, int Mp, int kern_kind, int white, const GemmLayerWs& ws);

@@ -589,7 +589,6 @@ __global__ void k_gl_zz(const double* __restrict__ Zs, int M, int Mp, int D_in, 
 // forward epilogue.  A workgroup takes 64 data rows; the per-tile-row sums of squares and q_mu^T a arrive M-major (coalesced along
 // the rows), go through LDS and leave row-major (a row's outputs are contiguous in mean / var / F), 32 outputs at a time.
 // The first layer writes `rep` output rows per input row.
-#define GL_EPI_ROWS 64
 #define GL_EPI_DC 32
 // lin_done: the Linear mean function's X mean_A is already part of MUT (thin product on [X^T ; 1]); only the bias is added here
 // sum of the per-tile-row partials p[t * ld], t < n, in tile order; four loads in flight
@@ -720,7 +719,6 @@ static int pgemm_split(dsdgp_ctx* ctx, PGemm P, double* pb, int64_t pb_doubles) 
   DS_HIP(hipGetLastError());
   return DSDGP_OK;
 }
-int layer_gemm_lik_blocks(int64_t Rin, int D_out) { return ceil_div(round_up(Rin, 16), GL_EPI_ROWS); }
 
 // backward, per data row: dX (or the transposed adjoints of the layer below) and this block's hyper-parameter partial sums from
 // OUT = ZZ^T GW:  WZ[j][r] = sum_m w z_mj,  Z2[j][r] = sum_m w z_mj^2,  W1[r] = sum_m w  (w = GW[m][r], z = Z / l)

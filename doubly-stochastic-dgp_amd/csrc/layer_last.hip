@@ -208,19 +208,13 @@ static int last_go(dsdgp_ctx* ctx, const LayerFwdArgs& a, const LayerBwdArgs& b,
   return DSDGP_OK;
 }
 
-// shapes this launch exists for (the caller checks the model-level conditions: layer position, likelihood, gradient set)
-int layer_last_built(int Mp, int D_in, int D_out) { return (Mp == 128 || Mp == 256) && D_out == 1 && D_in <= 16; }
-int layer_last_fusable(const LayerFwdArgs& a, int Mp, int kern_kind, int hyp_rows, int bwd_d_split, int want_E) {
-  const int waves = Mp == 128 ? 4 : 8;      // per row block of the instance: each writes one row of hyp_part, the surplus rows are zeroed
-  return layer_last_built(Mp, a.D_in, a.D_out) && (kern_kind == DSDGP_KERN_RBF || kern_kind == DSDGP_KERN_MATERN52) && hyp_rows >= waves &&
-         a.lik_Y && a.Asave && !a.Csave && !a.F && a.rep == 1 && !a.qmu_ld && a.mean_kind == DSDGP_MEAN_ZERO && a.d_split <= 1 &&
-         bwd_d_split <= 1 && !want_E;
-}
-
-// The backward block's Csave / mean_kind are the forward block's (one LayerState) and the adjoint prologue is an inner layer's: a block
-// that says otherwise was not built for this launch, which reads none of the three
+// The launch's scope is layer_last_fusable (chain_policy.hpp: the shapes and the model-level conditions the forward plan decided on),
+// asserted here on the two argument blocks.  The backward block's Csave / mean_kind are the forward block's (one LayerState) and the
+// adjoint prologue is an inner layer's: a block that says otherwise was not built for this launch, which reads none of the three
 int layer_last_launch(dsdgp_ctx* ctx, const LayerFwdArgs& a, const LayerBwdArgs& b, int Mp, int kern_kind, int hyp_rows) {
-  if (!layer_last_fusable(a, Mp, kern_kind, hyp_rows, b.d_split, b.E != nullptr) || b.Csave || b.up_dF || b.mean_kind != a.mean_kind) {
+  const LastScope s{Mp, a.D_in, a.D_out, kern_kind, hyp_rows, a.lik_Y != nullptr, a.Asave != nullptr, a.Csave != nullptr, a.F != nullptr, a.rep,
+                    a.qmu_ld != 0, a.mean_kind, a.d_split, b.d_split, b.E != nullptr};
+  if (!layer_last_fusable(s) || b.Csave || b.up_dF || b.mean_kind != a.mean_kind) {
     dsdgp_set_error("layer_last: launch outside the fused last layer's scope (internal)");
     return DSDGP_ERR_UNSUPPORTED;
   }

@@ -14,6 +14,7 @@ int gram_launch(dsdgp_ctx* ctx, int kind, const double* X, int64_t n, const doub
 
 #include "model_plan.hpp"       // split-K plan of the weight-gradient products (pure host code)
 #include "prepare_plan.hpp"     // what a prepare recomputes: validity record and plan (pure host code)
+#include "forward_plan.hpp"     // what a forward pass launches and keeps: plan and record for the reverse pass (pure host code)
 #include "model_types.hpp"      // descriptors, policies
 #include "model_layout.hpp"     // workspace layout
 #include "model_kernels.hpp"    // device kernels (transforms, KL, likelihoods, reduction, assembly, tail)
@@ -147,7 +148,7 @@ extern "C" int dsdgp_model_create(dsdgp_ctx* ctx, const dsdgp_model_desc* desc, 
     gf.push_back(P);
     // S_d = q_sqrt_d q_sqrt_d^T feeds the dense backward chain and KS_d; layers whose backward chain always takes the Csave
     // form (Mp >= 512) and that do not assemble dl/dKu algebraically never read it
-    if (!(Mp > 256 && save_c_enabled(m, Mp)) || v.alg_g) {
+    if (!(Mp > 256 && save_c_enabled(m->force.save_c, Mp)) || v.alg_g) {
       fill_gemm(P, v.Tp, v.Tp, v.Sd, Mp, Mp, Mp, Mp, Mp, Mp, 0, 1, v.D_out, MM, MM, MM, 0);            // S_d
       P.lower_only = 1; P.tri = 2 | 4 | 16;                                                              //   lower x lower^T, symmetric
       gf.push_back(P);

@@ -84,7 +84,7 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
       const int alg_env = m->force.alg_g;   // -1: heuristic, 0: never, 1: always
       const int64_t R_l = (l == 0) ? m->n_max : (int64_t)m->s_max * m->n_max;
       v.alg_g = (!D.white && (alg_env == 1 || (alg_env < 0 && (int64_t)4 * d.D_out * v.Mp <= R_l))) ? 1 : 0;
-      v.need_tpt = (v.Mp > 256 || save_c_enabled(m, v.Mp) || (m->force.gemm_mp > 0 && v.Mp >= m->force.gemm_mp)) ? 1 : 0;
+      v.need_tpt = (v.Mp > 256 || save_c_enabled(m->force.save_c, v.Mp) || (m->force.gemm_mp > 0 && v.Mp >= m->force.gemm_mp)) ? 1 : 0;
       // the fused last layer (layer_last.hip) forms abar's variance part as q_sqrt (q_sqrt^T a): it reads q_sqrt^T as rows
       if (l == D.L - 1 && D.L >= 2 && !D.white && m->force.last_fuse != 0 && layer_last_built(v.Mp, d.D_in, d.D_out)) v.need_tpt = 1;
       v.KS = v.alg_g ? b.take<double>(d.D_out * MM) : nullptr;
@@ -101,7 +101,7 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
     S.ld_max = round_up(Rin_max, 16);
     const size_t Mw = pad_Mw(v.Mp);      // rows Mp..Mw-1 stay zero (never written): whole tiles for the weight-gradient products
     S.A = b.take<double>(Mw * S.ld_max); S.E = b.take<double>(Mw * S.ld_max); S.GW = b.take<double>(Mw * S.ld_max);
-    S.C = save_c_enabled(m, (int)Mp) ? b.take<double>((size_t)d.D_out * Mp * S.ld_max) : nullptr;
+    S.C = save_c_enabled(m->force.save_c, (int)Mp) ? b.take<double>((size_t)d.D_out * Mp * S.ld_max) : nullptr;
     S.VB = b.take<double>(v.DP16 * S.ld_max); S.MB = b.take<double>(v.DP16 * S.ld_max);
     S.XT1 = b.take<double>((size_t)round_up(v.DinP16, 64) * S.ld_max);   // rows >= DinP16 stay zero: whole 64-row tiles for the mean-gradient product
     S.F = b.take<double>(S.R_max * d.D_out); S.mean = b.take<double>(S.R_max * d.D_out);

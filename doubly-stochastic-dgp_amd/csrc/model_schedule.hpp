@@ -1,7 +1,8 @@
 // Launch schedule of one evaluation: prepare (Ku, factor, parameter products; main / side stream — what of them is redone is decided
-// once, by prep_plan of prepare_plan.hpp, from the validity record dsdgp_model::ps), forward layers (dgp.py:61-76), upload
-// of the split-K plan (ensure_plan; the arithmetic is model_plan.hpp), reverse pass — its decisions taken once (BwdSchedule, bwd_schedule),
-// then launches only (backward_layers and its three endings) — ELBO / training step.  Part of the model translation unit.
+// once, by prep_plan of prepare_plan.hpp, from the validity record dsdgp_model::ps), forward layers (dgp.py:61-76) — their decisions taken
+// once per call by fwd_plan of forward_plan.hpp, then launches only (forward_pass, forward_layers), leaving the record dsdgp_model::fwd —
+// upload of the split-K plan (ensure_plan; the arithmetic is model_plan.hpp), reverse pass — its decisions taken once (BwdSchedule,
+// bwd_schedule), then launches only (backward_layers and its three endings) — ELBO / training step.  Part of the model translation unit.
 #pragma once
 // Side-stream overlap pays for its cross-stream events (a few microseconds each) only when the kernels are long enough:
 // tiny models (cfg 1: 100 rows, M = 50: n S Mp = 6400) are launch-latency-bound and run 40 % faster on a single stream.  The threshold
@@ -182,110 +183,94 @@ static int randn_async(dsdgp_ctx* ctx, uint64_t seed, uint64_t stream, int64_t c
   return DSDGP_OK;
 }
 
-// LayerBwdArgs::d_split of a backward chain over nblk row blocks. Few of them (the N-row first layer, small shards): up to four
-// workgroups per row block share the d-loop. Only from Mp = 512 (bwd_split = 2 forces it everywhere, 0 disables): every workgroup of a
-// split repeats the chain's prologue and epilogue phases. 63-row-block first layer of config 2 (M = 128): +57 us with the
-// __threadfence() hand-over of round 2, still +6 us per step with the fence-free sc1 hand-over of round 3 (cutting the upper layer's
-// weight-gradient task list over both streams to use the shortened chain: +10..+20 us); -0.9 ms on the 32-row-block, 30-output first
-// layer of config 4 (M = 512)
-static int bwd_d_split(const dsdgp_model* m, const LayerState& St, int64_t nblk) {
-  const bool want = m->force.bwd_split >= 2 || (m->force.bwd_split == 1 && St.dev.Mp > 256);
-  return (want && St.bpart) ? chain_d_split(nblk, St.dev.D_out) : 1;
-}
-// Whether the last layer's forward chain, the Gaussian likelihood and its reverse pass run as ONE launch (layer_last.hip) in this step.
-// Here: the properties of the model and the step; the launch's scope, backward side included, is layer_last_fusable's (layer.hpp).
-static bool last_chain_fusable(const dsdgp_model* m, const LayerState& St, const LayerFwdArgs& a) {
-  const LayerDev& v = St.dev;
-  // (bwd_split = 2 forces split chains everywhere: a D_out = 1 chain has nothing to split, d_split alone would not say so)
-  if (m->force.last_fuse == 0 || m->force.bwd_split >= 2 || !v.need_tpt || m->desc.white || St.gemm || m->desc.L < 2) return false;
-  if (m->grad_q_only && m->grad_first == m->desc.L - 1) return false;     // that layer runs no backward chain at all
-  static const bool timing = getenv("DSDGP_FWD_TIMING") || getenv("DSDGP_BWD_TIMING");      // the phase clocks are the two chains'
-  if (timing || ceil_div(a.Rin, 16) < m->force.last_min_blocks) return false;
-  const int hyp_rows = (int)(sm_hyp_parts(a.ldA, v.Mp, v.D_in) / (a.ldA / 16));
-  return layer_last_fusable(a, v.Mp, v.kern_kind, hyp_rows, bwd_d_split(m, St, a.ldA / 16), !v.alg_g);
+// A forward pass as its entry point states it: inputs, draws (zs / zstride as dsdgp_model_propagate takes them; what they leave open is
+// drawn from `seed`), optional output arrays per layer, the likelihood's targets and weight (data_scale / S) for the chain epilogue
+struct FwdCall {
+  const double* X;
+  int64_t n;
+  int S;
+  const double* const* zs;
+  const int64_t* zstride;
+  uint64_t seed;
+  double *const *Fs, *const *Fmeans, *const *Fvars;
+  const double* lik_Y;
+  double lik_w;
+};
+// minibatch to gather before the evaluation (dsdgp_model_train_step_minibatch): rows idx[0..n) of the resident data
+struct GatherSrc {
+  const double *Xs, *Ys;
+  const int64_t* idx;
+};
+// The call and the model as fwd_plan takes them (forward_plan.hpp).  prepare: the call runs a prepare of its own; save: for a reverse pass
+static FwdIn fwd_in(const dsdgp_model* m, const FwdCall& c, bool prepare, bool save, bool need_last_F, bool lik_target) {
+  static const bool timing = getenv("DSDGP_FWD_TIMING") || getenv("DSDGP_BWD_TIMING");
+  const dsdgp_model::Force& f = m->force;
+  FwdIn in{};
+  in.n = c.n; in.S = c.S;
+  in.prepare = prepare; in.save = in.with_grad = save; in.need_last_F = need_last_F; in.lik_target = lik_target; in.sample_w = m->sample_w != nullptr;
+  in.L = m->desc.L; in.white = m->desc.white != 0;
+  in.lik_elementwise = lik_family(m->desc.lik_kind) != LIKF_NONE; in.lik_gaussian = m->desc.lik_kind == DSDGP_LIK_GAUSSIAN;
+  in.grad_first = m->grad_first; in.grad_q_only = m->grad_q_only; in.head_ok = m->head_ok; in.overlap = overlap_on(m, c.n, c.S); in.timing = timing;
+  for (int l = 0; l < in.L; ++l) {
+    const LayerState& St = m->L[l];
+    const LayerDev& v = St.dev;
+    if (c.zs && c.zs[l]) in.caller_z |= 1u << l;
+    in.layer[l] = FwdIn::Layer{v.Mp, v.M, v.D_in, v.D_out, v.kern_kind, St.d.mean_kind, St.prop, St.gemm, v.alg_g != 0, v.need_tpt != 0, St.C != nullptr,
+                               St.bpart != nullptr};
+  }
+  in.force = {f.white_fwd, f.cs_min_blocks, f.cs_min_dout, f.cs_max_dout, f.last_fuse, f.last_min_blocks, f.bwd_split, f.lik_fuse};
+  return in;
 }
 
-// dgp.py:61-76 propagate
-static int forward_layers(dsdgp_model* m, const double* X, int64_t n, int S, const double* const* zs,
-                          const int64_t* zstride, uint64_t seed, bool save, bool need_last_F, double* const* Fs,
-                          double* const* Fmeans, double* const* Fvars, bool z_ready = false, const double* lik_Y = nullptr,
-                          double lik_w = 0.0, int* lik_nblocks = nullptr) {
+// dgp.py:61-76 propagate.  The decisions are fwd_plan's; here: every layer's argument block as the plan says, its launch, and the record
+// of the pass for the reverse pass (dsdgp_model::fwd)
+static int forward_layers(dsdgp_model* m, const FwdCall& c, const FwdIn& in, const FwdPlan& p) {
   dsdgp_ctx* ctx = m->ctx;
   const int L = m->desc.L;
-  DS_CHECK_ARG(n > 0 && n <= m->n_max && S > 0 && S <= m->s_max);
-  const double* Xin = X;
-  // Forward-only evaluations of a non-white model (predict_f, ELBO values) run in WHITENED coordinates: with V_d = Lu^-1 q_sqrt_d and
-  // nL = Lu^-1 q_mu — both formed for the KL term anyway — mean = a1^T nL and var = kdiag - |a1|^2 + |V_d^T a1|^2 (V_d is
-  // lower-triangular like q_sqrt_d), so the chain skips a = Lu^-T a1 (layers.py:188): one of 2 + D_out triangular products per row
-  // block, a third of the MFMA work of a D_out = 1 layer.  The training pass keeps `a` (the reverse pass is written in terms of it).
-  // Mp <= 256: the larger instances read the factor transposed, which exists for q_sqrt only.
-  const bool wf_ok = !m->desc.white && !save && m->force.white_fwd != 0;
-  m->last_deferred = false;
   m->ps.workspace_overwritten();
-  if (wf_ok) DS_TRY(join_prep(m));          // V, nL come from the parameter products (side stream in the overlapped schedule)
+  if (p.join_prep_first) DS_TRY(join_prep(m));
+  const double* Xin = c.X;
+  FwdUsed used[DSDGP_MAX_LAYERS];
+  LayerFwdArgs a{};
   for (int l = 0; l < L; ++l) {
     LayerState& St = m->L[l];
     const LayerDev& v = St.dev;
-    const int64_t Rin = (l == 0) ? n : (int64_t)S * n;
-    const int rep = (l == 0) ? S : 1;
-    const bool last = (l == L - 1);
-    const bool want_F = !last || need_last_F;
-    const bool wf = wf_ok && v.Mp <= 256 && !St.gemm;
-    LayerFwdArgs a{};
-    a.X = Xin; a.Rin = Rin; a.rep = rep;
+    const FwdPlan::Layer& y = p.layer[l];
+    a = LayerFwdArgs{};
+    a.X = Xin; a.Rin = y.Rin; a.rep = y.rep;
     a.D_in = v.D_in; a.D_out = v.D_out; a.M = v.M;
     a.Zp = v.Zp; a.Zs = v.Zs; a.hyp = v.hyp; a.LinvT = v.LinvT; a.Linv = v.Linv; a.Tp = v.Tp; a.TpT = v.TpT; a.qmu = v.qmu;
-    if (wf) { a.Tp = v.V; a.qmu = v.nL; a.qmu_ld = v.DP4; }
+    if (y.whitened) { a.Tp = v.V; a.qmu = v.nL; a.qmu_ld = v.DP4; }
     a.mean_kind = St.d.mean_kind; a.mean_A = St.meanA; a.mean_b = St.meanb;
     a.jitter = m->desc.jitter;
-    a.n_inner = n;
-    a.z = nullptr;
-    if (want_F) {
-      if (zs && zs[l]) {
-        a.z = zs[l];
-        a.zs_s = zstride[3 * l]; a.zs_n = zstride[3 * l + 1]; a.zs_d = zstride[3 * l + 2];
-      } else {
-        if (!(z_ready && !last)) DS_TRY(randn_async(ctx, seed, (uint64_t)l, (int64_t)S * n * v.D_out, St.zbuf));
-        a.z = St.zbuf;
-        a.zs_s = n * v.D_out; a.zs_n = v.D_out; a.zs_d = 1;
-      }
+    a.n_inner = c.n;
+    if (y.draw == DRAW_CALLER) {
+      a.z = c.zs[l];
+      a.zs_s = c.zstride[3 * l]; a.zs_n = c.zstride[3 * l + 1]; a.zs_d = c.zstride[3 * l + 2];
+    } else if (y.draw != DRAW_NONE) {
+      if (y.draw == DRAW_HERE) DS_TRY(randn_async(ctx, c.seed, (uint64_t)l, (int64_t)c.S * c.n * v.D_out, St.zbuf));
+      a.z = St.zbuf;
+      a.zs_s = c.n * v.D_out; a.zs_n = v.D_out; a.zs_d = 1;
     }
-    a.F = want_F ? ((Fs && Fs[l]) ? Fs[l] : St.F) : nullptr;
-    a.mean = (Fmeans && Fmeans[l]) ? Fmeans[l] : St.mean;
-    a.var = (Fvars && Fvars[l]) ? Fvars[l] : St.var;
-    a.ldA = round_up(Rin, 16);
-    const bool save_l = save && (m->desc.white || l >= m->grad_first);    // layers below the pruned reverse pass keep nothing for it
-    a.Asave = save_l ? St.A : nullptr;
-    // c_d is kept for the backward chain where that pays: enough row blocks to hide the extra latency per output (the N-row first
-    // layer is a latency-bound launch) and enough outputs for the halved d-loop to matter
-    // (from Mp = 512 one output's product outlasts the staging latency even on a handful of row blocks: always)
-    St.c_used = save_l && St.C && sm_cs_built(v.Mp) &&
-                (v.Mp > 256 || ((Rin + 15) / 16 > m->force.cs_min_blocks && v.D_out >= m->force.cs_min_dout && v.D_out <= m->force.cs_max_dout));
-    if (St.gemm) St.c_used = save_l && St.C != nullptr;      // the triangular abar product halves the largest GEMM of the reverse pass
-    // (q, q_sqrt)-only gradients: the lowest layer of the reverse pass runs no backward chain (backward_layers), so it keeps neither
-    const bool q_lowest = save_l && m->grad_q_only && !m->desc.white && l == m->grad_first;
-    if (q_lowest) St.c_used = false;
-    a.Csave = St.c_used ? St.C : nullptr;
-    a.XT1 = (save_l && !q_lowest) ? St.XT1 : nullptr;
-    {
-      const int64_t nblk = (Rin + 15) / 16;
-      a.d_split = chain_d_split(nblk, v.D_out);
-      if (last && lik_Y) {      // Gaussian variational expectations + adjoints in this chain's epilogue
-        a.lik_Y = lik_Y; a.lik_const = m->lik_const; a.lik_w = lik_w; a.lik_part = m->lik_part;
-        a.lik_MB = St.MB; a.lik_VB = St.VB; a.lik_ld = round_up(Rin, 16);
-        *lik_nblocks = St.gemm ? layer_gemm_lik_blocks(Rin, v.D_out) : (int)nblk * a.d_split;
-      }
+    a.F = y.want_F ? ((c.Fs && c.Fs[l]) ? c.Fs[l] : St.F) : nullptr;
+    a.mean = (c.Fmeans && c.Fmeans[l]) ? c.Fmeans[l] : St.mean;
+    a.var = (c.Fvars && c.Fvars[l]) ? c.Fvars[l] : St.var;
+    a.ldA = y.ld;
+    a.Asave = y.save_A ? St.A : nullptr; a.Csave = y.save_C ? St.C : nullptr; a.XT1 = y.save_XT1 ? St.XT1 : nullptr;
+    a.d_split = y.d_split;
+    if (y.lik_epilogue) {
+      a.lik_Y = c.lik_Y; a.lik_const = m->lik_const; a.lik_w = c.lik_w; a.lik_part = m->lik_part;
+      a.lik_MB = St.MB; a.lik_VB = St.VB; a.lik_ld = y.ld;
     }
-    if (last && last_chain_fusable(m, St, a)) {
-      m->last_fwd = a;               // launched by backward_layers together with this layer's reverse pass
-      m->last_deferred = true;
-    } else if (St.gemm) DS_TRY(layer_fwd_gemm_launch(ctx, a, v.Mp, v.kern_kind, m->desc.white ? 1 : 0, m->gws));
-    else DS_TRY(layer_fwd_sm_launch(ctx, a, v.Mp, v.kern_kind, m->desc.white || wf));
-    St.z_used = a.z; St.zs_s = a.zs_s; St.zs_n = a.zs_n; St.zs_d = a.zs_d;
-    St.X_used = Xin; St.Rin_used = Rin; St.rep_used = rep; St.ld_used = a.ldA;
-    if (St.prop && !last) {
-      const int64_t R = (int64_t)S * n, cnt = R * (v.D_out + St.prop);
-      DS_LAUNCH(k_concat_prop, dim3((int)std::min<int64_t>(4096, ceil_div(cnt, 256))), dim3(256), 0, ctx->stream, Xin, Rin,
+    switch (y.launch) {
+      case LAUNCH_WITH_REVERSE: break;      // backward_layers launches it together with this layer's reverse pass
+      case LAUNCH_GEMM: DS_TRY(layer_fwd_gemm_launch(ctx, a, v.Mp, v.kern_kind, m->desc.white ? 1 : 0, m->gws)); break;
+      case LAUNCH_CHAIN: DS_TRY(layer_fwd_sm_launch(ctx, a, v.Mp, v.kern_kind, m->desc.white || y.whitened)); break;
+    }
+    used[l] = FwdUsed{a.X, a.z, a.zs_s, a.zs_n, a.zs_d};
+    if (y.concat) {
+      const int64_t R = (int64_t)c.S * c.n, cnt = R * (v.D_out + St.prop);
+      DS_LAUNCH(k_concat_prop, dim3((int)std::min<int64_t>(4096, ceil_div(cnt, 256))), dim3(256), 0, ctx->stream, Xin, y.Rin,
                          v.D_in, St.prop, a.F, v.D_out, R, St.Xcat);
       DS_HIP(hipGetLastError());
       Xin = St.Xcat;
@@ -293,7 +278,57 @@ static int forward_layers(dsdgp_model* m, const double* X, int64_t n, int S, con
       Xin = a.F;
     }
   }
+  m->fwd.forward_done(in, p, used, p.layer[L - 1].launch == LAUNCH_WITH_REVERSE ? &a : nullptr);
   return DSDGP_OK;
+}
+
+// The N(0,1) draws of the inner layers that no explicit zs covers (DRAW_READY), ahead of the factorisation they do not depend on: in
+// spare block columns of the fused head launch (head_rand: the block prepare_async hands it), else — overlapped schedule — on the side
+// stream while Ku is factorised (inner_draws: the caller waits for ev_z behind prepare_async).  Neither: forward_layers draws them itself.
+static HeadRand head_rand(const dsdgp_model* m, const FwdCall& c, const FwdPlan& p) {
+  HeadRand hr{};
+  hr.seed = c.seed; hr.nblk = p.head_nblk;
+  for (int l = 0; l < m->desc.L; ++l)
+    if (p.layer[l].draw == DRAW_READY) {
+      hr.out[l] = m->L[l].zbuf;
+      hr.count[l] = (int64_t)c.S * c.n * m->L[l].dev.D_out;
+    }
+  return hr;
+}
+static int inner_draws(dsdgp_model* m, const FwdCall& c, const FwdPlan& p) {
+  DS_HIP(hipEventRecord(m->ev_fork, m->ctx->stream));     // after the previous step's readers of zbuf
+  DS_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0));
+  for (int l = 0; l < m->desc.L; ++l)
+    if (p.layer[l].draw == DRAW_READY) DS_TRY(randn_async(m->ctx, c.seed, (uint64_t)l, (int64_t)c.S * c.n * m->L[l].dev.D_out, m->L[l].zbuf, m->side));
+  if (p.draws_ahead) DS_HIP(hipEventRecord(m->ev_z, m->side));
+  return DSDGP_OK;
+}
+// The front of every forward pass: the plan; then, where the call prepares (an evaluation, a saved pass), the draws where the plan places
+// them, the minibatch gather, prepare, the wait for the side stream's draws — a call that does not (propagate, the mixtures) only makes
+// sure that the model is prepared; then the chains.  *plan: what was decided, for the caller's likelihood launches.
+static int forward_pass(dsdgp_model* m, const FwdCall& c, const FwdIn& in, const GatherSrc* gs = nullptr, FwdPlan* plan = nullptr) {
+  DS_CHECK_ARG(c.n > 0 && c.n <= m->n_max && c.S > 0 && c.S <= m->s_max);
+  const FwdPlan p = fwd_plan(in);
+  if (in.prepare) {
+    const bool ahead_in_head = p.draws == DRAWS_HEAD && p.draws_ahead;
+    const HeadRand hr = ahead_in_head ? head_rand(m, c, p) : HeadRand{};
+    if (p.draws == DRAWS_SIDE) DS_TRY(inner_draws(m, c, p));
+    HeadGather hg{};
+    if (gs) {
+      const int dx = m->desc.layers[0].D_in, dy = (m->desc.lik_kind == DSDGP_LIK_MULTICLASS) ? 1 : m->desc.layers[in.L - 1].D_out;
+      if (m->head_ok) {
+        hg = HeadGather{gs->Xs, gs->Ys, gs->idx, m->Xmb, m->Ymb, c.n, dx, dy, (int)std::min<int64_t>(16, ceil_div(c.n * (dx + dy), 2 * HEAD_THREADS))};
+      } else {
+        DS_TRY(dsdgp_gather_rows2(m->ctx, gs->Xs, dx, m->Xmb, gs->Ys, dy, m->Ymb, gs->idx, c.n, 0));
+      }
+    }
+    DS_TRY(prepare_async(m, in.with_grad, in.overlap, ahead_in_head ? &hr : nullptr, (gs && m->head_ok) ? &hg : nullptr));
+    if (p.draws == DRAWS_SIDE && p.draws_ahead) DS_HIP(hipStreamWaitEvent(m->ctx->stream, m->ev_z, 0));
+  } else {
+    DS_TRY(ensure_prepared(m));
+  }
+  if (plan) *plan = p;
+  return forward_layers(m, c, in, p);
 }
 
 extern "C" int dsdgp_model_propagate(dsdgp_model* m, const double* X, int64_t n, int32_t S, const double* const* zs,
@@ -301,8 +336,8 @@ extern "C" int dsdgp_model_propagate(dsdgp_model* m, const double* X, int64_t n,
                                      double* const* Fvars) {
   DS_CHECK_ARG(m && X);
   DS_CHECK_ARG(!zs || zstride);
-  DS_TRY(ensure_prepared(m));
-  return forward_layers(m, X, n, S, zs, zstride, seed, false, true, Fs, Fmeans, Fvars);
+  const FwdCall c{X, n, S, zs, zstride, seed, Fs, Fmeans, Fvars, nullptr, 0.0};
+  return forward_pass(m, c, fwd_in(m, c, false, false, true, false));
 }
 
 // The front that the three mixture entries below share: their refusals, then the forward pass of dsdgp_model_propagate with only the
@@ -320,8 +355,8 @@ static int mixture_forward(const char* who, dsdgp_model* m, const double* X, int
                     m->desc.lik_kind);
     return DSDGP_ERR_UNSUPPORTED;
   }
-  DS_TRY(ensure_prepared(m));
-  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, false, true, nullptr, nullptr, nullptr));
+  const FwdCall c{X, n, S, zs, zstride, seed, nullptr, nullptr, nullptr, nullptr, 0.0};
+  DS_TRY(forward_pass(m, c, fwd_in(m, c, false, false, true, false)));
   *last = &m->L[m->desc.L - 1];
   return DSDGP_OK;
 }
@@ -452,9 +487,9 @@ struct BwdSchedule {
   int gfirst; bool overlap, bucketed, pipelined, kinv_only, q_only, defer_upper, red_ahead;
   struct Layer { AdjFrom adj; bool chain; int d_split; ProductsAt products; } layer[DSDGP_MAX_LAYERS];      // entries [gfirst, L)
 };
-static BwdSchedule bwd_schedule(const dsdgp_model* m, int64_t n, int S) {
+static BwdSchedule bwd_schedule(const dsdgp_model* m) {
   const int L = m->desc.L;
-  BwdSchedule s{}; s.overlap = overlap_on(m, n, S);
+  BwdSchedule s{}; s.overlap = overlap_on(m, m->fwd.n, m->fwd.S);
   const int g = s.gfirst = m->desc.white ? 0 : m->grad_first;     // reverse mode stops below this layer (dsdgp_model_set_grad_first_layer)
   // data-parallel buckets: every layer's reduction, products, assembly and hyper-parameter gradients right behind its weight-gradient
   // products, then the caller's collective on that layer's segment of the gradient, on the stream the segment was produced on — the
@@ -482,12 +517,12 @@ static BwdSchedule bwd_schedule(const dsdgp_model* m, int64_t n, int S) {
     const LayerState& St = m->L[l];
     const LayerDev& v = St.dev;
     BwdSchedule::Layer& y = s.layer[l];
-    const bool last = (l == L - 1), produced = last ? m->fused_last : l >= 1;
-    const int64_t nblk = St.ld_used / 16;
+    const bool last = (l == L - 1), produced = last ? m->fwd.adjoints_from_lik : l >= 1;
+    const int64_t nblk = m->fwd.layer[l].ld / 16;
     y.chain = !(s.q_only && l == g);
-    const bool prologue = !produced && !last && y.chain && m->force.adj_fuse != 0 && !St.c_used && !St.gemm && sm_adj_fusable(v.Mp, nblk, v.D_in, v.D_out);
+    const bool prologue = !produced && !last && y.chain && m->force.adj_fuse != 0 && !m->fwd.layer[l].c_saved && !St.gemm && sm_adj_fusable(v.Mp, nblk, v.D_in, v.D_out);
     y.adj = produced ? ADJ_PRODUCER : (prologue ? ADJ_PROLOGUE : ADJ_PREP);
-    y.d_split = bwd_d_split(m, St, nblk);
+    y.d_split = bwd_d_split(m->force.bwd_split, v.Mp, St.bpart != nullptr, nblk, v.D_out);
     // the lowest layer of the reverse pass keeps its products on the main stream: nothing is left to run them under, and the
     // join then waits for side-stream work that finished long ago instead of for a just-in-time signal
     const bool on_main = s.overlap && l == g && L - g > 1;
@@ -497,26 +532,29 @@ static BwdSchedule bwd_schedule(const dsdgp_model* m, int64_t n, int S) {
 }
 
 // argument block of layer l's backward chain
-static LayerBwdArgs fill_bwd_args(const dsdgp_model* m, int l, const BwdSchedule& sc, int64_t n) {
+static LayerBwdArgs fill_bwd_args(const dsdgp_model* m, int l, const BwdSchedule& sc) {
   const LayerState& St = m->L[l];
   const LayerDev& v = St.dev;
+  const auto& R = m->fwd.layer[l];
+  const int64_t n = m->fwd.n;
   LayerBwdArgs b{};
-  b.X = St.X_used; b.Rin = St.Rin_used; b.D_in = v.D_in; b.D_out = v.D_out; b.M = v.M; b.DP4 = v.DP4;
+  b.X = R.X; b.Rin = R.Rin; b.D_in = v.D_in; b.D_out = v.D_out; b.M = v.M; b.DP4 = v.DP4;
   b.Zp = v.Zp; b.Zs = v.Zs; b.hyp = v.hyp; b.Kinv = v.Kinv; b.Linv = v.Linv; b.LinvT = v.LinvT; b.Sd = v.Sd; b.qmu4 = v.qmu4;
-  b.Asave = St.A; b.Csave = St.c_used ? St.C : nullptr; b.Tp = v.Tp; b.TpT = v.TpT; b.ldA = St.ld_used; b.VB = St.VB; b.MB = St.MB;
+  b.Asave = St.A; b.Csave = R.c_saved ? St.C : nullptr; b.Tp = v.Tp; b.TpT = v.TpT; b.ldA = R.ld; b.VB = St.VB; b.MB = St.MB;
   b.E = v.alg_g ? nullptr : St.E; b.GW = St.GW;
   b.dX = (l > sc.gfirst) ? m->L[l - 1].dF : nullptr;
   if (l >= 2 && l > sc.gfirst) {   // the previous layer is an inner layer: hand it its transposed adjoints directly
     const LayerState& Pv = m->L[l - 1];
+    const auto& Rp = m->fwd.layer[l - 1];
     b.dX = nullptr;
     b.MBp = Pv.MB; b.VBp = Pv.VB;
-    b.zp = Pv.z_used; b.zp_s = Pv.zs_s; b.zp_n = Pv.zs_n; b.zp_d = Pv.zs_d; b.n_inner = n;
+    b.zp = Rp.z; b.zp_s = Rp.zs_s; b.zp_n = Rp.zs_n; b.zp_d = Rp.zs_d; b.n_inner = n;
     b.varp = Pv.var; b.Dp = Pv.dev.D_out; b.prop = Pv.prop; b.jitter = m->desc.jitter;
   }
   b.mean_kind = St.d.mean_kind; b.mean_A = St.meanA; b.hyp_part = St.hyp_part;
   if (sc.layer[l].adj == ADJ_PROLOGUE) {
-    b.up_dF = St.dF; b.up_rep = St.rep_used; b.up_ld = v.D_out + St.prop; b.up_off = St.prop;
-    b.up_z = St.z_used; b.up_zs = St.zs_s; b.up_zn = St.zs_n; b.up_zd = St.zs_d; b.up_n_inner = n;
+    b.up_dF = St.dF; b.up_rep = R.rep; b.up_ld = v.D_out + St.prop; b.up_off = St.prop;
+    b.up_z = R.z; b.up_zs = R.zs_s; b.up_zn = R.zs_n; b.up_zd = R.zs_d; b.up_n_inner = n;
     b.up_var = St.var; b.up_jitter = m->desc.jitter; b.MBw = St.MB; b.VBw = St.VB;
   }
   b.d_split = sc.layer[l].d_split; b.part = St.bpart; b.part_cnt = St.bcnt;
@@ -536,7 +574,8 @@ static int launch_reduce(dsdgp_model* m, int first, int end, hipStream_t st) {
 static int launch_wgrad(dsdgp_model* m, const BwdSchedule& sc, int l, hipStream_t st) {
   const LayerState& Sx = m->L[l];
   const bool all = sc.layer[l].chain;
-  return wgrad_launch(m->ctx, Sx.wj, all ? Sx.njobs : Sx.njobsA, all ? Sx.tot_big : Sx.totA, Sx.ns_big, Sx.ld_used, Sx.ld_used, st);
+  const int64_t ld = m->fwd.layer[l].ld;
+  return wgrad_launch(m->ctx, Sx.wj, all ? Sx.njobs : Sx.njobsA, all ? Sx.tot_big : Sx.totA, Sx.ns_big, ld, ld, st);
 }
 // split-K reduction + P_d T_d / GS_d products of one layer right behind its weight-gradient products (pipelined tail); bucketed:
 // its assembly and the caller's collective on its segment of the gradient as well
@@ -599,11 +638,12 @@ static int end_unfused(dsdgp_model* m, hipStream_t st, const LayerDev* lay, int 
 // Every reduction is fixed-order, so the schedule does not change a bit of the result (tests/test_gpu_parity.py:
 // test_stream_overlap_is_bitwise_neutral, tests/test_gpu_round3.py).
 // The decisions are bwd_schedule's; here: wait, the layers (adjoint producer -> chain -> products), reductions, join, ending.
-static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
+static int backward_layers(dsdgp_model* m, double kl_weight) {
   dsdgp_ctx* ctx = m->ctx;
   const int L = m->desc.L;
-  DS_TRY(ensure_plan(m, n, S));
-  const BwdSchedule sc = bwd_schedule(m, n, S);
+  const int64_t n = m->fwd.n;
+  DS_TRY(ensure_plan(m, n, m->fwd.S));
+  const BwdSchedule sc = bwd_schedule(m);
   const int gfirst = sc.gfirst;
   if (sc.kinv_only) DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_kinv, 0));
   else DS_TRY(join_prep(m));
@@ -611,17 +651,18 @@ static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
     LayerState& St = m->L[l];
     const LayerDev& v = St.dev;
     const bool last = (l == L - 1);
-    const int64_t ld = St.ld_used;
+    const auto& R = m->fwd.layer[l];
+    const int64_t ld = R.ld;
     if (sc.layer[l].adj == ADJ_PREP)
       DS_LAUNCH(k_adj_prep, dim3(ceil_div(ld, 256), std::max(v.DP16, v.DinP16)), dim3(256), 0, ctx->stream, last ? nullptr : St.dF,
-                         last ? m->lik_dmean : nullptr, last ? m->lik_dvar : nullptr, St.z_used, St.zs_s, St.zs_n,
-                         St.zs_d, n, St.var, St.X_used, St.Rin_used, St.rep_used, v.D_in, v.D_out, v.DP16, v.DinP16, m->desc.jitter, ld,
+                         last ? m->lik_dmean : nullptr, last ? m->lik_dvar : nullptr, R.z, R.zs_s, R.zs_n,
+                         R.zs_d, n, St.var, R.X, R.Rin, R.rep, v.D_in, v.D_out, v.DP16, v.DinP16, m->desc.jitter, ld,
                          St.MB, St.VB, St.XT1, v.D_out + St.prop, St.prop);
     DS_HIP(hipGetLastError());
-    const LayerBwdArgs b = fill_bwd_args(m, l, sc, n);
-    if (last && m->last_deferred) {
-      DS_TRY(layer_last_launch(ctx, m->last_fwd, b, v.Mp, v.kern_kind, (int)(sm_hyp_parts(ld, v.Mp, v.D_in) / (ld / 16))));
-      m->last_deferred = false;
+    const LayerBwdArgs b = fill_bwd_args(m, l, sc);
+    if (last && m->fwd.last_pending) {
+      DS_TRY(layer_last_launch(ctx, m->fwd.last_fwd, b, v.Mp, v.kern_kind, m->fwd.hyp_rows));
+      m->fwd.last_launched();
     } else if (!sc.layer[l].chain) { /* nothing downstream of this layer's chain is wanted */ }
     else if (St.gemm) DS_TRY(layer_bwd_gemm_launch(ctx, b, v.Mp, v.kern_kind, m->desc.white ? 1 : 0, m->gws));
     else DS_TRY(layer_bwd_sm_launch(ctx, b, v.Mp, v.kern_kind, m->desc.white));
@@ -674,38 +715,6 @@ static int backward_layers(dsdgp_model* m, int64_t n, int S, double kl_weight) {
   return end_unfused(m, ctx->stream, m->layers_dev + gfirst, L - gfirst, kl_weight);
 }
 
-// The N(0,1) draws of the inner layers that no explicit zs covers, ahead of the factorisation they do not depend on: in spare block
-// columns of the fused head launch (*hr filled for prepare_async, *z_head), else — overlapped schedule — on the side stream while Ku is
-// factorised (*z_side: the caller waits for ev_z behind prepare_async).  Neither: forward_layers draws them itself.
-static int inner_draws(dsdgp_model* m, int64_t n, int S, const double* const* zs, uint64_t seed, bool ovl, HeadRand* hrp, bool* z_head_p,
-                       bool* z_side_p) {
-  dsdgp_ctx* ctx = m->ctx;
-  const int L = m->desc.L;
-  bool z_side = false, z_head = false;
-  HeadRand& hr = *hrp;
-  if (m->head_ok) {
-    // ... or, with the fused head launch, in spare block columns of that launch (no second stream, no events)
-    hr.seed = seed;
-    for (int l = 0; l + 1 < L; ++l)
-      if (!(zs && zs[l])) {
-        hr.out[l] = m->L[l].zbuf;
-        hr.count[l] = (int64_t)S * n * m->L[l].dev.D_out;
-        hr.nblk = std::max<int>(hr.nblk, (int)std::min<int64_t>(64, ceil_div((hr.count[l] + 1) / 2, 4 * HEAD_THREADS)));
-        z_head = true;
-      }
-  } else if (ovl) {
-    DS_HIP(hipEventRecord(m->ev_fork, ctx->stream));     // after the previous step's readers of zbuf
-    DS_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0));
-    for (int l = 0; l + 1 < L; ++l)
-      if (!(zs && zs[l])) {
-        DS_TRY(randn_async(ctx, seed, (uint64_t)l, (int64_t)S * n * m->L[l].dev.D_out, m->L[l].zbuf, m->side));
-        z_side = true;
-      }
-    if (z_side) DS_HIP(hipEventRecord(m->ev_z, m->side));
-  }
-  *z_head_p = z_head; *z_side_p = z_side;
-  return DSDGP_OK;
-}
 // the value (and the likelihood parameter's gradient) where the reverse pass's ending has not produced it: m->fin
 static int finish_value(dsdgp_model* m) {
   if (!m->fin.done) {
@@ -715,11 +724,6 @@ static int finish_value(dsdgp_model* m) {
   return DSDGP_OK;
 }
 
-// minibatch to gather before the evaluation (dsdgp_model_train_step_minibatch): rows idx[0..n) of the resident data
-struct GatherSrc {
-  const double *Xs, *Ys;
-  const int64_t* idx;
-};
 static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n, int32_t S, const double* const* zs,
                      const int64_t* zstride, uint64_t seed, double data_scale, double kl_weight, int with_grad, double* out,
                      const GatherSrc* gs) {
@@ -730,53 +734,27 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
     DS_CHECK_ARG(m->grad != nullptr);
   }
   dsdgp_ctx* ctx = m->ctx;
-  const int L = m->desc.L;
-  bool z_side = false, z_head = false;
-  const bool ovl = overlap_on(m, n, S);
-  HeadRand hr{};
-  DS_TRY(inner_draws(m, n, S, zs, seed, ovl, &hr, &z_head, &z_side));
-  HeadGather hg{};
-  if (gs) {
-    DS_CHECK_ARG(n > 0 && n <= m->n_max);
-    const int dx = m->desc.layers[0].D_in, dy = (m->desc.lik_kind == DSDGP_LIK_MULTICLASS) ? 1 : m->desc.layers[L - 1].D_out;
-    if (m->head_ok) {
-      hg = HeadGather{gs->Xs, gs->Ys, gs->idx, m->Xmb, m->Ymb, n, dx, dy, (int)std::min<int64_t>(16, ceil_div(n * (dx + dy), 2 * HEAD_THREADS))};
-    } else {
-      DS_TRY(dsdgp_gather_rows2(ctx, gs->Xs, dx, m->Xmb, gs->Ys, dy, m->Ymb, gs->idx, n, 0));
-    }
+  if (gs) {      // (gathered by forward_pass, on its way to prepare)
     X = m->Xmb;
     Y = m->Ymb;
   }
-  DS_TRY(prepare_async(m, with_grad != 0, ovl, z_head ? &hr : nullptr, (gs && m->head_ok) ? &hg : nullptr));
-  if (z_side) DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_z, 0));
-  LayerState& last = m->L[L - 1];
-  const int DY = last.dev.D_out;
-  const int64_t total = (int64_t)S * n * DY;
-  int nblocks = ceil_div(total, 256);
   const double w = data_scale / (double)S;
-  // the last layer of a deep model has one output row per input row: its transposed adjoints come straight from the
-  // likelihood kernel (no k_adj_prep launch on the critical path) — or, Gaussian likelihood without quadrature weights, from the
-  // last forward chain's own epilogue (no likelihood launch either)
-  const bool elementwise = lik_family(m->desc.lik_kind) != LIKF_NONE;
-  m->fused_last = with_grad && L > 1 && elementwise;
-  const bool lik_in_chain = m->fused_last && m->desc.lik_kind == DSDGP_LIK_GAUSSIAN && !m->sample_w && m->force.lik_fuse != 0;
-  int lik_nb = 0;
-  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, with_grad != 0, false, nullptr, nullptr, nullptr, z_side || z_head,
-                        lik_in_chain ? Y : nullptr, w, &lik_nb));
-  if (lik_in_chain) {
-    nblocks = lik_nb;
-  } else if (elementwise) {
+  const FwdCall c{X, n, S, zs, zstride, seed, nullptr, nullptr, nullptr, Y, w};
+  FwdPlan p;
+  DS_TRY(forward_pass(m, c, fwd_in(m, c, true, with_grad != 0, false, true), gs, &p));
+  LayerState& last = m->L[m->desc.L - 1];
+  const int DY = last.dev.D_out;
+  const bool own_adj = with_grad && !p.adjoints_from_lik;      // the adjoints go to lik_dmean / lik_dvar: k_adj_prep transposes them
+  if (p.lik == LIK_ELEMENTWISE) {
     const int64_t ldt = round_up((int64_t)S * n, 16);
-    if (m->fused_last) nblocks = ceil_div(ldt * DY, 256);
-    double* dm = (with_grad && !m->fused_last) ? m->lik_dmean : nullptr;
-    double* dv = (with_grad && !m->fused_last) ? m->lik_dvar : nullptr;
-    double* mbt = m->fused_last ? last.MB : nullptr;
-    double* vbt = m->fused_last ? last.VB : nullptr;
+    double* mbt = p.adjoints_from_lik ? last.MB : nullptr;
+    double* vbt = p.adjoints_from_lik ? last.VB : nullptr;
     lik_dispatch(m->desc.lik_kind, [&](auto fam) {
-      DS_LAUNCH(k_lik_elbo<decltype(fam)::value>, dim3(nblocks), dim3(256), 0, ctx->stream, (int)m->desc.lik_kind, (const double*)m->lik_const,
-                m->desc.lik_aux, last.mean, last.var, Y, n, S, DY, w, m->sample_w, m->lik_part, dm, dv, mbt, vbt, ldt);
+      DS_LAUNCH(k_lik_elbo<decltype(fam)::value>, dim3(p.lik_nblocks), dim3(256), 0, ctx->stream, (int)m->desc.lik_kind, (const double*)m->lik_const,
+                m->desc.lik_aux, last.mean, last.var, Y, n, S, DY, w, m->sample_w, m->lik_part, own_adj ? m->lik_dmean : nullptr,
+                own_adj ? m->lik_dvar : nullptr, mbt, vbt, ldt);
     });
-  } else {
+  } else if (p.lik == LIK_MULTICLASS) {
     // MultiClass: Y is (n x 1) labels, the last layer has K = num_classes outputs; ve per (s, i) row -> last.F scratch
     DS_CHECK_ARG(DY == m->desc.num_classes);
     const int64_t R = (int64_t)S * n;
@@ -787,14 +765,13 @@ static int elbo_impl(dsdgp_model* m, const double* X, const double* Y, int64_t n
       DS_LAUNCH(k_scale_by_sample, dim3((int)std::min<int64_t>(2048, ceil_div(cnt, 256))), dim3(256), 0, ctx->stream,
                          m->sample_w, n, S, DY, R, last.F, with_grad ? m->lik_dmean : nullptr, with_grad ? m->lik_dvar : nullptr);
     }
-    nblocks = ceil_div(R, 256);
-    DS_LAUNCH(k_partial_sum, dim3(nblocks), dim3(256), 0, ctx->stream, last.F, R, m->lik_part);
+    DS_LAUNCH(k_partial_sum, dim3(p.lik_nblocks), dim3(256), 0, ctx->stream, last.F, R, m->lik_part);
   }
   DS_HIP(hipGetLastError());
-  m->fin.nblocks = nblocks; m->fin.w = w; m->fin.kl_weight = kl_weight; m->fin.with_grad = with_grad; m->fin.out = out;
+  m->fin.nblocks = p.lik_nblocks; m->fin.w = w; m->fin.kl_weight = kl_weight; m->fin.with_grad = with_grad; m->fin.out = out;
   m->fin.done = false;
   if (with_grad) {
-    DS_TRY(backward_layers(m, n, S, kl_weight));
+    DS_TRY(backward_layers(m, kl_weight));
     m->ps.grad_evaluated(pass_is_pruned(m->desc.white, m->grad_first, m->grad_q_only));
   }
   return finish_value(m);
@@ -833,14 +810,8 @@ extern "C" int dsdgp_model_forward_saved(dsdgp_model* m, const double* X, int64_
   DS_CHECK_ARG(n > 0 && n <= m->n_max && S > 0 && S <= m->s_max);
   DS_TRY(vjp_refusals("dsdgp_model_forward_saved", m));
   dsdgp_ctx* ctx = m->ctx;
-  bool z_side = false, z_head = false;
-  const bool ovl = overlap_on(m, n, S);
-  HeadRand hr{};
-  DS_TRY(inner_draws(m, n, S, zs, seed, ovl, &hr, &z_head, &z_side));
-  DS_TRY(prepare_async(m, true, ovl, z_head ? &hr : nullptr, nullptr));
-  if (z_side) DS_HIP(hipStreamWaitEvent(ctx->stream, m->ev_z, 0));
-  m->fused_last = false;
-  DS_TRY(forward_layers(m, X, n, S, zs, zstride, seed, true, false, nullptr, nullptr, nullptr, z_side || z_head));
+  const FwdCall c{X, n, S, zs, zstride, seed, nullptr, nullptr, nullptr, nullptr, 0.0};
+  DS_TRY(forward_pass(m, c, fwd_in(m, c, true, true, false, false)));
   const LayerState& last = m->L[m->desc.L - 1];
   const size_t bytes = (size_t)S * n * last.dev.D_out * sizeof(double);
   if (mean_out) DS_HIP(hipMemcpyAsync(mean_out, last.mean, bytes, hipMemcpyDeviceToDevice, ctx->stream));
@@ -866,10 +837,10 @@ extern "C" int dsdgp_model_backward_adjoints(dsdgp_model* m, const double* dmean
   DS_LAUNCH(k_seed_adjoints, dim3((int)std::min<int64_t>(2048, ceil_div(count, 256))), dim3(256), 0, ctx->stream, dmean, dvar, count,
             m->lik_dmean, m->lik_dvar);
   DS_HIP(hipGetLastError());
-  m->fused_last = false;
+  m->fwd.adjoints_from_caller();
   m->fin.nblocks = 0; m->fin.w = 0.0; m->fin.kl_weight = kl_weight; m->fin.with_grad = 1; m->fin.out = out;
   m->fin.done = false;
-  DS_TRY(backward_layers(m, n, S, kl_weight));
+  DS_TRY(backward_layers(m, kl_weight));
   m->ps.grad_evaluated(false);
   DS_TRY(finish_value(m));
   // every ending writes -w * (sum of no partials) * sigmoid(raw) = -0.0 there: the entry is +0.0

@@ -1,5 +1,6 @@
-// Descriptors of the model path: host-side layer and model state, the DSDGP_FORCE table, the size policies of the chains (Csave, d-split,
-// blocked factorisation).  LayerDev, the job records and the split counts: plan_types.hpp / model_plan.hpp.  Part of the model translation unit.
+// Descriptors of the model path: host-side layer and model state, the DSDGP_FORCE table, the size policy of the blocked factorisation
+// (those of the chains — Csave, d-split — are chain_policy.hpp's).  LayerDev, the job records and the split counts: plan_types.hpp /
+// model_plan.hpp.  Part of the model translation unit.
 #pragma once
 #define NPART 32
 #define PREP_BLOCKS 64      // minimum; large models take more (dsdgp_model::prep_blocks: ~2048 elements of q_sqrt per thread block pass)
@@ -31,14 +32,6 @@ struct LayerState : PlanBufs {      // (operands and partial buffers of the weig
   int lq_nf = 0, lq_tf = 0, lq_n1 = 0, lq_t1 = 0, lq_n2 = 0, lq_t2 = 0, lq_np = 0, lq_tp = 0;   // forward / U, n, KS / U U^T / P_d T_d, GS_d
   WgradJob* wj;     // weight-gradient jobs of ONE launch per layer, rebuilt when (n, S) changes: [A | B] (plan_layer, model_plan.hpp)
   int ns_big, tot_big;
-  // z actually used by the last forward (for the backward pass)
-  const double* z_used;
-  int64_t zs_s, zs_n, zs_d;
-  const double* X_used;
-  int64_t Rin_used;
-  int rep_used;
-  int64_t ld_used;
-  bool c_used = false;   // the last forward stored c_d (Csave) for the backward chain
   bool gemm = false;     // this layer's passes are whole-layer GEMMs (layer_gemm.hip) instead of the fused chains
 };
 
@@ -87,9 +80,7 @@ struct dsdgp_model {
   double *Xmb = nullptr, *Ymb = nullptr;   // gathered minibatch of dsdgp_model_train_step_minibatch (n_max x D_in of layer 0 / x DY)
   bool head_ok = false;         // every layer has Mp <= 128 and D_in <= 16: parameter transforms, Ku, its factorisation and inverse
                                 // factor (and the inner layers' N(0,1) draws) in ONE launch (k_head, head_impl.hpp)
-  bool last_deferred = false;   // the last layer's forward chain was not launched by forward_layers: it runs fused with its reverse pass (layer_last.hip)
-  LayerFwdArgs last_fwd;        //   ... with these arguments
-  bool fused_last = false;      // the last layer's MB / VB were written by the likelihood kernel of this step
+  FwdRecord<LayerFwdArgs> fwd;  // what the reverse pass reads of the last forward pass: written by its transitions only (forward_plan.hpp)
   // arguments of the pending k_finalize (value + likelihood-variance gradient): launched on the side stream beside the
   // backward chain when streams overlap, otherwise on the main stream after it
   struct { int nblocks; double w, kl_weight; int with_grad; double* out; bool done; } fin;
@@ -150,24 +141,6 @@ struct Bump {
   }
 };
 
-// Csave backward chain: the forward chain keeps c_d = q_sqrt_d^T a (D_out x Mp doubles per row) so that the backward chain's
-// abar = sum_d 2 vbar_d S_d a becomes the triangular product sum_d q_sqrt_d (2 vbar_d c_d): half the MFMAs of that loop.  Measured
-// (profiles/r02_fp64_mfma_notes.md): a clear win from Mp = 512 (cfg 4 +10 %, cfg 5 +14 %); at Mp = 128 / 256 the d-loop turns from
-// MFMA-throughput-bound into latency-bound and the chain gets no faster, so those sizes keep the S_d form.
-static bool save_c_enabled(const dsdgp_model* m, int Mp) {
-  return m->force.save_c >= 2 || (m->force.save_c == 1 && Mp > 256);
-}
-// workgroups per row block of a chain launch with few row blocks (the d-split).  < 256 row blocks (first layers, small shards): up to
-// four, ~512 workgroups.  256..511 row blocks (the per-GPU shards of configs 4 / 5: two rounds on 256 CUs, the second a quarter to a
-// half full): two or three pack better, but every workgroup repeats the prologue (Kuf tile and the two triangular chains), so only
-// when each keeps at least five outputs (measured: config 4, D_out = 30, -6.6 % per step; config 5, D_out = 8, +6.7 % without the rule)
-static int chain_d_split(int64_t nblk, int D_out) {
-  int ds = 1;
-  if (nblk < 256) ds = (int)std::min<int64_t>(4, std::max<int64_t>(1, 512 / nblk));
-  else if (nblk < 512) ds = (int)std::min<int64_t>(1024 / nblk, D_out / 5);
-  if (ds > D_out) ds = D_out;
-  return ds < 1 ? 1 : ds;
-}
 // padded inducing count from which the multi-workgroup blocked Cholesky / inverse (look-ahead sequence, linalg.hip) replaces the
 // one-workgroup kernel: 192 (Mp a multiple of 64).  Measured, factor + inverse of one matrix: Mp = 192 180 -> 77 us, 256 371 -> 101,
 // 448 1990 -> 181.  Layers that share M are factorised as ONE batch.

@@ -233,7 +233,7 @@ def assert_same_bits(got, want, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# Mirrors of the shape-dependent switches (csrc/layer_sm.hip: sm_small / sm_nw; model_types.hpp: chain_d_split; model_schedule.hpp:
+# Mirrors of the shape-dependent switches (csrc/chain_policy.hpp: sm_small / sm_nw, chain_d_split; model_schedule.hpp:
 # overlap_on with the default overlap_min) for the tables above.
 def padded_M(M):
     if M <= 32:

@@ -1,6 +1,6 @@
 """The large-launch chain instances at a padded inducing count of 128, against the oracle.
 
-At Mp = 128 the chain kernels pick their instance by the number of 16-row blocks of a launch (csrc/layer_sm.hip: sm_small / sm_nw):
+At Mp = 128 the chain kernels pick their instance by the number of 16-row blocks of a launch (csrc/chain_policy.hpp: sm_small / sm_nw):
 the forward chain takes the 8-wave instance up to 160 row blocks and the 4-wave one (early-mean form) beyond, the backward chain the
 8-wave instance up to 768 row blocks and the 4-wave one (paired d-loop) beyond.  Every other M = 128 test of the suite stays on the
 8-wave side except the two full-size config-2 tests, which cover one point of the 4-wave side (RBF, white = False, D_out 8 and 1,
@@ -34,8 +34,8 @@ from tests.test_gpu_parity import _grad_check
 
 pytestmark = pytest.mark.gpu
 
-FWD_8W_BLOCKS = 160      # layer_sm.hip: SM_SMALL_BLOCKS
-BWD_8W_BLOCKS = 768      # layer_sm.hip: SM_BWD_RESIDENT_8W
+FWD_8W_BLOCKS = 160      # chain_policy.hpp: SM_SMALL_BLOCKS
+BWD_8W_BLOCKS = 768      # chain_policy.hpp: SM_BWD_RESIDENT_8W
 N_BWD, N_FWD, S4 = 3073, 641, 4
 
 

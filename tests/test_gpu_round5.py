@@ -208,7 +208,7 @@ def test_largest_inducing_count_mp_2048():
 
 
 # ---------------------------------------------------------------- backward chain at M = 128 on more row blocks than one round of the
-# 8-wave instance holds (> 768): the 4-wave instance with the paired d-loop (layer_sm.hip: SM_BWD_RESIDENT_8W)
+# 8-wave instance holds (> 768): the 4-wave instance with the paired d-loop (chain_policy.hpp: SM_BWD_RESIDENT_8W)
 @pytest.mark.parametrize("white", [False, True])
 def test_backward_chain_m128_beyond_one_resident_round(white):
     """(S n)/16 = 782 row blocks for the inner layers: dl/d(everything) against the oracle's reverse pass (layers.py:71-114 through

@@ -6,11 +6,11 @@ of those conditions are the functions below (`chunks`, `fast_path`, `tail_steps`
 that the CPU test can say which case runs which branch:
 
     D_in <= 8 | > 8          head launch: two or four k-steps of the Ku Gram block          (head_impl.hpp, head_factor)
-    D_in <= 16 | > 16        head launch on / off (HEAD_MAX_DIN), fused last layer built    (model.hip head_ok, layer_last.hip layer_last_built)
+    D_in <= 16 | > 16        head launch on / off (HEAD_MAX_DIN), fused last layer built    (model.hip head_ok, chain_policy.hpp layer_last_built)
     D_in + 1 <= 16 | > 16    DinP16 = round_up(D_in + 1, 16): 16 -> 32 between 15 and 16    (model_layout.hpp; thinz / WZ / XT1 products)
     D_in <= 32 | > 32        fused tail and folded Ku-side adjoints on / off (WIDE_DIN)     (model.hip tail_ok, model_kernels.hpp)
     D_in <= 64 | > 64        narrow | WIDE chain instances (XCH), 8-wave instances and the
-                             adjoint prologue off above                                     (layer_sm.hip sm_small / sm_nw / sm_adj_fusable)
+                             adjoint prologue off above                                     (chain_policy.hpp sm_small / sm_nw / sm_adj_fusable)
     per 64-column chunk      whole groups of 16 with D_in % 4 == 0: the 32-byte-load path,
                              else the masked path; a last group of fewer than 16 dimensions
                              issues ns = 1 .. 3 k-steps                                     (sm_sqdist, sqdist_chunk_masked)
@@ -42,8 +42,8 @@ XCH = 64            # layer_sm_impl.hpp: columns of x / l staged per chunk
 HEAD_MAX_DIN = 16   # head_impl.hpp
 HEAD_MAX_N = 128    # head_impl.hpp
 WIDE_DIN = 32       # model_types.hpp
-SM_SMALL_BLOCKS = 160       # layer_sm.hip
-SM_BWD_RESIDENT_8W = 768    # layer_sm.hip
+SM_SMALL_BLOCKS = 160       # chain_policy.hpp
+SM_BWD_RESIDENT_8W = 768    # chain_policy.hpp
 
 Case = namedtuple("Case", "name widths M Mp N S kind white ard force two_steps comment")
 

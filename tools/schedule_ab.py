@@ -15,7 +15,8 @@ step).  Per (case, setting) the file holds
   launches           dsdgp_launch_count of the evaluation and of each step
   workspace          dsdgp_model_workspace_bytes of the model
   buckets            (bucket case) the (bucket, offset, count) triples the callback was handed
-The walk case holds, per call of its sequence (cNN_<call>_<what>), the result scalars, gradient, theta or propagated arrays, and in
+The cases with draws from a seed or input propagation also hold the arrays of one propagate (prop_*) and, last in `launches`, its count.
+The walk and vjp cases hold, per call of their sequence (cNN_<call>_<what>), the result scalars, gradient, theta or propagated arrays, and in
 `launches` the launch count of every call: which launches each state of the model leads to.
 `--compare` exits non-zero unless every array of the two files is equal (np.array_equal; NaNs in the same places count as equal)."""
 import argparse
@@ -56,6 +57,16 @@ CASES = {
     "L2.Mp320": dict(N=128, D=3, M=310, S=2, L=2),
     # what a prepare keeps (csrc/prepare_plan.hpp): the walk of tests/test_gpu_prepare_walk.py, bits and launch count of every call
     "L3.M20.walk": dict(N=40, D=3, M=20, S=2, L=3, walk=True),
+    # forward-side decisions (csrc/forward_plan.hpp) the cases above leave where they are: input propagation (the concat launch between
+    # the layers); draws of every inner layer from a fixed seed (head launch; at M = 180 the side stream, once the streams overlap) or
+    # of some layers only (layer 1's from the seed); a saved forward pass and its reverse pass from the caller's adjoints (a second
+    # pair at a smaller shape behind the first)
+    "L3.prop": dict(N=90, D=2, M=14, S=3, L=3, prop=True),
+    "L3.M20.seed": dict(N=100, D=3, M=20, S=3, L=3, draws="seed"),
+    "L3.Mp192.seed": dict(N=256, D=3, M=180, S=8, L=3, draws="seed"),
+    "L3.M20.some": dict(N=100, D=3, M=20, S=3, L=3, draws="some"),
+    "L3.M20.vjp": dict(N=100, D=3, M=20, S=3, L=3, vjp=True),
+    "L2.M128.vjp": dict(N=512, D=5, M=128, S=4, L=2, vjp=True, draws="seed"),
 }
 SETTINGS = {
     "default": {},
@@ -75,6 +86,8 @@ SETTINGS = {
     "head=0": {"DSDGP_FORCE": "head=0"},
     "gemm_mp=16": {"DSDGP_FORCE": "gemm_mp=16"},
     "bwd_split+save_c": {"DSDGP_FORCE": "bwd_split=2,save_c=2,cs_min_blocks=0,cs_min_dout=1"},
+    "white_fwd=0": {"DSDGP_FORCE": "white_fwd=0"},
+    "lik_fuse=0": {"DSDGP_FORCE": "lik_fuse=0"},
 }
 
 
@@ -115,6 +128,49 @@ def run_walk(eng, X, Y, zs, S):
     return res
 
 
+def run_vjp(eng, X, Y, zs, S, seed):
+    """a gradient evaluation; a saved forward pass and its reverse pass from the caller's adjoints; the pair again on the first
+    half of the rows and one sample less, draws from the seed; a gradient evaluation: results and launch count of every call"""
+    count = eng.lib.dsdgp_launch_count
+    rng = np.random.RandomState(3)
+    res, launches = {}, []
+    DY = Y.shape[1]
+
+    def call(what, fn):
+        i, n0 = len(launches), count()
+        got = fn()
+        eng.ctx.sync()
+        launches.append(count() - n0)
+        for k, v in got.items():
+            res[f"c{i:02d}_{what}_{k}"] = v
+
+    def grad():
+        out4 = eng.elbo(X, Y, S, zs=zs, seed=seed, data_scale=5.0, with_grad=True)
+        return {"out4": np.array(out4), "grad": eng.grad.cpu().numpy().copy()}
+
+    def pair(Xp, Sp, zp):
+        got = {}
+
+        def fwd():
+            got["mean"], got["var"] = eng.forward_saved(Xp, Sp, zs=zp, seed=seed)
+            return {k: v.cpu().numpy().copy() for k, v in got.items()}
+
+        def bwd():
+            out4 = eng.backward_adjoints(rng.randn(Sp, Xp.shape[0], DY), rng.randn(Sp, Xp.shape[0], DY))
+            return {"out4": np.array(out4), "grad": eng.grad.cpu().numpy().copy()}
+
+        return fwd, bwd
+
+    h = X.shape[0] // 2
+    f1, b1 = pair(X, S, zs)
+    f2, b2 = pair(X[:h], S - 1, None)
+    for what, fn in (("G", grad), ("saved", f1), ("adjoints", b1), ("saved_small", f2), ("adjoints_small", b2), ("G", grad)):
+        call(what, fn)
+    res["launches"] = np.array(launches, dtype=np.int64)
+    res["workspace"] = np.array([eng.workspace.numel() - 256])
+    return res
+
+
 def run_case(c):
     """arrays of one case under the environment as it stands"""
     from doubly_stochastic_dgp import _lib
@@ -131,8 +187,15 @@ def run_case(c):
     kw = {}
     if c.get("linear_mean"):
         kw["mean_function"] = Linear(0.3 * rng.randn(D, DY), 0.5 * rng.randn(DY))
-    model = DGP(X, Y, Z, kernels, MultiClass(classes) if classes else Gaussian(variance=0.2), white=bool(c.get("white")),
-                num_outputs=classes, num_samples=S, num_data=5 * N, **kw)
+    if c.get("prop"):      # every inner layer forwards the D inputs beside its own outputs (widths D + 3, D + 2)
+        from doubly_stochastic_dgp.dgp import DGP_Base
+        from doubly_stochastic_dgp.layer_initializations import init_layers_input_prop
+        kernels = [RBF(D, variance=1.3, lengthscales=0.9), Matern52(D + 3, variance=0.8, lengthscales=1.4), RBF(D + 2, variance=1.1, lengthscales=1.2)]
+        np.random.seed(5)      # the inducing inputs of the propagated columns come from numpy's global generator
+        model = DGP_Base(X, Y, Gaussian(variance=0.2), init_layers_input_prop(X, Y, Z, kernels), num_samples=S, num_data=5 * N)
+    else:
+        model = DGP(X, Y, Z, kernels, MultiClass(classes) if classes else Gaussian(variance=0.2), white=bool(c.get("white")),
+                    num_outputs=classes, num_samples=S, num_data=5 * N, **kw)
     for layer in model.layers:
         layer.q_mu = 0.3 * rng.randn(*layer.q_mu.shape)
         q = np.asarray(layer.q_sqrt.value)
@@ -140,9 +203,16 @@ def run_case(c):
         if c.get("walk"):      # well-conditioned, so that the natural-gradient step on an inner layer is not refused
             layer.q_sqrt = 0.7 * np.tile(np.eye(q.shape[1]), (q.shape[0], 1, 1)) + np.tril(rng.randn(*q.shape)) / q.shape[1]
     zs = [rng.randn(S, N, layer.num_outputs) for layer in model.layers]
+    if c.get("draws") == "seed":
+        zs = None
+    elif c.get("draws") == "some":
+        zs[1] = None
+    seed = 4242      # fixed: what zs leaves open is drawn from it, the same numbers in both builds
     eng = model.engine()
     if c.get("walk"):
         return run_walk(eng, X, Y, zs, S)
+    if c.get("vjp"):
+        return run_vjp(eng, X, Y, zs, S, seed)
     handed = []
     if c.get("buckets"):
         def on_bucket(user, bucket, ptr, count, stream):      # no exchange: the step's own results must not depend on the callback
@@ -153,7 +223,7 @@ def run_case(c):
         eng._post_create[0](eng)      # the device model exists since Engine(): install now, the hook re-installs after a re-creation
     count = eng.lib.dsdgp_launch_count
     launches = [count()]
-    out4 = eng.elbo(X, Y, S, zs=zs, data_scale=5.0, with_grad=True, grad_from_layer=c.get("grad_first", 0),
+    out4 = eng.elbo(X, Y, S, zs=zs, seed=seed, data_scale=5.0, with_grad=True, grad_from_layer=c.get("grad_first", 0),
                     grad_q_only=bool(c.get("q_only")))
     launches.append(count())
     res = {"out4": np.array(out4), "grad": eng.grad.cpu().numpy().copy(), "workspace": np.array([eng.workspace.numel() - 256])}
@@ -161,12 +231,18 @@ def run_case(c):
         res["buckets"] = np.array(handed, dtype=np.int64)
     if not c.get("grad_first"):
         for _ in range(3):
-            eng.train_step(X, Y, S, zs=zs, data_scale=5.0, lr=0.01)
+            eng.train_step(X, Y, S, zs=zs, seed=seed, data_scale=5.0, lr=0.01)
             eng.ctx.sync()
             launches.append(count())
         res["theta"] = eng.theta.cpu().numpy().copy()
         res["out4_step3"] = eng.out4.cpu().numpy().copy()
     res["launches"] = np.diff(np.array(launches, dtype=np.int64))
+    if c.get("prop") or c.get("draws"):      # the forward-only plan of the same model: every layer's sample, mean and variance
+        n0 = count()
+        for k, ts in zip(("F", "mean", "var"), eng.propagate(X, S, zs=zs, seed=seed)):
+            for l, t in enumerate(ts):
+                res[f"prop_{k}{l}"] = t.cpu().numpy().copy()
+        res["launches"] = np.append(res["launches"], count() - n0)
     return res
 
 
