@@ -132,25 +132,39 @@ def positive_backward_np(y):
 # (consumed at layers.py:161,171,184,213 through feature.Kuu/Kuf, kern.K, kern.Kdiag)
 # --------------------------------------------------------------------------------------------------
 class Kern:
-    """kind in {'rbf','matern52'}; optional White summand (k + White) -> white_variance."""
+    """kind in {'rbf','matern52'}; optional White summand (k + White) -> white_variance.
 
-    def __init__(self, kind, input_dim, variance=1.0, lengthscales=1.0, ARD=False, white_variance=None):
+    sqdist: "upstream" (default: what GPflow computes), "clamped" (the form the device documents: the same expansion, clamped
+    at 0 and exactly 0 on the diagonal of K(X, X)) or "direct" (differences of the scaled coordinates).  The last two exist for
+    inputs far from the origin, where the upstream form goes negative (tests/shift_reference.py)."""
+
+    def __init__(self, kind, input_dim, variance=1.0, lengthscales=1.0, ARD=False, white_variance=None, sqdist="upstream"):
+        if sqdist not in ("upstream", "clamped", "direct"):
+            raise ValueError(sqdist)
+        self.sqdist = sqdist
         self.kind, self.input_dim, self.ARD = kind, int(input_dim), bool(ARD)
         self.variance = variance
         self.lengthscales = lengthscales
         self.white_variance = white_variance      # None: no White summand
 
     def _sqdist(self, xp, X, X2):
-        # [UPSTREAM] Stationary.square_dist: expand-the-square form on X/ℓ, no clamp
+        # [UPSTREAM] Stationary.square_dist: expand-the-square form on X/ℓ, no clamp (sqdist = "upstream"; see the class docstring)
         ls = self.lengthscales
         Xs = X / ls
+        if self.sqdist == "direct":
+            X2s = Xs if X2 is None else X2 / ls
+            return xp.sum((Xs[:, None, :] - X2s[None, :, :]) ** 2, 2)
         Xss = xp.sum(Xs * Xs, 1)
         if X2 is None:
             d = -2.0 * (Xs @ xp.t(Xs))
-            return d + Xss[:, None] + Xss[None, :]
+            r2 = d + Xss[:, None] + Xss[None, :]
+            if self.sqdist == "clamped":
+                r2 = xp.clip_min(r2, 0.0) * (1.0 - xp.eye(X.shape[0]))
+            return r2
         X2s = X2 / ls
         X2ss = xp.sum(X2s * X2s, 1)
-        return -2.0 * (Xs @ xp.t(X2s)) + Xss[:, None] + X2ss[None, :]
+        r2 = -2.0 * (Xs @ xp.t(X2s)) + Xss[:, None] + X2ss[None, :]
+        return xp.clip_min(r2, 0.0) if self.sqdist == "clamped" else r2
 
     def K(self, xp, X, X2=None):
         r2 = self._sqdist(xp, X, X2)

@@ -6,7 +6,8 @@ free variables GPflow would optimise):
 spec  = {"jitter": 1e-6, "white": False, "likelihood": "gaussian"|"multiclass"|"bernoulli"|"poisson"|"exponential"|"student_t"|"gamma"|"beta",
          "num_classes": K, "lik_aux": Poisson binsize / StudentT deg_free (optional),
          "layers": [{"kind": "rbf"|"matern52", "input_dim": D_in, "ARD": bool, "has_white": bool,
-                     "mean": "zero"|"identity"|"linear", "mean_A": ndarray|None, "kvar_identity": bool (optional)}, ...]}
+                     "mean": "zero"|"identity"|"linear", "mean_A": ndarray|None, "kvar_identity": bool (optional)}, ...],
+         "sqdist": "upstream" (default) | "clamped" | "direct" (optional: dgp_oracle.Kern)}
 state = {"l{i}.Z": (M,D_in), "l{i}.q_mu": (M,D_out), "l{i}.q_sqrt": (D_out,M,M)  [tril part is the free var],
          "l{i}.kern_variance_raw": (), "l{i}.kern_lengthscales_raw": () or (D_in,),
          "l{i}.white_variance_raw": () [if has_white], "lik_variance_raw": () [gaussian: variance; student_t / beta: scale; gamma: shape]}
@@ -64,7 +65,7 @@ def build(xp, spec, state, num_samples=1, num_data=None, sample_weights=None):
                       variance=(g("kern_variance_raw") if ls.get("kvar_identity")
                                 else O.positive_forward(xp, g("kern_variance_raw"))),
                       lengthscales=O.positive_forward(xp, g("kern_lengthscales_raw")),
-                      ARD=ls["ARD"],
+                      ARD=ls["ARD"], sqdist=spec.get("sqdist", "upstream"),
                       white_variance=(O.positive_forward(xp, g("white_variance_raw"))
                                       if ls.get("has_white") else None))
         if ls.get("mean_trainable"):

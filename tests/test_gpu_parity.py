@@ -116,7 +116,8 @@ def test_gram(ctx, kind, ard):
     _lib.check(ctx.lib.dsdgp_gram(ctx.handle, C.byref(spec), _p(dX), n, _p(dX2), n2, 0.0, _p(out), n2))
     _lib.check(ctx.lib.dsdgp_gram(ctx.handle, C.byref(spec), _p(dX), n, None, 0, 1e-6, _p(outs), n))
     ctx.sync()
-    # direct-difference r2 (HIP) vs expand-the-square r2 (GPflow form in the oracle): ~1e-15 * |x|^2 apart
+    # at D = 8 both sides expand the square (the device on the MFMA pipe since round 3, clamped at 0 with an exact diagonal; the
+    # oracle in GPflow's form): two summation orders of one expansion, ~1e-15 * |x|^2 apart.  Direct differences only from D = 33
     assert_allclose(out.cpu().numpy(), k.K(O.NP, X, X2), rtol=1e-11, atol=1e-13)
     Ks = outs.cpu().numpy()
     assert_allclose(Ks, k.K(O.NP, X) + 1e-6 * np.eye(n), rtol=1e-11, atol=1e-13)
