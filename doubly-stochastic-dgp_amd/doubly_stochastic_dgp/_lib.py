@@ -168,7 +168,14 @@ _PROTOS = {
     "dsdgp_collapsed_adjoints": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
-    "dsdgp_model_set_grad_first_layer": (C.c_int, [C.c_void_p, C.c_int32]),
+    # the reverse pass tf.gradients builds through kern.K of the dense layers (layers.py:278-279, 320-342; model_zoo.py:60-88)
+    "dsdgp_gram_grad": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    # multivariate_normal of layers.py:342 summed over the outputs
+    "dsdgp_gpr_bound": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    # layers.py:333-334
+    "dsdgp_gpr_var": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),
+    "dsdgp_model_set_grad_first_layer":(C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),
     "dsdgp_model_theta_changed": (C.c_int, [C.c_void_p]),

@@ -120,6 +120,27 @@ class Context:
                                                      p("psi0", psi0, (1,)), s2, p("g_psi2", g_psi2, MM), p("d_Kuu", d_Kuu, MM),
                                                      p("out", out, (8,))))
 
+    def gram_grad(self, spec, X, X2, G, d_X=None, d_X2=None, d_kern=None):
+        """the reverse pass of gram: G (n, n2) the adjoint of K(X, X2), or (n, n) of K(X, X) + diag with X2 None; each output may be None.
+        d_kern (2 + lengthscale entries): variance, lengthscales, the diagonal add"""
+        n, n2, D = X.shape[0], 0 if X2 is None else X2.shape[0], spec.input_dim
+        x2 = None if X2 is None else self._p("gram_grad: X2", X2, (n2, D), True)[0]
+        opt = lambda k, t, shape: None if t is None else self._p("gram_grad: " + k, t, shape, True)[0]
+        nk = 2 + (D if spec.ard else 1)
+        _lib.check(self.lib.dsdgp_gram_grad(self.handle, C.byref(spec), self._p("gram_grad: X", X, (n, D), True)[0], n, x2, n2,
+                                            *self._p("gram_grad: G", G, (n, n2 or n)), opt("d_X", d_X, (n, D)),
+                                            opt("d_X2", d_X2, (n2, D)), opt("d_kern", d_kern, (nk,))))
+
+    def gpr_bound(self, L, V, out):                          # out (4): the bound and its three terms, from L = chol(K + s2 I), V = L^-1 (Y - m)
+        n, DY = V.shape
+        _lib.check(self.lib.dsdgp_gpr_bound(self.handle, n, DY, *self._p("gpr_bound: L", L, (n, n)), *self._p("gpr_bound: V", V, (n, DY)),
+                                            self._p("gpr_bound: out", out, (4,), True)[0]))
+
+    def gpr_var(self, A, kdiag, var):                        # var (ns, DY) = kdiag - colsum(A^2), A = L^-1 K(F, X*) (n, ns)
+        (n, ns), DY = A.shape, var.shape[1]
+        _lib.check(self.lib.dsdgp_gpr_var(self.handle, n, ns, DY, *self._p("gpr_var: A", A, (n, ns)), kdiag,
+                                          self._p("gpr_var: var", var, (ns, DY), True)[0]))
+
     def prof_enable(self, on=True):
         _lib.check(self.lib.dsdgp_prof_enable(self.handle, int(on)))
 

@@ -1,7 +1,8 @@
 """Host mirror of the reference's layer classes (layers.py:36-246): `Layer`, `SVGP_Layer` with the same constructor,
 attributes (`q_mu`, `q_sqrt`, `feature.Z`, `kern`, `mean_function`, `num_outputs`, `white`) and methods
-(`conditional_ND`, `conditional_SND`, `sample_from_conditional`, `KL`), and of the collapsed layers `Collapsed_Layer`, `SGPR_Layer`
-(layers.py:296-307, 345-367, 371-525).  All arithmetic runs in libdsdgp (HIP)."""
+(`conditional_ND`, `conditional_SND`, `sample_from_conditional`, `KL`), of the collapsed layers `Collapsed_Layer`, `SGPR_Layer`
+(layers.py:296-307, 345-367, 371-525) and of the dense layers `GPMC_Layer`, `GPR_Layer` (layers.py:263-293, 310-342).  All arithmetic
+runs in libdsdgp (HIP)."""
 import ctypes as C
 
 import numpy as np
@@ -191,6 +192,168 @@ def kernel_expectations_grad(kern, Z, X_mean, X_var, g_psi0, g_psi1, g_psi2, on_
     return out if on_device else _to_host(ctx, out, ("variance",))
 
 
+_KERN_KIND = {"rbf": _lib.KERN_RBF, "matern52": _lib.KERN_MATERN52}
+
+
+def _kernel_spec(kern):
+    """(KernelSpec, its lengthscale array — keep it alive) of an RBF or Matern52 kernel, with or without a White part, at the
+    kernel's current values"""
+    stat, white = split_kernel(kern)
+    ls = np.ascontiguousarray(np.asarray(stat.lengthscales.value, dtype=np.float64).reshape(-1))
+    spec = _lib.KernelSpec(kind=_KERN_KIND[stat.kind], input_dim=int(stat.input_dim), ard=int(stat.ARD), has_white=int(white is not None),
+                           variance=float(stat.variance.value), white_variance=float(white.variance.value) if white is not None else 0.0,
+                           lengthscales=ls.ctypes.data_as(_lib.c_double_p))
+    return spec, ls
+
+
+def kernel_gram_grad(kern, X, X2, G, on_device=False):
+    """The reverse pass of the kernel's Gram matrix (dsdgp_gram_grad): G is the adjoint, for a scalar F, of K(X, X2) (N, N2) — or, with
+    X2=None, of K(X, X) + diag I (N, N; G need not be symmetric), diag the White variance plus any jitter.  Returns the gradients of F as
+    a dict: `X` (N, D), `X2` (N2, D; None with X2=None), `variance` (a number), `lengthscales` (D entries with ARD, else one) and `diag`
+    (a number): the gradient in what is added to the diagonal — the White variance, a jitter, a noise variance — sum_i G_ii with X2=None,
+    0 otherwise.  kern: RBF or Matern52 (input_dim <= 32), with or without a White part.  X, X2, G: numpy arrays or device tensors;
+    on_device: return device tensors (the numbers of shape (1,)) without waiting for them.  The same arguments give the same bits."""
+    spec, ls = _kernel_spec(kern)
+    ctx = Context.get()
+    Xd, Gd = ctx.as_device(X), ctx.as_device(G)
+    X2d = None if X2 is None else ctx.as_device(X2)
+    D = int(spec.input_dim)
+    if Xd.dim() != 2 or Xd.shape[1] != D or (X2d is not None and (X2d.dim() != 2 or X2d.shape[1] != D)) or \
+            tuple(Gd.shape) != (Xd.shape[0], Xd.shape[0] if X2d is None else X2d.shape[0]):
+        raise ValueError("kernel_gram_grad: X must be (N, D), X2 (N2, D) or None, G (N, N2) — (N, N) with X2=None — D the kernel's input_dim")
+    nls = D if spec.ard else 1
+    d_X, d_X2, d_k = ctx.empty(Xd.shape[0], D), None if X2d is None else ctx.empty(X2d.shape[0], D), ctx.empty(2 + nls)
+    ctx.gram_grad(spec, Xd, X2d, Gd, d_X, d_X2, d_k)
+    out = dict(X=d_X, variance=d_k[:1], lengthscales=d_k[1:1 + nls], diag=d_k[1 + nls:])
+    if d_X2 is not None:
+        out["X2"] = d_X2
+    out = out if on_device else _to_host(ctx, out, ("variance", "diag"))
+    out.setdefault("X2", None)
+    return out
+
+
+def _mean_on_device(ctx, mean_function, X, num_outputs):
+    """m(X) as a device tensor (N, num_outputs), None for Zero: Identity is X itself, Linear one dsdgp_gemm plus its bias"""
+    kind = getattr(mean_function, "kind", None)
+    if kind == "zero":
+        return None
+    if kind == "identity":
+        if X.shape[1] != num_outputs:
+            raise ValueError(f"an Identity mean function needs as many outputs as inputs, not {X.shape[1]} -> {num_outputs}")
+        return X
+    if kind == "linear":
+        A, b = ctx.to_device(mean_function.A.value), ctx.to_device(mean_function.b.value)
+        if tuple(A.shape) != (X.shape[1], num_outputs):
+            raise ValueError(f"Linear mean function: A is {tuple(A.shape)}, the layer maps {X.shape[1]} -> {num_outputs}")
+        out = ctx.empty(X.shape[0], num_outputs)
+        ctx.gemm(0, 0, 1.0, X, A, 0.0, out)
+        return out + b
+    raise NotImplementedError(f"mean function {type(mean_function).__name__}: Zero, Identity and Linear are on the dense layers' path")
+
+
+class GPMC_Layer(Layer):
+    """A dense layer with fixed inputs, sampled rather than optimised (layers.py:263-293): the latent values at the training inputs X
+    are f = Lu q_mu + m(X) with Lu = chol(K(X, X) + jitter I) and a standard-normal prior on the whitened `q_mu` (N, num_outputs).  X
+    does not change and must be the model's inputs: no minibatches.  Lu is computed ONCE, at construction, on the device
+    (dsdgp_gram, dsdgp_potrf; `settings.jitter`) and is a constant afterwards, as in the reference (layers.py:278-279): the layer's
+    own kernel hyper-parameters therefore have no gradient, and changing them later does not change Lu."""
+    white = True
+
+    def __init__(self, kern, X, num_outputs, mean_function, input_prop_dim=None, **kwargs):
+        Layer.__init__(self, input_prop_dim, **kwargs)
+        X = np.array(X, dtype=np.float64)
+        self.num_data = X.shape[0]
+        self.q_mu = Parameter(np.zeros((self.num_data, int(num_outputs))))
+        self.kern = kern
+        self.mean_function = mean_function
+        self.num_outputs = int(num_outputs)
+        self.X = X
+        ctx = Context.get()
+        spec, ls = _kernel_spec(kern)
+        Xd, Lu = ctx.to_device(X), ctx.empty(self.num_data, self.num_data)
+        ctx.gram(spec, Xd, None, settings.jitter, Lu)
+        ctx.potrf(Lu)
+        object.__setattr__(self, "_dev", dict(ctx=ctx, spec=spec, ls=ls, X=Xd, Lu=Lu))
+
+    def _engine(self):
+        """where sample_from_conditional draws when it is given no z: the owning DGP_Heinonen (its `randn`, under its seeds)"""
+        ref = getattr(self, "_model", None)
+        model = ref() if ref is not None else None
+        if model is None:
+            raise RuntimeError("a GPMC_Layer outside a DGP_Heinonen owns no random numbers: pass z to sample_from_conditional")
+        return model
+
+    def log_prior(self):
+        """the standard-normal prior of q_mu (layers.py:272): -1/2 sum q_mu^2 - 1/2 N D log(2 pi)"""
+        q = self.q_mu.value
+        return float(-0.5 * np.sum(q * q) - 0.5 * q.size * np.log(2.0 * np.pi))
+
+    def build_latents(self, on_device=False):
+        """f = Lu q_mu + m(X) (N, num_outputs), the propagated columns X[:, :input_prop_dim] prepended (layers.py:282-287)"""
+        d = self._dev
+        ctx, p = d["ctx"], self.input_prop_dim
+        f = ctx.empty(self.num_data, self.num_outputs)
+        ctx.gemm(0, 0, 1.0, d["Lu"], ctx.to_device(self.q_mu.value), 0.0, f)
+        m = _mean_on_device(ctx, self.mean_function, d["X"], self.num_outputs)
+        if m is not None:
+            f = f + m
+        if p:
+            f = ctx.torch.cat([d["X"][:, :p], f], 1).contiguous()
+        if on_device:
+            return f
+        ctx.sync()
+        return f.cpu().numpy()
+
+    def latents_vjp(self, dF, on_device=False):
+        """The adjoint of q_mu given the adjoint dF of build_latents(): Lu^T dF (one dsdgp_gemm); the adjoints of the propagated columns,
+        which are copies of the fixed inputs, are dropped."""
+        d = self._dev
+        ctx, p = d["ctx"], self.input_prop_dim or 0
+        dF = ctx.as_device(dF)
+        if tuple(dF.shape) != (self.num_data, p + self.num_outputs):
+            raise ValueError(f"latents_vjp: dF must be {(self.num_data, p + self.num_outputs)}")
+        dF = dF[:, p:].contiguous()
+        out = ctx.empty(self.num_data, self.num_outputs)
+        ctx.gemm(1, 0, 1.0, d["Lu"], dF, 0.0, out)
+        if on_device:
+            return out
+        ctx.sync()
+        return out.cpu().numpy()
+
+    def conditional_ND(self, Xnew, full_cov=False):
+        """The whitened conditional without q_sqrt (layers.py:289-293): mean = K(Xnew, X) Lu^-T q_mu + m(Xnew), variance = Kdiag -
+        colsum((Lu^-1 K(X, Xnew))^2) for every output; full_cov: K(Xnew, Xnew) - A^T A as (N*, N*, num_outputs), the layout
+        Layer.sample_from_conditional takes."""
+        d = self._dev
+        return _dense_conditional(d["ctx"], d["spec"], d["X"], d["Lu"], d["ctx"].to_device(self.q_mu.value), self.mean_function, Xnew,
+                                  full_cov)
+
+
+def _dense_conditional(ctx, spec, X, L, W, mean_function, Xnew, full_cov):
+    """The prediction both dense layers share (layers.py:289-293, 320-335), from a factor L of the kernel matrix at X and W (N, D_out):
+    A = L^-1 K(X, X*), mean = A^T W + m(X*), variance = Kdiag - colsum(A^2) (X*, D_out), or with full_cov K(X*, X*) - A^T A tiled to
+    (N*, N*, D_out) -> numpy arrays"""
+    Xs = ctx.as_device(Xnew)
+    N, ns, DO = X.shape[0], Xs.shape[0], W.shape[1]
+    A, mean = ctx.empty(N, ns), ctx.empty(ns, DO)
+    ctx.gram(spec, X, Xs, 0.0, A)                # K(X, X*)
+    ctx.trsm(L, A)
+    ctx.gemm(1, 0, 1.0, A, W, 0.0, mean)
+    m = _mean_on_device(ctx, mean_function, Xs, DO)
+    if m is not None:
+        mean = mean + m
+    if full_cov:
+        K = ctx.empty(ns, ns)
+        ctx.gram(spec, Xs, None, 0.0, K)
+        ctx.gemm(1, 0, -1.0, A, A, 1.0, K)
+        ctx.sync()
+        return mean.cpu().numpy(), np.tile(K.cpu().numpy()[:, :, None], [1, 1, DO])       # layers.py:330-331: a copy per output
+    var = ctx.empty(ns, DO)
+    ctx.gpr_var(A, float(spec.variance) + (float(spec.white_variance) if spec.has_white else 0.0), var)
+    ctx.sync()
+    return mean.cpu().numpy(), var.cpu().numpy()
+
+
 class Collapsed_Layer(Layer):
     """Extra functions for a collapsed layer (layers.py:296-307): a last layer whose Gaussian posterior is at its exact optimum for
     the data it has been given, so it carries no variational parameters and no KL term of its own."""
@@ -356,3 +519,104 @@ class SGPR_Layer(Collapsed_Layer):
         ctx.collapsed_var(tmp1, tmp2, f["kdiag"], var)
         ctx.sync()
         return mean.cpu().numpy(), var.cpu().numpy()
+
+
+class GPR_Layer(Collapsed_Layer):
+    """A dense GP layer with a Gaussian likelihood where the GP is integrated out (layers.py:310-342): exact GP regression on the
+    inputs it is given, no inducing points.  set_data factorises once — L = chol(k(F, F) + s2 I) (dsdgp_gram with the noise variance as
+    its diagonal add, dsdgp_potrf) and V = L^-1 (Y - m(F)) stay on the device — and build_likelihood / conditional_ND /
+    bound_gradients read the factors.  X_var is ignored, as in the reference.  Kernels: RBF or Matern52, with or without a White
+    part; mean functions: Zero, Identity, Linear."""
+
+    def __init__(self, kern, mean_function, num_outputs, **kwargs):
+        Collapsed_Layer.__init__(self, **kwargs)
+        split_kernel(kern)
+        self.kern = kern
+        self.mean_function = mean_function
+        self.num_outputs = int(num_outputs)
+        object.__setattr__(self, "_factors", None)
+
+    def set_data(self, X_mean, X_var, Y, lik_variance):
+        """X_mean (N, D_in), Y (N, D_Y) — numpy or device tensors — and the noise variance; X_var is ignored.  Runs the Gram matrix,
+        its factorisation and one solve; CholeskyError if k(F, F) + s2 I is not positive definite (the layer then holds no data)."""
+        object.__setattr__(self, "_factors", None)
+        ctx = Context.get()
+        F, Yd = ctx.as_device(X_mean), ctx.as_device(Y)
+        spec, ls = _kernel_spec(self.kern)
+        if F.dim() != 2 or Yd.dim() != 2 or Yd.shape[0] != F.shape[0] or F.shape[1] != spec.input_dim:
+            raise ValueError("set_data: X_mean must be (N, D_in), D_in the kernel's input_dim, and Y (N, D_Y)")
+        N, DY = Yd.shape
+        s2 = float(lik_variance)
+        L = ctx.empty(N, N)
+        ctx.gram(spec, F, None, s2, L)
+        ctx.potrf(L)                                 # L = chol(K + s2 I)
+        m = _mean_on_device(ctx, self.mean_function, F, DY)
+        V = (Yd.clone() if m is None else Yd - m).contiguous()
+        ctx.trsm(L, V)                               # V = L^-1 (Y - m(F))
+        Collapsed_Layer.set_data(self, F, None, Yd, s2)
+        object.__setattr__(self, "_factors", dict(ctx=ctx, spec=spec, ls=ls, L=L, V=V, N=N, DY=DY, s2=s2))
+
+    def _need_factors(self):
+        if self._factors is None:
+            raise RuntimeError("GPR_Layer: call set_data(X_mean, X_var, Y, lik_variance) first")
+        return self._factors
+
+    def bound_terms(self):
+        """(bound, its three terms -1/2 N D_Y log 2 pi, -D_Y sum log L_ii, -1/2 sum V^2) as the device assembled them (dsdgp_gpr_bound)"""
+        f = self._need_factors()
+        ctx = f["ctx"]
+        out = ctx.empty(4)
+        ctx.gpr_bound(f["L"], f["V"], out)
+        ctx.sync()
+        o = out.cpu().numpy()
+        return float(o[0]), o[1:].copy()
+
+    def build_likelihood(self):
+        return self.bound_terms()[0]
+
+    def bound_gradients(self, on_device=False):
+        """The bound of build_likelihood and its gradients with respect to the CONSTRAINED values of everything it depends on, as a
+        dict: `bound`, `variance`, `lengthscales` (the kernel's), `white_variance` (if the kernel has a White part), `lik_variance`
+        (the noise variance given to set_data), `X_mean`, `X_var` (N, D_in; `X_var` is all zeros: the layer ignores it).  numpy arrays
+        and numbers, or device tensors (the scalars of shape (1,)) without waiting for them with on_device=True.
+        With alpha = L^-T V = K^-1 (Y - m) the bound has dF/dK = 1/2 (alpha alpha^T - D_Y K^-1): K^-1 from the factor (dsdgp_trsm of
+        the identity, one dsdgp_gemm), then one dsdgp_gemm with beta = -1/2 D_Y into it, and one symmetric dsdgp_gram_grad takes it to
+        the inputs and the kernel; its diagonal entry is at once the gradient in the noise variance and in the White variance.  The
+        mean function adds dF/dm = alpha through its own Jacobian: alpha for Identity, alpha A^T (one dsdgp_gemm) for Linear.  A Linear
+        mean with trainable A or b raises NotImplementedError: their gradients are not formed."""
+        f = self._need_factors()
+        mf = self.mean_function
+        if getattr(mf, "kind", None) == "linear" and (mf.A.trainable or mf.b.trainable):
+            raise NotImplementedError("GPR_Layer.bound_gradients: a trainable Linear mean function — the gradients of its A and b are not "
+                                      "formed; fix it with set_trainable(False)")
+        ctx, N, DY, L, V, spec = f["ctx"], f["N"], f["DY"], f["L"], f["V"], f["spec"]
+        F = self._X_mean
+        D = int(spec.input_dim)
+        nls = D if spec.ard else 1
+        alpha = V.clone()
+        ctx.trsm(L, alpha, trans=1)                  # alpha = L^-T V
+        zeros = ctx.torch.zeros(N, N, dtype=ctx.torch.float64, device=F.device)
+        Li, dK = ctx.empty(N, N), ctx.empty(N, N)
+        ctx.scale_copy(zeros, Li, diag_add=1.0)      # I
+        ctx.trsm(L, Li)                              # L^-1
+        ctx.gemm(1, 0, 1.0, Li, Li, 0.0, dK)         # K^-1
+        ctx.gemm(0, 1, 0.5, alpha, alpha, -0.5 * DY, dK)      # dF/dK = 1/2 (alpha alpha^T - D_Y K^-1)
+        d_X, d_k, bound = ctx.empty(N, D), ctx.empty(2 + nls), ctx.empty(4)
+        ctx.gram_grad(spec, F, None, dK, d_X, None, d_k)
+        if mf.kind == "identity":
+            d_X = d_X + alpha
+        elif mf.kind == "linear":
+            ctx.gemm(0, 1, 1.0, alpha, ctx.to_device(mf.A.value), 1.0, d_X)
+        ctx.gpr_bound(L, V, bound)
+        res = dict(bound=bound[:1], variance=d_k[:1], lengthscales=d_k[1:1 + nls], lik_variance=d_k[1 + nls:], X_mean=d_X,
+                   X_var=ctx.torch.zeros_like(d_X))
+        scalars = ["bound", "variance", "lik_variance"]
+        if spec.has_white:
+            res["white_variance"] = d_k[1 + nls:]
+            scalars.append("white_variance")
+        return res if on_device else _to_host(ctx, res, tuple(scalars))
+
+    # layers.py:320-335
+    def conditional_ND(self, Xnew, full_cov=False):
+        f = self._need_factors()
+        return _dense_conditional(f["ctx"], f["spec"], self._X_mean, f["L"], f["V"], self.mean_function, Xnew, full_cov)

@@ -1,4 +1,6 @@
-"""Host mirror of the reference's model_zoo.py:25-57: `DGP_Collapsed`, a DGP whose last layer is a collapsed one (layers.SGPR_Layer).
+"""Host mirror of the reference's model_zoo.py:25-88: `DGP_Collapsed`, a DGP whose last layer is a collapsed one (layers.SGPR_Layer, or
+the dense layers.GPR_Layer: exact GP regression on top, no inducing inputs, gradients through the reverse pass of the Gram matrix), and
+`DGP_Heinonen` (at the end of this file), the dense two-layer model sampled by training.HMC.  What follows describes `DGP_Collapsed`.
 Its bound is the one of the reference's `_build_likelihood`: the last layer at its exact optimum over the WHOLE training set, the input
 noise of the last hop integrated analytically through the kernel expectations, minus the KL terms of the inner layers.  The inner
 layers run as one device Engine over `layers[:-1]` (`inner_engine()`; S = 1 on the full training set, explicit `zs` accepted); the
@@ -22,7 +24,7 @@ import numpy as np
 from . import _lib
 from .dgp import DGP_Base
 from .gpflow_compat import Gaussian
-from .layers import Collapsed_Layer, SGPR_Layer, _to_host, concat_input_prop
+from .layers import Collapsed_Layer, GPMC_Layer, GPR_Layer, SGPR_Layer, _to_host, concat_input_prop
 
 
 class DGP_Collapsed(DGP_Base):
@@ -37,7 +39,7 @@ class DGP_Collapsed(DGP_Base):
                                       f"{type(likelihood).__name__}")
         layers = list(layers)
         if not layers or not isinstance(layers[-1], Collapsed_Layer):
-            raise ValueError("DGP_Collapsed: the last layer must be a Collapsed_Layer (SGPR_Layer)")
+            raise ValueError("DGP_Collapsed: the last layer must be a Collapsed_Layer (SGPR_Layer, GPR_Layer)")
         if any(isinstance(layer, Collapsed_Layer) for layer in layers[:-1]):
             raise ValueError("DGP_Collapsed: only the last layer is collapsed")
         DGP_Base.__init__(self, X, Y, likelihood, layers, **kwargs)
@@ -219,8 +221,9 @@ class DGP_Collapsed(DGP_Base):
         `q_mu`, `q_sqrt` (lower-triangular), the kernel's `variance` and `lengthscales`, a White part's `variance`, a trainable Linear
         mean's `A` and `b` — again the gradient of the bound, the KL terms included, with respect to the constrained value.  A one-layer
         model has no inner layers: the same four pairs.  NotImplementedError when the last inner layer propagates inputs
-        (`input_prop_dim`): the adjoints of the propagated columns would have to re-enter the layer below."""
-        from .gpflow_compat import split_kernel
+        (`input_prop_dim`): the adjoints of the propagated columns would have to re-enter the layer below.
+        A GPR_Layer on top: the pairs are those of `top_parameters()` — the kernel's `variance` and `lengthscales`, a White part's
+        `variance`, the likelihood's `variance`; there is no `feature.Z` — and `X_var` is all zeros (GPR_Layer.bound_gradients)."""
         inner = bool(inner) and len(self.layers) > 1
         top = self.layers[-1]
         if inner:
@@ -238,18 +241,27 @@ class DGP_Collapsed(DGP_Base):
             eng.forward_saved(self._device_data()[0], 1, zs=list(zs)[:len(self.layers) - 1] if zs is not None else None, seed=seed)
             g = top.bound_gradients(on_device=True)
             eng.backward_adjoints(g["X_mean"][None], g["X_var"][None], sync=False)
-            g = _to_host(eng.ctx, g, ("bound", "variance", "lik_variance"))
+            g = _to_host(eng.ctx, g, ("bound", "variance", "lik_variance", "white_variance"))
         else:
             g = top.bound_gradients()
         KL = sum(layer.KL() for layer in self.layers[:-1])
-        stat, _ = split_kernel(top.kern)
-        lik = self.likelihood.likelihood
-        pairs = [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape))
-                 for p, k in ((top.feature.Z, "Z"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales"),
-                              (lik.variance, "lik_variance"))]
+        pairs = [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape)) for p, k in self.top_parameters()]
         if inner:
             pairs += self._inner_pairs(eng)
         return g["bound"] - KL, pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
+
+    def top_parameters(self):
+        """[(Parameter, its key in the last layer's bound_gradients), ...]: what the collapsed last layer owns and the likelihood's
+        variance.  SGPR_Layer: `feature.Z`, the kernel's `variance` and `lengthscales`, the noise variance.  GPR_Layer: no inducing
+        inputs; the kernel's `variance` and `lengthscales`, a White part's `variance`, the noise variance."""
+        from .gpflow_compat import split_kernel
+        top = self.layers[-1]
+        stat, wk = split_kernel(top.kern)
+        lik = self.likelihood.likelihood
+        if isinstance(top, GPR_Layer):
+            return [(stat.variance, "variance"), (stat.lengthscales, "lengthscales")] + \
+                   ([(wk.variance, "white_variance")] if wk is not None else []) + [(lik.variance, "lik_variance")]
+        return [(top.feature.Z, "Z"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales"), (lik.variance, "lik_variance")]
 
     def inner_parameters(self):
         """The Parameters of the inner layers in the order of the engine's layout (trainable or not) — per layer `feature.Z`, `q_mu`,
@@ -294,3 +306,77 @@ class DGP_Collapsed(DGP_Base):
                                   "the whole training set, and its reverse pass through the inner layers is "
                                   "compute_log_likelihood_gradients(inner=True) — train with training.ScipyOptimizer(inner=True) or "
                                   "training.CollapsedAdamOptimizer")
+
+
+class DGP_Heinonen(DGP_Collapsed):
+    """A dense two-layer DGP with HMC for inference over the inner layer (model_zoo.py:60-88; Heinonen et al., Non-stationary Gaussian
+    process regression with Hamiltonian Monte Carlo, AISTATS 2016): a GPMC_Layer whose whitened latents `q_mu` carry a standard-normal
+    prior, under a GPR_Layer that is exact GP regression on those latents.  Two layers, a Gaussian likelihood, no minibatches.
+    `compute_log_likelihood()` is log p(Y | q_mu), `compute_log_prior()` the prior of q_mu, `compute_log_density()` their sum — the
+    target of `training.HMC` and what `training.ScipyOptimizer` maximises for this model (MAP).  Prediction is the host layer loop of
+    DGP_Base.propagate over both layers, as in the reference."""
+
+    def __init__(self, X, Y, likelihood, layers, **kwargs):
+        layers = list(layers)
+        if len(layers) != 2:                                            # model_zoo.py:77-80
+            raise ValueError(f"DGP_Heinonen: two layers, not {len(layers)}")
+        if not isinstance(likelihood, Gaussian):
+            raise NotImplementedError(f"DGP_Heinonen: a Gaussian likelihood, not {type(likelihood).__name__}")
+        if not isinstance(layers[0], GPMC_Layer) or not isinstance(layers[1], GPR_Layer):
+            raise ValueError("DGP_Heinonen: layers must be [GPMC_Layer, GPR_Layer]")
+        DGP_Collapsed.__init__(self, X, Y, likelihood, layers, **kwargs)
+        if layers[0].num_data != self.X_data.shape[0]:
+            raise ValueError("DGP_Heinonen: the GPMC_Layer must be built on the model's inputs X")
+        object.__setattr__(layers[0], "_model", weakref.ref(self))
+
+    def inner_engine(self):
+        raise RuntimeError("DGP_Heinonen has no engine: its inner layer is a GPMC_Layer")
+
+    def _refresh(self):
+        pass
+
+    # model_zoo.py:85-88
+    def inner_layers_propagate(self, X, full_cov=False, S=1, zs=None):
+        f = self.layers[0].build_latents()[None, :, :]
+        return [f], [f], [np.zeros_like(f)]
+
+    def _set_data(self, zs=None, seed=None):
+        _, Yd = self._device_data()
+        self.layers[-1].set_data(self.layers[0].build_latents(on_device=True), None, Yd, float(self.likelihood.likelihood.variance.value))
+
+    def propagate(self, X, full_cov=False, S=1, zs=None):
+        """model_zoo.py:46-50: the latents at the training inputs become the GPR_Layer's data, then DGP_Base.propagate's loop over the
+        layers (dgp.py:61-76) on the host, each layer's arithmetic on the device."""
+        self._set_data()
+        F = np.tile(np.asarray(X, dtype=np.float64)[None], [int(S), 1, 1])
+        Fs, Fmeans, Fvars = [], [], []
+        for layer, z in zip(self.layers, zs or [None] * len(self.layers)):
+            F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=full_cov)
+            Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
+        return Fs, Fmeans, Fvars
+
+    def compute_log_prior(self):
+        return self.layers[0].log_prior()
+
+    def compute_log_density(self):
+        return self.compute_log_likelihood() + self.compute_log_prior()
+
+    def compute_log_likelihood_gradients(self, zs=None, inner=False):
+        """(bound, [(Parameter, gradient), ...], {"X_mean": ..., "X_var": ...}): log p(Y | q_mu) and its gradients with respect to the
+        constrained values of `layers[0].q_mu` (the GPR_Layer's input adjoint taken through Lu: GPMC_Layer.latents_vjp), the top
+        kernel's `variance` and `lengthscales` (and White `variance`) and the likelihood's `variance`; the third result is the adjoint of
+        the latents.  The GPMC_Layer's own kernel has no gradient: its factor Lu is a constant (layers.py:278-279).  zs and inner are
+        accepted for the signature of DGP_Collapsed and ignored: nothing is sampled, and q_mu is always among the pairs."""
+        self._set_data()
+        top, low = self.layers[-1], self.layers[0]
+        g = top.bound_gradients(on_device=True)
+        dq = low.latents_vjp(g["X_mean"], on_device=True)
+        g = _to_host(self._context(), dict(g, q_mu=dq), ("bound", "variance", "lik_variance", "white_variance"))
+        pairs = [(low.q_mu, g["q_mu"])] + [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape)) for p, k in self.top_parameters()]
+        return g["bound"], pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
+
+    def compute_log_density_gradients(self):
+        """(log density, [(Parameter, gradient), ...]): compute_log_likelihood_gradients with the prior added — -q_mu to q_mu's pair"""
+        bound, pairs, _ = self.compute_log_likelihood_gradients()
+        low = self.layers[0]
+        return bound + low.log_prior(), [(p, g - low.q_mu.value if p is low.q_mu else g) for p, g in pairs]

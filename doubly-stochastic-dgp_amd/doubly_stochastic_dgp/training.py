@@ -1,5 +1,6 @@
 """[UPSTREAM] gpflow.training.AdamOptimizer mirror: `AdamOptimizer(0.01).minimize(model, maxiter=K)`
 (demos/demo_regression_UCI.ipynb:324).  The step itself (gradient + Adam update) runs in libdsdgp."""
+import numpy as np
 
 _NO_SAMPLED_GRADIENT = ("{} takes no minibatch step of a sampled bound: there is no reverse pass of one to step along (a DGP_Collapsed "
                         "trains on its own bound: ScipyOptimizer(inner=True), CollapsedAdamOptimizer)")
@@ -62,6 +63,9 @@ class ScipyOptimizer:
     scipy's L-BFGS-B line search turns an infinite or a huge trial value into a step of zero length and then reports convergence at
     the point it started from; tests/test_psi_grad_reference_cpu.py shows the finite value recovering.)  A failure at the starting
     point itself is raised: there is nothing to step back to.
+    A GPR_Layer on top has no inducing inputs: its variables are the kernel's `variance` and `lengthscales`, a White part's `variance`
+    and the likelihood's `variance` (`DGP_Collapsed.top_parameters`).  For a `DGP_Heinonen` the objective is `compute_log_density` (MAP:
+    the prior of the inner layer's latents included), with `layers[0].q_mu` among the variables.
     Any other model: NotImplementedError.  `options`: further entries of scipy's options dict (`maxiter` is minimize's argument)."""
 
     def __init__(self, method="L-BFGS-B", tol=None, options=None):
@@ -79,11 +83,16 @@ class ScipyOptimizer:
         if not isinstance(model, DGP_Collapsed):
             raise NotImplementedError(f"ScipyOptimizer fits the collapsed last layer of a DGP_Collapsed; {type(model).__name__} is "
                                       "trained by AdamOptimizer / NatGradOptimizer")
+        from .model_zoo import DGP_Heinonen
         train, free = _collapsed_variables(model, inner)
         if not train:
             raise ValueError("ScipyOptimizer: none of the collapsed layer's parameters is trainable" if not inner else
                              "ScipyOptimizer: none of the model's parameters is trainable")
         kw = {"inner": True} if inner else {}
+        if isinstance(model, DGP_Heinonen):           # MAP: the log density (the prior of q_mu included), q_mu among the variables
+            gradients = lambda: model.compute_log_density_gradients() + (None,)
+        else:
+            gradients = lambda: model.compute_log_likelihood_gradients(zs=zs, **kw)
 
         def pack(values):
             return np.concatenate([np.asarray(v, dtype=np.float64)[m] for v, m in zip(values, free)])
@@ -102,7 +111,7 @@ class ScipyOptimizer:
         def objective(x):
             assign(x)
             try:
-                bound, pairs, _ = model.compute_log_likelihood_gradients(zs=zs, **kw)
+                bound, pairs, _ = gradients()
             except CholeskyError:
                 if last[0] is None:
                     raise
@@ -130,11 +139,12 @@ def _collapsed_variables(model, inner):
     the collapsed layer's `feature.Z`, kernel `variance` and `lengthscales` and the likelihood's `variance`; with `inner` the inner
     layers' as well.  Every entry is a variable, except above the diagonal of a `q_sqrt` (transform "tril")."""
     import numpy as np
-    from .gpflow_compat import split_kernel
-    top = model.layers[-1]
-    stat = split_kernel(top.kern)[0]
-    params = [top.feature.Z, stat.variance, stat.lengthscales, model.likelihood.likelihood.variance]
-    if inner:
+    from .model_zoo import DGP_Heinonen
+    # DGP_Collapsed.top_parameters: an SGPR_Layer's four as above; a GPR_Layer has no inducing inputs and may have a White variance
+    params = [p for p, _ in model.top_parameters()]
+    if isinstance(model, DGP_Heinonen):
+        params = [model.layers[0].q_mu] + params         # the inner layer's latents: always among the variables
+    elif inner:
         params += model.inner_parameters()
     train = [p for p in params if p.trainable]
     free = [np.broadcast_to(np.tril(np.ones(p.shape[-2:], dtype=bool)), p.shape) if p.transform == "tril" else np.ones(p.shape, dtype=bool)
@@ -163,9 +173,12 @@ class CollapsedAdamOptimizer:
         """returns the bound at the last evaluated point (before the last step); zs as for compute_log_likelihood"""
         import numpy as np
         from .gpflow_compat import positive_backward, positive_forward, positive_slope
-        from .model_zoo import DGP_Collapsed
+        from .model_zoo import DGP_Collapsed, DGP_Heinonen
         if not isinstance(model, DGP_Collapsed):
             raise NotImplementedError(f"CollapsedAdamOptimizer trains a DGP_Collapsed; {type(model).__name__} is trained by AdamOptimizer")
+        if isinstance(model, DGP_Heinonen):
+            raise NotImplementedError("CollapsedAdamOptimizer steps the inner layers through their engine, which a DGP_Heinonen does not "
+                                      "have: sample it with HMC or fit it with ScipyOptimizer (MAP)")
         top4, _ = _collapsed_variables(model, False)
         deep = len(model.layers) > 1
         # moments and step count of the four live with the model, as the engine's do with the engine: a second call goes on (TF's slots)
@@ -192,3 +205,147 @@ class CollapsedAdamOptimizer:
         if deep and bound is not None:
             model.inner_engine().prepare()      # the last host step reaches the device; a failed factorisation there is raised here
         return bound
+
+
+class HMC:
+    """[UPSTREAM] gpflow.train.HMC mirror: Hamiltonian Monte Carlo on `model.compute_log_density()` of a `DGP_Heinonen`, the way the
+    reference's model is built to be used (model_zoo.py:60-88).  The variables are `var_list`, by default `[model.layers[0].q_mu]`; any
+    Parameter among the pairs of `compute_log_likelihood_gradients` may be added (the top kernel's, the likelihood's variance).  A
+    positive parameter moves in unconstrained space, theta = softplus(x) + 1e-6 (gpflow_compat).  Only `q_mu` has a prior (standard
+    normal, part of compute_log_density); a parameter without a prior has a FLAT density in the space it moves in — unconstrained space
+    for a positive one: no prior and no Jacobian term is added for it.
+    Leapfrog integration with unit mass: positions and momenta are device tensors updated by torch operations, and every step costs one
+    `compute_log_likelihood_gradients` (the model's Parameters are assigned at every position, which is how the gradient sees it).
+    Randomness, so that a run can be replayed: the momenta of iteration i are `dsdgp_randn(seed, stream = i)` (one draw of the total
+    size, cut in var_list order); the path lengths and the acceptance uniforms come from `np.random.default_rng(seed)`, one
+    `integers(lmin, lmax + 1)` and one `uniform()` per iteration, in that order.  A CholeskyError inside a trajectory is a rejection."""
+
+    @staticmethod
+    def _variables(model, var_list):
+        var_list = [model.layers[0].q_mu] if var_list is None else list(var_list)
+        if not var_list:
+            raise ValueError("HMC: var_list is empty")
+        return var_list
+
+    @staticmethod
+    def _ctx(model):
+        return model._context()
+
+    @classmethod
+    def _position(cls, model, var_list):
+        """the unconstrained values of var_list as device tensors"""
+        from .gpflow_compat import positive_backward
+        ctx = cls._ctx(model)
+        return [ctx.to_device(positive_backward(p.value) if p.transform == "positive" else p.value) for p in var_list]
+
+    @staticmethod
+    def _assign(var_list, q):
+        from .gpflow_compat import positive_forward
+        for p, x in zip(var_list, q):
+            x = x.cpu().numpy()
+            p.assign(positive_forward(x) if p.transform == "positive" else x)
+
+    @classmethod
+    def _logp_and_grad(cls, model, var_list):
+        """(log density, its gradient in the unconstrained variables as device tensors) at the model's current parameters"""
+        from .gpflow_compat import positive_slope
+        ctx = cls._ctx(model)
+        logp, pairs = model.compute_log_density_gradients()
+        grads = {id(p): g for p, g in pairs}
+        out = []
+        for p in var_list:
+            if id(p) not in grads:
+                raise ValueError("HMC: a Parameter of var_list has no gradient of the model's log density")
+            g = np.asarray(grads[id(p)], dtype=np.float64).reshape(p.shape)
+            out.append(ctx.to_device(g * positive_slope(p.value) if p.transform == "positive" else g))
+        return float(logp), out
+
+    @classmethod
+    def _leapfrog(cls, model, var_list, q, p, grad, epsilon, steps):
+        """`steps` leapfrog steps from (q, p) with the gradient `grad` at q -> (q, p, log density at q, gradient at q); q, p: lists of
+        device tensors, not modified"""
+        eps = float(epsilon)
+        q = [x.clone() for x in q]
+        p = [m + (0.5 * eps) * g for m, g in zip(p, grad)]
+        logp = None
+        for s in range(int(steps)):
+            for x, m in zip(q, p):
+                x += eps * m
+            cls._assign(var_list, q)
+            logp, grad = cls._logp_and_grad(model, var_list)
+            w = eps if s + 1 < int(steps) else 0.5 * eps
+            p = [m + w * g for m, g in zip(p, grad)]
+        return q, p, logp, grad
+
+    @classmethod
+    def leapfrog(cls, model, q, p, epsilon, steps, var_list=None):
+        """`steps` leapfrog steps of size epsilon from position q and momentum p (arrays shaped like the variables — unconstrained
+        values — or lists of them, one per entry of var_list) -> (q, p, log density at the new q) as numpy arrays (lists if lists were
+        given).  The model's Parameters are left at the new position."""
+        var_list = cls._variables(model, var_list)
+        ctx = cls._ctx(model)
+        single = not isinstance(q, (list, tuple))
+        qd = [ctx.to_device(x) for x in ([q] if single else q)]
+        pd = [ctx.to_device(x) for x in ([p] if single else p)]
+        if len(qd) != len(var_list) or any(tuple(x.shape) != v.shape or tuple(m.shape) != v.shape for x, m, v in zip(qd, pd, var_list)):
+            raise ValueError("HMC.leapfrog: q and p must have the shapes of var_list")
+        cls._assign(var_list, qd)
+        _, grad = cls._logp_and_grad(model, var_list)
+        qd, pd, logp, _ = cls._leapfrog(model, var_list, qd, pd, grad, epsilon, steps)
+        qn, pn = [x.cpu().numpy() for x in qd], [m.cpu().numpy() for m in pd]
+        return (qn[0], pn[0], logp) if single else (qn, pn, logp)
+
+    @classmethod
+    def momenta(cls, model, var_list, seed, iteration):
+        """the momenta of one iteration: dsdgp_randn(seed, stream = iteration), cut in var_list order (device tensors)"""
+        import ctypes as C
+        from . import _lib
+        ctx = cls._ctx(model)
+        sizes = [int(np.prod(p.shape)) for p in var_list]
+        flat = ctx.empty(sum(sizes))
+        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(int(seed)), C.c_uint64(int(iteration)), sum(sizes), C.c_void_p(flat.data_ptr())))
+        out, at = [], 0
+        for p, k in zip(var_list, sizes):
+            out.append(flat[at:at + k].reshape(p.shape))
+            at += k
+        return out
+
+    def sample(self, model, num_samples, epsilon, lmin=1, lmax=1, thin=1, burn=0, var_list=None, seed=0):
+        """-> dict(samples={name: (num_samples, *shape)} of the CONSTRAINED values — names "q_mu", then "var<i>" by position in var_list
+        for any other Parameter —, logprobs (num_samples,), accepted (one flag per iteration, burn-in included), accept_rate).
+        burn + num_samples thin iterations; every thin-th state after the burn-in is kept.  The model is left at the last state."""
+        from ._lib import CholeskyError
+        from .gpflow_compat import positive_forward
+        from .model_zoo import DGP_Heinonen
+        if not isinstance(model, DGP_Heinonen):
+            raise NotImplementedError(f"HMC samples a DGP_Heinonen; {type(model).__name__} has no log density to sample from")
+        if int(num_samples) < 1 or int(thin) < 1 or int(burn) < 0 or int(lmin) < 1 or int(lmax) < int(lmin) or not float(epsilon) > 0.0:
+            raise ValueError("HMC.sample: num_samples, thin >= 1, burn >= 0, 1 <= lmin <= lmax, epsilon > 0")
+        var_list = self._variables(model, var_list)
+        names = ["q_mu" if p is model.layers[0].q_mu else f"var{i}" for i, p in enumerate(var_list)]
+        rng = np.random.default_rng(seed)
+        q = self._position(model, var_list)
+        logp, grad = self._logp_and_grad(model, var_list)
+        kept, logps, accepted = {n: [] for n in names}, [], []
+        for it in range(int(burn) + int(num_samples) * int(thin)):
+            steps, u = int(rng.integers(int(lmin), int(lmax) + 1)), float(rng.uniform())
+            p0 = self.momenta(model, var_list, seed, it)
+            H0 = -logp + 0.5 * sum(float((m * m).sum()) for m in p0)
+            try:
+                q1, p1, logp1, grad1 = self._leapfrog(model, var_list, q, p0, grad, epsilon, steps)
+                H1 = -logp1 + 0.5 * sum(float((m * m).sum()) for m in p1)
+                ok = bool(np.log(u) < H0 - H1)
+            except CholeskyError:
+                ok = False
+            if ok:
+                q, logp, grad = q1, logp1, grad1
+            accepted.append(ok)
+            if it >= int(burn) and (it - int(burn) + 1) % int(thin) == 0:
+                for n, p, x in zip(names, var_list, q):
+                    x = x.cpu().numpy()
+                    kept[n].append(positive_forward(x) if p.transform == "positive" else x.copy())
+                logps.append(logp)
+        self._assign(var_list, q)
+        accepted = np.array(accepted, dtype=bool)
+        return dict(samples={n: np.stack(v) for n, v in kept.items()}, logprobs=np.array(logps), accepted=accepted,
+                    accept_rate=float(np.mean(accepted)))

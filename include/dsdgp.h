@@ -60,7 +60,7 @@ int dsdgp_ctx_destroy(dsdgp_ctx* ctx);
 int dsdgp_sync(dsdgp_ctx* ctx);
 /* HIP-event timing of the most recent launch of a named kernel class on the ctx stream (bench.py roofline):
  * enable, run, then read the accumulated milliseconds and launch count. name in
- * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig","psi","psi2"}. */
+ * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig","psi","psi2","gram_grad"}. */
 int dsdgp_prof_enable(dsdgp_ctx* ctx, int on);
 int dsdgp_prof_read(dsdgp_ctx* ctx, const char* name, double* total_ms, int64_t* launches, int reset);
 /* Kernel launches this library has enqueued in this process so far (all contexts; memsets / copies not counted): the difference
@@ -614,6 +614,42 @@ int dsdgp_collapsed_var(dsdgp_ctx* ctx, int32_t M, int64_t ns, int32_t DY, const
 int dsdgp_collapsed_adjoints(dsdgp_ctx* ctx, int32_t M, int64_t n, int32_t DY, const double* Si, const double* Ki, const double* KpK,
                              const double* psi2, const double* alpha, const double* c, const double* Y, const double* psi0,
                              double noise_var, double* g_psi2, double* d_Kuu, double* out);
+
+/* dsdgp_gram_grad: the reverse pass of dsdgp_gram — what tf.gradients builds through kern.K when the reference fits or samples a model of
+ * dense layers (GPMC_Layer, GPR_Layer: layers.py:263-293, 310-342; DGP_Heinonen, model_zoo.py:60-88), whose bound depends on its inputs
+ * only through K(F, F).  Same kernels as dsdgp_gram: RBF or Matern52, scalar or ARD lengthscales, optional White part.  G (device,
+ * n x ldg) is the adjoint of dsdgp_gram's output for a scalar F; every output is optional (NULL) and is OVERWRITTEN:
+ *   cross form (X2 != NULL):       d_X[i, :]  = sum_j G_ij dk(x_i, y_j)/dx_i   (n x D),    d_X2[j, :] = sum_i G_ij dk(x_i, y_j)/dy_j   (n2 x D)
+ *   symmetric form (X2 == NULL, K = k(X, X) + (white_variance + jitter) I; G need not be symmetric; d_X2 must be NULL):
+ *                                  d_X[i, :]  = sum_j (G_ij + G_ji) dk(x_i, x_j)/dx_i
+ *   d_kern (device, 2 + (ard ? D : 1) doubles): [0] = dF/d variance, [1 ..] = dF/d lengthscales (D entries with ARD, else one), then one
+ *                                  more entry, dF/d(diagonal add) = sum_i G_ii: written in the symmetric form, 0 in the cross form.  It is at
+ *                                  once the gradient in the White variance and in whatever the caller passed to dsdgp_gram as `jitter`
+ *                                  (GPR_Layer passes the noise variance there).
+ * With r2 = sum_d ((x_d - y_d) / l_d)^2 and dk/dr2 of the forward's kernel function (Matern52 with its r = sqrt(r2 + 1e-12)):
+ * dk/dx_d = 2 (x_d - y_d) / l_d^2 dk/dr2, dk/dl_d = -2 (x_d - y_d)^2 / l_d^3 dk/dr2.  Every x_d - y_d is formed as a difference of the
+ * inputs, never from an expanded square.  Coincident rows give a finite, zero contribution; a pair whose exponential underflows
+ * contributes +0.  One thread holds one row, the other side is walked in tiles staged in the LDS; rows are split over workgroups, column
+ * ranges over splits, partial results are added in ascending split order.  No floating-point atomics; every summation order depends on
+ * (n, n2, D, form) alone: the same arguments give the same bits, and an output requested alone has the bits it has when all are
+ * requested.  Asynchronous on the context's stream; the partial sums live in the context's scratch.
+ * DSDGP_ERR_UNSUPPORTED for input_dim > 32 (as for dsdgp_rbf_expectations_grad) or more than 8 GB of partial sums.  DSDGP_ERR_BAD_ARG for
+ * n or n2 outside 1 .. 2^31 - 1, ldg < n2 (n in the symmetric form), a kernel kind other than the two, input_dim < 1, a NULL ctx / kern /
+ * X / G, or d_X2 != NULL in the symmetric form.  A refused call launches nothing. */
+int dsdgp_gram_grad(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* X, int64_t n, const double* X2, int64_t n2, const double* G,
+                    int64_t ldg, double* d_X, double* d_X2, double* d_kern);
+
+/* The two small steps of the reference's dense collapsed layer (GPR_Layer, layers.py:310-342) that the primitives above lack; GPR_Layer
+ * of the host mirror composes them with dsdgp_gram (the noise variance as its diagonal add), dsdgp_potrf, dsdgp_trsm and dsdgp_gemm.
+ * Both asynchronous; every sum in a fixed order.
+ * dsdgp_gpr_bound: multivariate_normal(Y, m, L) of layers.py:342 summed over the outputs, from L = chol(K + noise_var I) (device,
+ * n x ldl, the diagonal is read) and V = L^-1 (Y - m) (device, n x ldv, DY columns used).  out (device, 4 doubles): out[0] = the bound,
+ * out[1..3] = -1/2 n DY log(2 pi), -DY sum log L_ii, -1/2 sum V^2;  out[0] adds them in this order.  One workgroup. */
+int dsdgp_gpr_bound(dsdgp_ctx* ctx, int64_t n, int32_t DY, const double* L, int64_t ldl, const double* V, int64_t ldv, double* out);
+/* dsdgp_gpr_var: var[r, d] = kdiag - sum_i A[i, r]^2 for every output d < DY (layers.py:333-334); A = L^-1 K(F, X*) (n x lda, ns columns
+ * used), var (ns x DY).  An entry point of its own rather than dsdgp_collapsed_var, which would need an n x ns matrix of zeros as its
+ * second operand. */
+int dsdgp_gpr_var(dsdgp_ctx* ctx, int64_t n, int64_t ns, int32_t DY, const double* A, int64_t lda, double kdiag, double* var);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
