@@ -175,6 +175,14 @@ _PROTOS = {
     "dsdgp_gpr_bound": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     # layers.py:333-334
     "dsdgp_gpr_var": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),
+    # the sparse conditional with q_sqrt = None (layers.py:200, 249-260) and its reverse pass; the caller holds the scratch block
+    "dsdgp_sparse_conditional_scratch_bytes": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "dsdgp_sparse_conditional": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_int)]),
+    "dsdgp_sparse_conditional_grad": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                                C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "dsdgp_model_set_grad_first_layer":(C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),

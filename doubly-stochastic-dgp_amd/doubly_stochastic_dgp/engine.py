@@ -141,6 +141,36 @@ class Context:
         _lib.check(self.lib.dsdgp_gpr_var(self.handle, n, ns, DY, *self._p("gpr_var: A", A, (n, ns)), kdiag,
                                           self._p("gpr_var: var", var, (ns, DY), True)[0]))
 
+    def _sparse_scratch(self, n, M, D, DO, reverse):
+        """the block the sparse conditional keeps its intermediates in (the calls it composes use the context's own scratch)"""
+        need = C.c_int64()
+        _lib.check(self.lib.dsdgp_sparse_conditional_scratch_bytes(n, M, D, DO, int(reverse), C.byref(need)))
+        return self.torch.empty(need.value // 8 + 32, dtype=self.torch.float64, device=f"cuda:{self.device}"), need.value
+
+    def sparse_conditional(self, spec, Z, X, q_mu, white, jitter, mean=None, var=None):
+        """the sparse conditional without q_sqrt (dsdgp_sparse_conditional): mean (n, DO) = A^T W, var (n,) = kdiag - colsum(A^2), A =
+        Lu^-1 K(Z, X), W = q_mu (white) or Lu^-1 q_mu; each output may be None.  CholeskyError if K(Z, Z) + jitter I is not positive
+        definite: nothing is written then."""
+        (M, D), n, DO = Z.shape, X.shape[0], q_mu.shape[1]
+        p = lambda k, t, shape: None if t is None else self._p("sparse_conditional: " + k, t, shape, True)[0]
+        scr, nbytes = self._sparse_scratch(n, M, D, DO, False)
+        _lib.check(self.lib.dsdgp_sparse_conditional(self.handle, C.byref(spec), p("Z", Z, (M, spec.input_dim)), M, p("X", X, (n, D)), n,
+                                                     p("q_mu", q_mu, (M, DO)), DO, int(bool(white)), float(jitter), ptr(scr), nbytes,
+                                                     p("mean", mean, (n, DO)), p("var", var, (n,)), C.byref(C.c_int(0))))
+
+    def sparse_conditional_grad(self, spec, Z, X, q_mu, white, jitter, gm, gv, d_q_mu=None, d_Z=None, d_X=None, d_kern=None):
+        """the reverse pass of sparse_conditional (dsdgp_sparse_conditional_grad): gm (n, DO) the adjoint of the mean, gv (n,) the adjoint
+        of the variance summed over the outputs; each output may be None.  d_kern (2 + lengthscale entries): variance, lengthscales,
+        the diagonal add (the White variance)"""
+        (M, D), n, DO = Z.shape, X.shape[0], q_mu.shape[1]
+        p = lambda k, t, shape: None if t is None else self._p("sparse_conditional_grad: " + k, t, shape, True)[0]
+        nk = 2 + (D if spec.ard else 1)
+        scr, nbytes = self._sparse_scratch(n, M, D, DO, True)
+        _lib.check(self.lib.dsdgp_sparse_conditional_grad(
+            self.handle, C.byref(spec), p("Z", Z, (M, spec.input_dim)), M, p("X", X, (n, D)), n, p("q_mu", q_mu, (M, DO)), DO,
+            int(bool(white)), float(jitter), p("gm", gm, (n, DO)), p("gv", gv, (n,)), ptr(scr), nbytes, p("d_q_mu", d_q_mu, (M, DO)),
+            p("d_Z", d_Z, (M, D)), p("d_X", d_X, (n, D)), p("d_kern", d_kern, (nk,)), C.byref(C.c_int(0))))
+
     def prof_enable(self, on=True):
         _lib.check(self.lib.dsdgp_prof_enable(self.handle, int(on)))
 
@@ -164,6 +194,11 @@ def ptr(t):
 
 class Engine:
     def __init__(self, layers, likelihood, white, n_max=1024, s_max=1):
+        for layer in layers:
+            if hasattr(layer, "q_sqrt") and layer.q_sqrt is None:
+                raise NotImplementedError(f"Engine: {type(layer).__name__} has no q_sqrt, and the engine's KL tail reads one from every "
+                                          "layer record (the logarithm of its diagonal); an SGPMC_Layer runs under a collapsed layer in "
+                                          "a DGP_Collapsed, outside the engine")
         self.ctx = Context.get()
         self.lib = self.ctx.lib
         self.layers, self.likelihood, self.white = list(layers), likelihood, bool(white)

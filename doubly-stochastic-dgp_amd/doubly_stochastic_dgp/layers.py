@@ -1,8 +1,8 @@
 """Host mirror of the reference's layer classes (layers.py:36-246): `Layer`, `SVGP_Layer` with the same constructor,
 attributes (`q_mu`, `q_sqrt`, `feature.Z`, `kern`, `mean_function`, `num_outputs`, `white`) and methods
 (`conditional_ND`, `conditional_SND`, `sample_from_conditional`, `KL`), of the collapsed layers `Collapsed_Layer`, `SGPR_Layer`
-(layers.py:296-307, 345-367, 371-525) and of the dense layers `GPMC_Layer`, `GPR_Layer` (layers.py:263-293, 310-342).  All arithmetic
-runs in libdsdgp (HIP)."""
+(layers.py:296-307, 345-367, 371-525), of the dense layers `GPMC_Layer`, `GPR_Layer` (layers.py:263-293, 310-342) and of the sparse
+sampled layer `SGPMC_Layer` (layers.py:249-260).  All arithmetic runs in libdsdgp (HIP)."""
 import ctypes as C
 
 import numpy as np
@@ -352,6 +352,122 @@ def _dense_conditional(ctx, spec, X, L, W, mean_function, Xnew, full_cov):
     ctx.gpr_var(A, float(spec.variance) + (float(spec.white_variance) if spec.has_white else 0.0), var)
     ctx.sync()
     return mean.cpu().numpy(), var.cpu().numpy()
+
+
+class SGPMC_Layer(Layer):
+    """A sparse layer for sampling (layers.py:249-260): an SVGP layer without q_sqrt, whose inducing outputs `q_mu` (M, num_outputs)
+    carry a standard-normal prior (white=True: of the whitened values) and are sampled or optimised rather than given a Gaussian
+    posterior.  Its conditional is the reference's conditional_ND on the branch `q_sqrt is None` (layers.py:178-219, line 200):
+    A = Lu^-1 K(Z, X), mean = A^T W + m(X) with W = q_mu (white) or Lu^-1 q_mu, variance = Kdiag - colsum(A^2) for every output
+    (dsdgp_sparse_conditional), and `conditional_vjp` is its reverse pass (dsdgp_sparse_conditional_grad).  Unlike GPMC_Layer nothing is
+    frozen at construction: Z and the kernel are read at every evaluation and have gradients.  Constructing the layer touches no
+    device.  It lives under a collapsed layer in a DGP_Collapsed; the engine does not take it (its KL tail reads a q_sqrt)."""
+
+    def __init__(self, kern, Z, num_outputs, mean_function, white=False, input_prop_dim=None, **kwargs):
+        Layer.__init__(self, input_prop_dim, **kwargs)
+        split_kernel(kern)
+        Z = np.array(Z, dtype=np.float64)
+        self.num_inducing = Z.shape[0]
+        self.feature = InducingPoints(Z)
+        self.q_mu = Parameter(np.zeros((self.num_inducing, int(num_outputs))))
+        self.q_sqrt = None
+        self.kern = kern
+        self.mean_function = mean_function
+        self.num_outputs = int(num_outputs)
+        self.white = bool(white)
+
+    def _engine(self):
+        """where sample_from_conditional draws when it is given no z: the owning DGP_Collapsed (its `randn`, under its seeds)"""
+        ref = getattr(self, "_model", None)
+        model = ref() if ref is not None else None
+        if model is None:
+            raise RuntimeError("an SGPMC_Layer outside a DGP_Collapsed owns no random numbers: pass z to sample_from_conditional")
+        return model
+
+    def KL(self):
+        return 0.0
+
+    def log_prior(self):
+        """the standard-normal prior of q_mu (layers.py:257): -1/2 sum q_mu^2 - 1/2 M D log(2 pi)"""
+        q = self.q_mu.value
+        return float(-0.5 * np.sum(q * q) - 0.5 * q.size * np.log(2.0 * np.pi))
+
+    def _check_mean(self, what):
+        mf = self.mean_function
+        if getattr(mf, "kind", None) == "linear" and (mf.A.trainable or mf.b.trainable):
+            raise NotImplementedError(f"SGPMC_Layer.{what}: a trainable Linear mean function — the gradients of its A and b are not "
+                                      "formed; fix it with set_trainable(False)")
+
+    def _operands(self, X):
+        ctx = Context.get()
+        spec, ls = _kernel_spec(self.kern)
+        Xd = ctx.as_device(X)
+        if Xd.dim() != 2 or Xd.shape[1] != spec.input_dim or self.feature.Z.shape[1] != spec.input_dim:
+            raise ValueError("SGPMC_Layer: X must be (N, D) and Z (M, D), D the kernel's input_dim")
+        object.__setattr__(self, "_last_X", Xd)
+        return ctx, spec, ls, ctx.to_device(self.feature.Z.value), Xd, ctx.to_device(self.q_mu.value)
+
+    def conditional_device(self, X):
+        """(mean (N, num_outputs), var (N,)) as device tensors, without waiting for them: the variance is ONE column, the same for every
+        output.  X: a numpy array or a device tensor."""
+        self._check_mean("conditional")
+        ctx, spec, ls, Z, Xd, q = self._operands(X)
+        mean, var = ctx.empty(Xd.shape[0], self.num_outputs), ctx.empty(Xd.shape[0])
+        ctx.sparse_conditional(spec, Z, Xd, q, self.white, settings.jitter, mean, var)
+        m = _mean_on_device(ctx, self.mean_function, Xd, self.num_outputs)
+        return (mean if m is None else mean + m), var
+
+    # layers.py:178-219 with q_sqrt = None
+    def conditional_ND(self, X, full_cov=False):
+        """full_cov: K(X, X) - A^T A as (N, N, num_outputs), a copy per output, composed from dsdgp_gram / dsdgp_trsm / dsdgp_gemm as
+        the dense layers' prediction is"""
+        if not full_cov:
+            mean, var = self.conditional_device(X)
+            Context.get().sync()
+            return mean.cpu().numpy(), np.tile(var.cpu().numpy()[:, None], [1, self.num_outputs])
+        self._check_mean("conditional")
+        ctx, spec, ls, Z, Xd, q = self._operands(X)
+        Lu = ctx.empty(self.num_inducing, self.num_inducing)
+        ctx.gram(spec, Z, None, settings.jitter, Lu)
+        ctx.potrf(Lu)
+        if not self.white:
+            ctx.trsm(Lu, q)
+        return _dense_conditional(ctx, spec, Z, Lu, q, self.mean_function, Xd, True)
+
+    def conditional_vjp(self, dmean, dvar, X=None, on_device=False):
+        """The reverse pass of conditional_ND(X) for a scalar F: dmean (N, num_outputs) and dvar (N, num_outputs; or (N,), already
+        summed over the outputs) are the adjoints of its mean and variance; X=None: the inputs of the last conditional_ND /
+        conditional_device call.  Returns the gradients of F as a dict: `q_mu` (M,
+        num_outputs), `Z` (M, D), `X` (N, D), `variance`, `lengthscales` (the kernel's) and, with a White part, `white_variance`.
+        A fixed mean function adds its own Jacobian to `X`: dmean for Identity, dmean A^T for Linear.  numpy arrays or device tensors
+        in; on_device: device tensors (the numbers of shape (1,)) out, without waiting for them."""
+        self._check_mean("conditional_vjp")
+        if X is None:
+            X = getattr(self, "_last_X", None)
+            if X is None:
+                raise RuntimeError("SGPMC_Layer.conditional_vjp: no X given and no conditional evaluated yet")
+        ctx, spec, ls, Z, Xd, q = self._operands(X)
+        gm, gv = ctx.as_device(dmean), ctx.as_device(dvar)
+        n, D, M, DO = Xd.shape[0], int(spec.input_dim), self.num_inducing, self.num_outputs
+        if gv.dim() == 2:
+            gv = gv.sum(1) if gv.shape[1] > 1 else gv[:, 0]
+        gv = gv.contiguous()
+        if tuple(gm.shape) != (n, DO) or tuple(gv.shape) != (n,):
+            raise ValueError(f"conditional_vjp: dmean must be {(n, DO)} and dvar {(n, DO)} or {(n,)}")
+        nls = D if spec.ard else 1
+        d_q, d_Z, d_X, d_k = ctx.empty(M, DO), ctx.empty(M, D), ctx.empty(n, D), ctx.empty(2 + nls)
+        ctx.sparse_conditional_grad(spec, Z, Xd, q, self.white, settings.jitter, gm, gv, d_q, d_Z, d_X, d_k)
+        mf = self.mean_function
+        if mf.kind == "identity":
+            d_X = d_X + gm
+        elif mf.kind == "linear":
+            ctx.gemm(0, 1, 1.0, gm, ctx.to_device(mf.A.value), 1.0, d_X)
+        res = dict(q_mu=d_q, Z=d_Z, X=d_X, variance=d_k[:1], lengthscales=d_k[1:1 + nls])
+        scalars = ["variance"]
+        if spec.has_white:
+            res["white_variance"] = d_k[1 + nls:]
+            scalars.append("white_variance")
+        return res if on_device else _to_host(ctx, res, tuple(scalars))
 
 
 class Collapsed_Layer(Layer):

@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from .dgp import DGP_Base
 from .gpflow_compat import Gaussian
-from .layers import Collapsed_Layer, GPMC_Layer, GPR_Layer, SGPR_Layer, _to_host, concat_input_prop
+from .layers import Collapsed_Layer, GPMC_Layer, GPR_Layer, SGPMC_Layer, SGPR_Layer, _to_host, concat_input_prop
 
 
 class DGP_Collapsed(DGP_Base):
@@ -42,7 +42,17 @@ class DGP_Collapsed(DGP_Base):
             raise ValueError("DGP_Collapsed: the last layer must be a Collapsed_Layer (SGPR_Layer, GPR_Layer)")
         if any(isinstance(layer, Collapsed_Layer) for layer in layers[:-1]):
             raise ValueError("DGP_Collapsed: only the last layer is collapsed")
+        sgpmc = any(isinstance(layer, SGPMC_Layer) for layer in layers[:-1])
+        if sgpmc and len(layers) != 2:
+            raise NotImplementedError("DGP_Collapsed: an SGPMC_Layer is the ONE inner layer of a two-layer model, [SGPMC_Layer, SGPR_Layer] "
+                                      f"or [SGPMC_Layer, GPR_Layer], not one of {len(layers) - 1} inner layers: the collapsed layer takes "
+                                      "the marginal mean and variance of its inputs, which below a second inner layer need draws — "
+                                      "that is the engine's work, and the engine takes no layer without q_sqrt (an SVGP layer beside an "
+                                      "SGPMC layer needs it as well)")
         DGP_Base.__init__(self, X, Y, likelihood, layers, **kwargs)
+        object.__setattr__(self, "_sgpmc", sgpmc)
+        if sgpmc:
+            object.__setattr__(layers[0], "_model", weakref.ref(self))
         self.white = bool(layers[0].white) if len(layers) > 1 else False
         object.__setattr__(layers[-1], "_model", weakref.ref(self))          # the last layer draws its samples through this model's seeds
 
@@ -81,6 +91,8 @@ class DGP_Collapsed(DGP_Base):
     def inner_engine(self):
         if len(self.layers) == 1:
             raise RuntimeError("a one-layer DGP_Collapsed has no inner layers and no engine")
+        if self._sgpmc:
+            raise RuntimeError("a DGP_Collapsed over an SGPMC_Layer has no engine: the layer's conditional is a call of its own")
         if self._eng is None:
             from .engine import Engine
             inner = self.layers[:-1]
@@ -119,7 +131,7 @@ class DGP_Collapsed(DGP_Base):
         """Parameters that another engine (the DGP the inner layers are shared with) has trained since the last evaluation: reading
         `.value` pulls them to the host; if the inner engine's parameter vector then differs from the one it last saw, it uploads.
         (Whether the other engine still counts itself as newer than the host says nothing: any earlier read has settled that.)"""
-        if len(self.layers) == 1:
+        if len(self.layers) == 1 or self._sgpmc:
             return
         eng = self.inner_engine()
         for p, *_ in eng.entries:
@@ -139,10 +151,10 @@ class DGP_Collapsed(DGP_Base):
         inner = self.layers[:-1]
         zs = list(zs)[:len(inner)] if zs is not None else None
         self._refresh()
-        if full_cov:
+        if full_cov or self._sgpmc:                                 # the host layer loop; an SGPMC_Layer is in no engine
             F, Fs, Fmeans, Fvars = sX, [], [], []
             for layer, z in zip(inner, zs or [None] * len(inner)):
-                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=True)
+                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=full_cov)
                 Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
             return Fs, Fmeans, Fvars
         eng = self.inner_engine()
@@ -165,6 +177,16 @@ class DGP_Collapsed(DGP_Base):
         Xd, Yd = self._device_data()
         if len(self.layers) == 1:
             self.layers[-1].set_data(Xd, None, Yd, lik_var)
+            return
+        if self._sgpmc:                 # the layer's conditional at the training inputs: nothing is drawn, nothing leaves the device
+            low = self.layers[0]
+            mean, var = low.conditional_device(Xd)
+            var = var[:, None].expand(-1, low.num_outputs)
+            p = low.input_prop_dim
+            if p:
+                torch = self._context().torch
+                mean, var = torch.cat([Xd[:, :p], mean], 1), torch.cat([torch.zeros_like(Xd[:, :p]), var], 1)
+            self.layers[-1].set_data(mean.contiguous(), var.contiguous(), Yd, lik_var)
             return
         if self.layers[-2].input_prop_dim:
             _, ms, vs = self.inner_layers_propagate(self.X_data, full_cov=False, S=1, zs=zs)
@@ -226,6 +248,8 @@ class DGP_Collapsed(DGP_Base):
         `variance`, the likelihood's `variance`; there is no `feature.Z` — and `X_var` is all zeros (GPR_Layer.bound_gradients)."""
         inner = bool(inner) and len(self.layers) > 1
         top = self.layers[-1]
+        if self._sgpmc:
+            return self._sgpmc_gradients(inner)
         if inner:
             if self.layers[-2].input_prop_dim:
                 raise NotImplementedError("DGP_Collapsed.compute_log_likelihood_gradients(inner=True): the last inner layer propagates "
@@ -250,6 +274,53 @@ class DGP_Collapsed(DGP_Base):
             pairs += self._inner_pairs(eng)
         return g["bound"] - KL, pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
 
+    def _sgpmc_gradients(self, inner):
+        """compute_log_likelihood_gradients over an SGPMC_Layer: the top layer's adjoints in X_mean and X_var (the propagated columns'
+        dropped: they are copies of the fixed inputs) pushed through SGPMC_Layer.conditional_vjp, all on the device; with `inner` the
+        pairs go on with the layer's `feature.Z`, `q_mu`, kernel `variance`, `lengthscales` and a White part's `variance`."""
+        from .gpflow_compat import split_kernel
+        top, low = self.layers[-1], self.layers[0]
+        self._set_data()
+        g = top.bound_gradients(on_device=True)
+        scalars = ["bound", "variance", "lik_variance", "white_variance"]
+        low_pairs = []
+        if inner:
+            p = low.input_prop_dim or 0
+            v = low.conditional_vjp(g["X_mean"][:, p:].contiguous(), g["X_var"][:, p:].contiguous(), X=self._device_data()[0],
+                                    on_device=True)
+            stat, wk = split_kernel(low.kern)
+            low_pairs = [(low.feature.Z, "Z"), (low.q_mu, "q_mu"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales")] + \
+                        ([(wk.variance, "white_variance")] if wk is not None else [])
+            g.update({"low_" + k: v[k] for _, k in low_pairs})
+            scalars += ["low_variance", "low_white_variance"]
+        g = _to_host(self._context(), g, tuple(scalars))
+        pairs = [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape)) for p, k in self.top_parameters()]
+        pairs += [(p, np.asarray(g["low_" + k], dtype=np.float64).reshape(p.shape)) for p, k in low_pairs]
+        return g["bound"], pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
+
+    def _need_sgpmc(self, what):
+        if not self._sgpmc:
+            raise NotImplementedError(f"DGP_Collapsed.{what}: a log density needs a sampled inner layer with a prior — an SGPMC_Layer "
+                                      "below the collapsed layer (or a DGP_Heinonen)")
+
+    def compute_log_prior(self):
+        """the standard-normal prior of the SGPMC_Layer's q_mu"""
+        self._need_sgpmc("compute_log_prior")
+        return self.layers[0].log_prior()
+
+    def compute_log_density(self):
+        """compute_log_likelihood() + compute_log_prior(): the target of training.HMC and, with inner=True, of training.ScipyOptimizer"""
+        self._need_sgpmc("compute_log_density")
+        return self.compute_log_likelihood() + self.compute_log_prior()
+
+    def compute_log_density_gradients(self):
+        """(log density, [(Parameter, gradient), ...]): compute_log_likelihood_gradients(inner=True) with the prior added — -q_mu to
+        q_mu's pair"""
+        self._need_sgpmc("compute_log_density_gradients")
+        bound, pairs, _ = self.compute_log_likelihood_gradients(inner=True)
+        low = self.layers[0]
+        return bound + low.log_prior(), [(p, g - low.q_mu.value if p is low.q_mu else g) for p, g in pairs]
+
     def top_parameters(self):
         """[(Parameter, its key in the last layer's bound_gradients), ...]: what the collapsed last layer owns and the likelihood's
         variance.  SGPR_Layer: `feature.Z`, the kernel's `variance` and `lengthscales`, the noise variance.  GPR_Layer: no inducing
@@ -271,7 +342,7 @@ class DGP_Collapsed(DGP_Base):
         out = []
         for layer in self.layers[:-1]:
             stat, wk = split_kernel(layer.kern)
-            out += [layer.feature.Z, layer.q_mu, layer.q_sqrt, stat.variance, stat.lengthscales]
+            out += [layer.feature.Z, layer.q_mu] + ([layer.q_sqrt] if layer.q_sqrt is not None else []) + [stat.variance, stat.lengthscales]
             if wk is not None:
                 out.append(wk.variance)
             mf = layer.mean_function

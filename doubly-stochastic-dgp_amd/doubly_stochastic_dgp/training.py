@@ -89,7 +89,8 @@ class ScipyOptimizer:
             raise ValueError("ScipyOptimizer: none of the collapsed layer's parameters is trainable" if not inner else
                              "ScipyOptimizer: none of the model's parameters is trainable")
         kw = {"inner": True} if inner else {}
-        if isinstance(model, DGP_Heinonen):           # MAP: the log density (the prior of q_mu included), q_mu among the variables
+        if isinstance(model, DGP_Heinonen) or (inner and getattr(model, "_sgpmc", False)):
+            # MAP: the log density (the prior of q_mu included), q_mu among the variables
             gradients = lambda: model.compute_log_density_gradients() + (None,)
         else:
             gradients = lambda: model.compute_log_likelihood_gradients(zs=zs, **kw)
@@ -176,6 +177,9 @@ class CollapsedAdamOptimizer:
         from .model_zoo import DGP_Collapsed, DGP_Heinonen
         if not isinstance(model, DGP_Collapsed):
             raise NotImplementedError(f"CollapsedAdamOptimizer trains a DGP_Collapsed; {type(model).__name__} is trained by AdamOptimizer")
+        if getattr(model, "_sgpmc", False):
+            raise NotImplementedError("CollapsedAdamOptimizer steps the inner layers through their engine, which a model over an "
+                                      "SGPMC_Layer does not have: sample it with HMC or fit it with ScipyOptimizer(inner=True) (MAP)")
         if isinstance(model, DGP_Heinonen):
             raise NotImplementedError("CollapsedAdamOptimizer steps the inner layers through their engine, which a DGP_Heinonen does not "
                                       "have: sample it with HMC or fit it with ScipyOptimizer (MAP)")
@@ -317,7 +321,7 @@ class HMC:
         from ._lib import CholeskyError
         from .gpflow_compat import positive_forward
         from .model_zoo import DGP_Heinonen
-        if not isinstance(model, DGP_Heinonen):
+        if not isinstance(model, DGP_Heinonen) and not getattr(model, "_sgpmc", False):
             raise NotImplementedError(f"HMC samples a DGP_Heinonen; {type(model).__name__} has no log density to sample from")
         if int(num_samples) < 1 or int(thin) < 1 or int(burn) < 0 or int(lmin) < 1 or int(lmax) < int(lmin) or not float(epsilon) > 0.0:
             raise ValueError("HMC.sample: num_samples, thin >= 1, burn >= 0, 1 <= lmin <= lmax, epsilon > 0")

@@ -651,6 +651,35 @@ int dsdgp_gpr_bound(dsdgp_ctx* ctx, int64_t n, int32_t DY, const double* L, int6
  * second operand. */
 int dsdgp_gpr_var(dsdgp_ctx* ctx, int64_t n, int64_t ns, int32_t DY, const double* A, int64_t lda, double kdiag, double* var);
 
+/* dsdgp_sparse_conditional / dsdgp_sparse_conditional_grad: the reference's sparse conditional on the branch `q_sqrt is None`
+ * (layers.py:178-219, line 200), which is all of its SGPMC_Layer (layers.py:249-260), and the reverse pass tf.gradients builds through it.
+ * kern: RBF or Matern52, scalar or ARD lengthscales, with or without a White part; Z (M x D), X (n x D), q_mu (M x DO): device.  With
+ *   Ku = K(Z, Z) + jitter I (White on the diagonal, as dsdgp_gram's symmetric form),  Lu = chol(Ku),  A = Lu^-1 K(Z, X),
+ *   W = q_mu (white != 0) or Lu^-1 q_mu,  kd = variance + White variance:
+ *   mean (n x DO) = A^T W,   var (n) = kd - sum_i A_ir^2 in ascending i: ONE column, the reference gives every output the same variance.
+ * Reverse, given gm = dJ/dmean (n x DO) and gv = dJ/dvar already summed over the outputs (n), every output optional and OVERWRITTEN:
+ *   d_q_mu (M x DO);  d_Z (M x D);  d_X (n x D);  d_kern (2 + (ard ? D : 1) doubles): variance, lengthscales, then the gradient in what is
+ *   added to Ku's diagonal — with a White part the White variance, which also takes kd's adjoint sum_r gv_r; without one the jitter.
+ * The Gram matrices, the factorisation, the solves, the M x M products and the two Gram reverse passes are this library's own calls; the
+ * passes over the M x n matrix A are two kernels of their own (csrc/sparse_cond.hip): one read of a tile of A gives mean and var, one read
+ * gives A_bar and the tile's part of A gm.  No floating-point atomics; every summation order follows from (n, M, D, DO) alone
+ * (csrc/sparse_cond_plan.hpp): the same call gives the same bits, whichever outputs are asked for.
+ * SCRATCH: the composed calls use the context's scratch, so the intermediates live in a block the CALLER holds: `scratch` (device, 256-byte
+ * aligned) of at least dsdgp_sparse_conditional_scratch_bytes(n, M, D, DO, reverse) bytes.  No state is saved between the two calls: the
+ * reverse call repeats the forward's factorisation and solves itself.
+ * info (host, may be NULL): the Cholesky status, as dsdgp_potrf; a failed factorisation returns DSDGP_ERR_NOT_SPD and writes no output.
+ * M <= 2048.  The forward takes any input_dim dsdgp_gram takes; the reverse inherits dsdgp_gram_grad's input_dim <= 32
+ * (DSDGP_ERR_UNSUPPORTED, nothing launched).  DSDGP_ERR_UNSUPPORTED for more than 8 GB of scratch; DSDGP_ERR_BAD_ARG for M, n, DO out of
+ * range, a NULL input, or a scratch block that is too small.  Asynchronous up to the read of the Cholesky status. */
+int dsdgp_sparse_conditional_scratch_bytes(int64_t n, int32_t M, int32_t D, int32_t DO, int32_t reverse, int64_t* bytes);
+int dsdgp_sparse_conditional(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* X, int64_t n,
+                             const double* q_mu, int32_t DO, int32_t white, double jitter, void* scratch, int64_t scratch_bytes,
+                             double* mean, double* var, int* info);
+int dsdgp_sparse_conditional_grad(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* X, int64_t n,
+                                  const double* q_mu, int32_t DO, int32_t white, double jitter, const double* gm, const double* gv,
+                                  void* scratch, int64_t scratch_bytes, double* d_q_mu, double* d_Z, double* d_X, double* d_kern,
+                                  int* info);
+
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
 
