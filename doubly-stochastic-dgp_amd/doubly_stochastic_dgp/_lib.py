@@ -54,6 +54,19 @@ class ModelDesc(C.Structure):
                 ("layers", LayerDesc * DSDGP_MAX_LAYERS)]
 
 
+class StackLayer(C.Structure):
+    """dsdgp_stack_layer: Z, q_mu, mean_A, mean_b are device pointers"""
+    _fields_ = [("kern", KernelSpec), ("Z", C.c_void_p), ("q_mu", C.c_void_p), ("mean_A", C.c_void_p), ("mean_b", C.c_void_p),
+                ("M", C.c_int32), ("DO", C.c_int32), ("white", C.c_int32), ("mean_kind", C.c_int32), ("input_prop_dim", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class StackDesc(C.Structure):
+    """dsdgp_stack_desc"""
+    _fields_ = [("L", C.c_int32), ("lik_kind", C.c_int32), ("lik_width", C.c_int32), ("reserved", C.c_int32),
+                ("lik_p0", C.c_double), ("lik_p1", C.c_double), ("jitter", C.c_double), ("layers", StackLayer * DSDGP_MAX_LAYERS)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -183,6 +196,20 @@ _PROTOS = {
     "dsdgp_sparse_conditional_grad": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                                 C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    # DGP_Base over SGPMC layers (dgp.py:42-98, layers.py:249-260): the whole stack forward and backward in a block the caller holds
+    "dsdgp_sizeof_stack_desc": (C.c_int, []),
+    "dsdgp_stack_scratch_bytes": (C.c_int, [C.POINTER(StackDesc), C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "dsdgp_stack_propagate": (C.c_int, [C.c_void_p, C.POINTER(StackDesc), C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
+                                        C.c_uint64, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    "dsdgp_stack_logdensity": (C.c_int, [C.c_void_p, C.POINTER(StackDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
+                                         C.POINTER(C.c_void_p), C.c_uint64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_int)]),
+    "dsdgp_stack_hop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "dsdgp_stack_hop_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
+                                      C.c_void_p, C.c_void_p]),
+    "dsdgp_sghmc_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
     "dsdgp_model_set_grad_first_layer":(C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),

@@ -361,7 +361,8 @@ class SGPMC_Layer(Layer):
     A = Lu^-1 K(Z, X), mean = A^T W + m(X) with W = q_mu (white) or Lu^-1 q_mu, variance = Kdiag - colsum(A^2) for every output
     (dsdgp_sparse_conditional), and `conditional_vjp` is its reverse pass (dsdgp_sparse_conditional_grad).  Unlike GPMC_Layer nothing is
     frozen at construction: Z and the kernel are read at every evaluation and have gradients.  Constructing the layer touches no
-    device.  It lives under a collapsed layer in a DGP_Collapsed; the engine does not take it (its KL tail reads a q_sqrt)."""
+    device.  It lives under a collapsed layer in a DGP_Collapsed, or at every depth of a model_zoo.DGP_SGPMC; the engine does not take it
+    (its KL tail reads a q_sqrt)."""
 
     def __init__(self, kern, Z, num_outputs, mean_function, white=False, input_prop_dim=None, **kwargs):
         Layer.__init__(self, input_prop_dim, **kwargs)

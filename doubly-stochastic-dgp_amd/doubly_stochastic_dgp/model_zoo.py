@@ -1,6 +1,7 @@
 """Host mirror of the reference's model_zoo.py:25-88: `DGP_Collapsed`, a DGP whose last layer is a collapsed one (layers.SGPR_Layer, or
 the dense layers.GPR_Layer: exact GP regression on top, no inducing inputs, gradients through the reverse pass of the Gram matrix), and
-`DGP_Heinonen` (at the end of this file), the dense two-layer model sampled by training.HMC.  What follows describes `DGP_Collapsed`.
+`DGP_Heinonen`, the dense two-layer model sampled by training.HMC, and (at the end of this file) `DGP_SGPMC`, the reference's DGP_Base
+over SGPMC layers (dgp.py:42-98), sampled by training.SGHMC.  What follows describes `DGP_Collapsed`.
 Its bound is the one of the reference's `_build_likelihood`: the last layer at its exact optimum over the WHOLE training set, the input
 noise of the last hop integrated analytically through the kernel expectations, minus the KL terms of the inner layers.  The inner
 layers run as one device Engine over `layers[:-1]` (`inner_engine()`; S = 1 on the full training set, explicit `zs` accepted); the
@@ -451,3 +452,515 @@ class DGP_Heinonen(DGP_Collapsed):
         bound, pairs, _ = self.compute_log_likelihood_gradients()
         low = self.layers[0]
         return bound + low.log_prior(), [(p, g - low.q_mu.value if p is low.q_mu else g) for p, g in pairs]
+
+
+class DGP_SGPMC(DGP_Base):
+    """The doubly-stochastic DGP with sampling in place of the Gaussian posterior: the reference's
+    `DGP_Base(X, Y, likelihood, [SGPMC_Layer, ...], minibatch_size, num_samples)` (dgp.py:42-98 over layers.py:249-260) — layers without
+    q_sqrt at every depth, a draw between them, the last layer not sampled — whose density is
+    `num_data / N * sum E_q[log p(y | f)]` over a minibatch of N rows plus the standard-normal priors of every `q_mu`, the target of
+    `training.SGHMC`.  Any likelihood of the project, MultiClass and Bernoulli included.  Every evaluation is ONE library call over the
+    whole stack (dsdgp_stack_propagate, dsdgp_stack_logdensity: csrc/sgpmc_stack.hip) in a scratch block this model holds; the
+    parameters are read from the host Parameters at every evaluation.  There is no engine (its KL tail reads a q_sqrt): `engine()`,
+    `train_step`, `training.AdamOptimizer`, `NatGradOptimizer`, `ScipyOptimizer` and `HMC` refuse the model.
+    `compute_log_likelihood(X, Y, zs)` is the data term, `compute_log_prior()` the priors, `compute_log_density(...)` their sum and
+    `compute_log_density_gradients(...)` the sum with `[(Parameter, gradient), ...]` in the constrained values: per layer `feature.Z`,
+    `q_mu`, the kernel's `variance` and `lengthscales`, a White part's `variance` — the pairs DGP_Collapsed over an SGPMC layer gives —
+    then the likelihood's parameter where it has one.  X = Y = None: the next minibatch.  zs: explicit draws per sampled layer,
+    broadcastable to (S, N, D_out); else Philox draws under the model's next seed, or under the seed `fix_draws(seed)` pinned
+    (`fix_draws(None)` releases it), so that finite differences and replays see one function.  Test sets go through in row batches
+    that fit `scratch_budget` bytes of scratch."""
+    supports_gradients = False
+    scratch_budget = 1 << 30
+
+    def __init__(self, X, Y, likelihood, layers, minibatch_size=None, num_samples=1, num_data=None, **kwargs):
+        from .gpflow_compat import likelihood_entry
+        layers = list(layers)
+        if not layers or len(layers) > _lib.DSDGP_MAX_LAYERS:
+            raise ValueError(f"DGP_SGPMC: 1 .. {_lib.DSDGP_MAX_LAYERS} layers, not {len(layers)}")
+        for layer in layers:
+            if not isinstance(layer, SGPMC_Layer):
+                raise ValueError(f"DGP_SGPMC: every layer is an SGPMC_Layer, not {type(layer).__name__}: layers with a q_sqrt are the "
+                                 "engine's (DGP), dense and collapsed ones DGP_Heinonen's and DGP_Collapsed's")
+            layer._check_mean("DGP_SGPMC")
+        if layers[-1].input_prop_dim:
+            raise ValueError("DGP_SGPMC: the last layer propagates no inputs (input_prop_dim): its outputs are the likelihood's")
+        likelihood_entry(likelihood)
+        DGP_Base.__init__(self, X, Y, likelihood, layers, minibatch_size=minibatch_size, num_samples=num_samples, num_data=num_data, **kwargs)
+        for layer in layers:
+            object.__setattr__(layer, "_model", weakref.ref(self))
+        object.__setattr__(self, "_fixed_seed", None)
+        object.__setattr__(self, "_scratch", None)
+
+    def engine(self):
+        raise NotImplementedError("DGP_SGPMC.engine: there is no device engine over SGPMC layers — the engine's KL tail reads a q_sqrt from "
+                                  "every layer record; the stack runs as one library call of its own (dsdgp_stack_propagate / "
+                                  "dsdgp_stack_logdensity): use propagate, predict_*, compute_log_density[_gradients], training.SGHMC")
+
+    def train_step(self, *args, **kwargs):
+        raise NotImplementedError("DGP_SGPMC.train_step: the model is sampled, not optimised on a bound: training.SGHMC")
+
+    def _context(self):
+        from .engine import Context
+        return Context.get()
+
+    def _device_data(self):
+        if self._dev_data is None:
+            ctx = self._context()
+            object.__setattr__(self, "_dev_data", (ctx.to_device(self.X_data), ctx.to_device(self.Y_data)))
+        return self._dev_data
+
+    def next_minibatch(self):
+        """Device tensors (Xb, Yb) of the next minibatch (dgp.py:51-52), or the full data when not minibatching"""
+        Xd, Yd = self._device_data()
+        if self._minibatch is None:
+            return Xd, Yd
+        ctx = self._context()
+        idx = ctx.torch.from_numpy(self._minibatch.next_indices()).to(Xd.device)
+        n = idx.shape[0]
+        Xb, Yb = ctx.empty(n, Xd.shape[1]), ctx.empty(n, Yd.shape[1])
+        _lib.check(ctx.lib.dsdgp_gather_rows2(ctx.handle, C.c_void_p(Xd.data_ptr()), Xd.shape[1], C.c_void_p(Xb.data_ptr()),
+                                              C.c_void_p(Yd.data_ptr()), Yd.shape[1], C.c_void_p(Yb.data_ptr()),
+                                              C.c_void_p(idx.data_ptr()), n, 0))
+        object.__setattr__(self, "_keep_idx", idx)
+        return Xb, Yb
+
+    def randn(self, shape, seed=None):
+        """N(0, 1) draws for Layer.sample_from_conditional without z, under this model's seed sequence"""
+        ctx = self._context()
+        n = int(np.prod(shape))
+        out = ctx.empty(n)
+        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(self._eval_seed() if seed is None else seed), C.c_uint64(0), n,
+                                       C.c_void_p(out.data_ptr())))
+        ctx.sync()
+        return out.cpu().numpy().reshape(shape)
+
+    def fix_draws(self, seed):
+        """pin the Philox seed of every evaluation that is given no zs (None: back to a fresh seed per evaluation)"""
+        object.__setattr__(self, "_fixed_seed", None if seed is None else int(seed))
+
+    def _eval_seed(self):
+        return self._draw_seed() if self._fixed_seed is None else self._fixed_seed
+
+    # ------------------------------------------------------------------ the library's view of the model
+    def parameter_list(self):
+        """[(Parameter, its block of the flat gradient: layer index or None, key)] in the order of compute_log_density_gradients: per
+        layer `feature.Z`, `q_mu`, kernel `variance`, `lengthscales`, a White part's `variance`; then the likelihood's parameter"""
+        from .gpflow_compat import likelihood_entry, split_kernel
+        out = []
+        for l, layer in enumerate(self.layers):
+            stat, wk = split_kernel(layer.kern)
+            out += [(layer.feature.Z, l, "Z"), (layer.q_mu, l, "q_mu"), (stat.variance, l, "variance"), (stat.lengthscales, l, "lengthscales")]
+            if wk is not None:
+                out.append((wk.variance, l, "white_variance"))
+        par = likelihood_entry(self.likelihood.likelihood)[1]
+        if par is not None:
+            out.append((par, None, "lik"))
+        return out
+
+    def _stack_desc(self, ctx):
+        """(StackDesc at the Parameters' current values, what its pointers point to: keep it until the device is done)"""
+        from . import settings
+        from .gpflow_compat import likelihood_args
+        from .layers import _kernel_spec
+        keep = []
+        if ctx.lib.dsdgp_sizeof_stack_desc() != C.sizeof(_lib.StackDesc):
+            raise _lib.DsdgpError("_lib.StackDesc does not mirror dsdgp_stack_desc as the library was compiled")
+        d = _lib.StackDesc()
+        d.L = len(self.layers)
+        d.lik_kind, d.lik_p0, d.lik_p1 = likelihood_args(self.likelihood.likelihood)
+        d.lik_width = self.layers[-1].num_outputs
+        d.jitter = float(settings.jitter)
+        mean_kind = {"zero": _lib.MEAN_ZERO, "identity": _lib.MEAN_IDENTITY, "linear": _lib.MEAN_LINEAR}
+        for l, layer in enumerate(self.layers):
+            layer._check_mean("DGP_SGPMC")
+            spec, ls = _kernel_spec(layer.kern)
+            Z, q = ctx.to_device(layer.feature.Z.value), ctx.to_device(layer.q_mu.value)
+            if Z.shape[1] != spec.input_dim:
+                raise ValueError(f"DGP_SGPMC: layer {l}: Z is {tuple(Z.shape)}, the kernel's input_dim {spec.input_dim}")
+            y = d.layers[l]
+            y.kern, y.Z, y.q_mu = spec, Z.data_ptr(), q.data_ptr()
+            y.M, y.DO, y.white, y.input_prop_dim = Z.shape[0], layer.num_outputs, int(layer.white), int(layer.input_prop_dim or 0)
+            kind = getattr(layer.mean_function, "kind", None)
+            if kind not in mean_kind:
+                raise NotImplementedError(f"DGP_SGPMC: mean function {type(layer.mean_function).__name__}: Zero, Identity and a fixed Linear")
+            y.mean_kind = mean_kind[kind]
+            keep += [ls, Z, q]
+            if kind == "linear":
+                A = ctx.to_device(layer.mean_function.A.value)
+                if tuple(A.shape) != (spec.input_dim, layer.num_outputs):
+                    raise ValueError(f"DGP_SGPMC: layer {l}: Linear mean function: A is {tuple(A.shape)}, the layer maps "
+                                     f"{spec.input_dim} -> {layer.num_outputs}")
+                y.mean_A = A.data_ptr()
+                keep.append(A)
+                if np.any(layer.mean_function.b.value != 0.0):
+                    b = ctx.to_device(layer.mean_function.b.value)
+                    y.mean_b = b.data_ptr()
+                    keep.append(b)
+            elif kind == "identity" and spec.input_dim != layer.num_outputs:
+                raise ValueError(f"DGP_SGPMC: layer {l}: an Identity mean function needs as many outputs as inputs, not "
+                                 f"{spec.input_dim} -> {layer.num_outputs}")
+        return d, keep
+
+    def _scratch_bytes(self, ctx, d, n, S, reverse):
+        """the scratch the stack takes on n rows, or None where the library refuses the size"""
+        need = C.c_int64()
+        rc = ctx.lib.dsdgp_stack_scratch_bytes(C.byref(d), n, S, int(reverse), C.byref(need))
+        if rc == _lib.ERR_UNSUPPORTED and not reverse:
+            return None
+        _lib.check(rc)
+        return need.value
+
+    def _scratch_block(self, ctx, nbytes):
+        if self._scratch is None or self._scratch.numel() * 8 < nbytes:
+            object.__setattr__(self, "_scratch", None)
+            object.__setattr__(self, "_scratch", ctx.empty(nbytes // 8 + 32))
+        return self._scratch
+
+    def _device_zs(self, ctx, zs, n, S, keep):
+        """the ctypes array of L draw pointers ((S n, D_out) each, row s n + i) from zs (None, or per layer None / an array or tensor
+        broadcastable to (S, n, D_out))"""
+        L = len(self.layers)
+        arr = (C.c_void_p * L)()
+        if zs is None:
+            return arr
+        for l, z in enumerate(list(zs)[:L - 1]):
+            if z is None:
+                continue
+            DO = self.layers[l].num_outputs
+            if hasattr(z, "data_ptr"):
+                t = ctx.as_device(z).expand(S, n, DO).reshape(S * n, DO).contiguous()
+            else:
+                t = ctx.to_device(np.broadcast_to(np.asarray(z, dtype=np.float64), (S, n, DO)).reshape(S * n, DO))
+            keep.append(t)
+            arr[l] = t.data_ptr()
+        return arr
+
+    # ------------------------------------------------------------------ dgp.py:61-76
+    def propagate_device(self, X, S=1, zs=None, want=("F", "mean", "var"), seed=None):
+        """dsdgp_stack_propagate on X (numpy or a device tensor, (n, D_in)) -> {"F", "mean", "var"}: per asked-for key the list over the
+        layers of device tensors (S n, .), row s n + i — F with its propagated columns, var ONE column (S n,) — without waiting for
+        them.  CholeskyError if some layer's Ku is not positive definite: nothing is written then."""
+        ctx = self._context()
+        Xd = ctx.as_device(X)
+        n, S, L = Xd.shape[0], int(S), len(self.layers)
+        d, keep = self._stack_desc(ctx)
+        nbytes = self._scratch_bytes(ctx, d, n, S, False)
+        if nbytes is None:
+            raise _lib.DsdgpError(f"DGP_SGPMC: {n} rows x {S} samples take more than 8 GB of scratch: pass the rows in batches")
+        scr = self._scratch_block(ctx, nbytes)
+        out, ptrs = {}, {}
+        for k in ("F", "mean", "var"):
+            ptrs[k] = (C.c_void_p * L)()
+            if k in want:
+                out[k] = []
+                for l, layer in enumerate(self.layers):
+                    w = layer.num_outputs + (int(layer.input_prop_dim or 0) if k == "F" else 0)
+                    t = ctx.empty(S * n) if k == "var" else ctx.empty(S * n, w)
+                    out[k].append(t)
+                    ptrs[k][l] = t.data_ptr()
+        zarr = self._device_zs(ctx, zs, n, S, keep)
+        _lib.check(ctx.lib.dsdgp_stack_propagate(ctx.handle, C.byref(d), C.c_void_p(Xd.data_ptr()), n, S, zarr,
+                                                 C.c_uint64(self._eval_seed() if seed is None else int(seed)), C.c_void_p(scr.data_ptr()),
+                                                 nbytes, ptrs["F"], ptrs["mean"], ptrs["var"], C.byref(C.c_int(0))))
+        object.__setattr__(self, "_keep", (keep, Xd))
+        return out
+
+    def _row_batch(self, ctx, N, S):
+        """rows per batch: the most (up to N) whose scratch fits scratch_budget"""
+        d, keep = self._stack_desc(ctx)
+        nb = N
+        while nb > 1:
+            need = self._scratch_bytes(ctx, d, nb, S, False)
+            if need is not None and need <= self.scratch_budget:
+                break
+            nb = (nb + 1) // 2
+        return nb
+
+    def _batches(self, X, S, zs):
+        """(a, b, the batch's zs) over the row batches of X"""
+        ctx = self._context()
+        N = X.shape[0]
+        nb = self._row_batch(ctx, N, int(S))
+        for a in range(0, N, nb):
+            b = min(a + nb, N)
+            zb = None
+            if zs is not None:
+                zb = [z if z is None or np.ndim(z) < 2 or np.shape(z)[-2] == 1 else z[..., a:b, :] for z in zs]
+            yield a, b, zb
+
+    def propagate(self, X, full_cov=False, S=1, zs=None):
+        S = int(S)
+        Xh = X.cpu().numpy() if hasattr(X, "data_ptr") else np.asarray(X, dtype=np.float64)
+        if full_cov:                                                # the host layer loop of dgp.py:69-74, as DGP_Base.propagate
+            F, Fs, Fmeans, Fvars = np.tile(Xh[None], [S, 1, 1]), [], [], []
+            for layer, z in zip(self.layers, zs or [None] * len(self.layers)):
+                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=True)
+                Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
+            return Fs, Fmeans, Fvars
+        ctx = self._context()
+        N, L = Xh.shape[0], len(self.layers)
+        widths = [(layer.num_outputs, int(layer.input_prop_dim or 0)) for layer in self.layers]
+        Fs = [np.empty((S, N, p + DO)) for DO, p in widths]
+        Fmeans, Fvars = [np.empty((S, N, DO)) for DO, p in widths], [np.empty((S, N, DO)) for DO, p in widths]
+        for a, b, zb in self._batches(Xh, S, zs):
+            r = self.propagate_device(Xh[a:b], S, zs=zb)
+            ctx.sync()
+            for l, (DO, p) in enumerate(widths):
+                Fs[l][:, a:b] = r["F"][l].cpu().numpy().reshape(S, b - a, p + DO)
+                Fmeans[l][:, a:b] = r["mean"][l].cpu().numpy().reshape(S, b - a, DO)
+                Fvars[l][:, a:b] = r["var"][l].cpu().numpy().reshape(S, b - a, 1)
+        Fin = np.tile(Xh[None], [S, 1, 1])
+        for l, (DO, p) in enumerate(widths):                       # layers.py:105-117: the means get the same copies, the variances zeros
+            if p:
+                Fmeans[l] = np.concatenate([Fin[:, :, :p], Fmeans[l]], 2)
+                Fvars[l] = np.concatenate([np.zeros((S, N, p)), Fvars[l]], 2)
+            Fin = Fs[l]
+        return Fs, Fmeans, Fvars
+
+    def _build_predict(self, X, full_cov=False, S=1, zs=None):
+        _, Fmeans, Fvars = self.propagate(X, full_cov=full_cov, S=S, zs=zs)
+        return Fmeans[-1], Fvars[-1]
+
+    # ------------------------------------------------------------------ dgp.py:92-98 and the priors of layers.py:257
+    def log_density_device(self, X=None, Y=None, zs=None, with_grad=False, seed=None):
+        """dsdgp_stack_logdensity -> (out, grad): device tensors, out (4,) = [log density, data term, priors, 0], grad flat in the
+        library's layout or None; the host has waited for neither.  CholeskyError: nothing was written."""
+        ctx = self._context()
+        if X is None:
+            Xd, Yd = self.next_minibatch()
+        else:
+            if not hasattr(Y, "data_ptr"):
+                self.likelihood.check_targets(Y)
+            Xd, Yd = ctx.as_device(X), ctx.as_device(Y)
+        n, S = Xd.shape[0], self.num_samples
+        if Yd.dim() != 2 or Yd.shape[0] != n:
+            raise ValueError(f"X has {n} rows, Y {tuple(Yd.shape)}")
+        d, keep = self._stack_desc(ctx)
+        nbytes = self._scratch_bytes(ctx, d, n, S, with_grad)
+        scr = self._scratch_block(ctx, nbytes)
+        out = ctx.empty(4)
+        grad = None
+        if with_grad:
+            count = 1
+            for layer in self.layers:
+                M, D = layer.feature.Z.shape
+                count += M * D + M * layer.num_outputs + 2 + (D if split_kernel_ard(layer.kern) else 1)
+            grad = ctx.empty(count)
+        zarr = self._device_zs(ctx, zs, n, S, keep)
+        _lib.check(ctx.lib.dsdgp_stack_logdensity(ctx.handle, C.byref(d), C.c_void_p(Xd.data_ptr()), C.c_void_p(Yd.data_ptr()), n, S, zarr,
+                                                  C.c_uint64(self._eval_seed() if seed is None else int(seed)),
+                                                  float(self.num_data) / float(n), C.c_void_p(scr.data_ptr()), nbytes,
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(grad.data_ptr() if with_grad else 0),
+                                                  C.byref(C.c_int(0))))
+        object.__setattr__(self, "_keep", (keep, Xd, Yd))
+        return out, grad
+
+    def _out4(self, X, Y, zs):
+        out, _ = self.log_density_device(X, Y, zs)
+        self._context().sync()
+        return out.cpu().numpy()
+
+    def _build_likelihood(self, X=None, Y=None, zs=None, with_grad=False, **kwargs):
+        if with_grad:
+            raise NotImplementedError("DGP_SGPMC._build_likelihood(with_grad=True) would leave a gradient in an engine, which the model "
+                                      "does not have: compute_log_density_gradients")
+        return float(self._out4(X, Y, zs)[1])
+
+    def compute_log_prior(self):
+        """the standard-normal priors of every layer's q_mu (layers.py:257); host arithmetic on the Parameters"""
+        return float(sum(layer.log_prior() for layer in self.layers))
+
+    def compute_log_density(self, X=None, Y=None, zs=None):
+        return float(self._out4(X, Y, zs)[0])
+
+    def split_gradient(self, grad):
+        """the flat gradient of the library (a numpy array) as [(Parameter, gradient), ...] in the order of parameter_list()"""
+        blocks, at = [], 0
+        for layer in self.layers:
+            M, D = layer.feature.Z.shape
+            DO, nls = layer.num_outputs, (D if split_kernel_ard(layer.kern) else 1)
+            b = dict(Z=grad[at:at + M * D].reshape(M, D), q_mu=grad[at + M * D:at + M * D + M * DO].reshape(M, DO))
+            at += M * D + M * DO
+            b.update(variance=grad[at:at + 1], lengthscales=grad[at + 1:at + 1 + nls], white_variance=grad[at + 1 + nls:at + 2 + nls])
+            at += 2 + nls
+            blocks.append(b)
+        return [(p, np.array((blocks[l][k] if l is not None else grad[at:at + 1]), dtype=np.float64).reshape(p.shape))
+                for p, l, k in self.parameter_list()]
+
+    def compute_log_density_gradients(self, X=None, Y=None, zs=None):
+        """(log density, [(Parameter, gradient), ...]) of one evaluation: the next minibatch (or X, Y), S = num_samples draws"""
+        out, grad = self.log_density_device(X, Y, zs, with_grad=True)
+        self._context().sync()
+        return float(out.cpu().numpy()[0]), self.split_gradient(grad.cpu().numpy())
+
+    # ------------------------------------------------------------------ scoring over posterior samples
+    def _states(self, run):
+        """the kept states of a run of training.SGHMC as a list of assignments [(Parameter, value), ...]; None: the current state"""
+        if run is None:
+            return [[]]
+        T = len(run["logprobs"])
+        return [[(p, run["samples"][name][t]) for name, p in zip(run["names"], run["variables"])] for t in range(T)]
+
+    def components_device(self, Xs, S, run=None, zs=None):
+        """The last layer's mean and variance (T S N, D_Y each — the one variance column repeated — row (t S + s) N + i) as device
+        tensors: every kept state of `run` set in turn (the model is left at the last), S components each.  The form every mixture
+        primitive takes, with T S components."""
+        ctx = self._context()
+        means, vars_ = [], []
+        DY = self.layers[-1].num_outputs
+        for state in self._states(run):
+            for p, v in state:
+                p.assign(v)
+            r = self.propagate_device(Xs, S, zs=zs, want=("mean", "var"))
+            means.append(r["mean"][-1])
+            vars_.append(r["var"][-1][:, None].expand(-1, DY))
+        return ctx.torch.cat(means, 0).contiguous(), ctx.torch.cat(vars_, 0).contiguous(), len(means) * int(S)
+
+    def _score_batches(self, Xs, Ys, S, run, call):
+        """call(a, b, mean, var, Yb, components) over the row batches of Xs that fit the scratch, then one synchronisation"""
+        ctx = self._context()
+        Xd = ctx.as_device(Xs)
+        Yd = None if Ys is None else ctx.as_device(Ys)
+        N = Xd.shape[0]
+        if N < 1 or (Yd is not None and Yd.shape[0] != N):
+            raise ValueError(f"Xs has {N} rows, Ys {None if Yd is None else Yd.shape[0]}")
+        nb = self._row_batch(ctx, N, int(S))
+        keep = []
+        for a in range(0, N, nb):
+            b = min(a + nb, N)
+            mean, var, comps = self.components_device(Xd[a:b], S, run)
+            Yb = None if Yd is None else Yd[a:b].contiguous()
+            keep.append((mean, var, Yb, call(a, b, mean, var, Yb, comps)))
+        ctx.sync()
+
+    def predict_y_samples(self, Xs, S, run):
+        """(mean, variance) of y for every component: (T S, N*, D_Y) arrays, the likelihood's predict_mean_and_var of each kept state's
+        S components (dgp.py:116-119)"""
+        ctx = self._context()
+        outs = []
+
+        def call(a, b, mean, var, Yb, comps):
+            outs.append((a, b, mean, var, comps))
+        self._score_batches(Xs, None, S, run, call)
+        N, DY = ctx.as_device(Xs).shape[0], self.layers[-1].num_outputs
+        comps = outs[0][4]
+        m, v = np.empty((comps, N, DY)), np.empty((comps, N, DY))
+        for a, b, mean, var, _ in outs:
+            pm, pv = self.likelihood.predict_mean_and_var(mean.cpu().numpy().reshape(comps, b - a, DY), var.cpu().numpy().reshape(comps, b - a, DY))
+            m[:, a:b], v[:, a:b] = pm, pv
+        return m, v
+
+    def predict_density(self, Xnew, Ynew, num_samples, run=None):
+        """dgp.py:121-126: logsumexp over the components of log p(y | f) minus the logarithm of their number, (N*, D); with `run` the
+        components are the T num_samples of its kept states"""
+        if run is None:
+            return DGP_Base.predict_density(self, Xnew, Ynew, num_samples)
+        ctx = self._context()
+        N, DY = Xnew.shape[0], self.layers[-1].num_outputs
+        mean, var, comps = self.components_device(Xnew, num_samples, run)
+        ctx.sync()
+        return self.likelihood.predict_density_logmeanexp(mean.cpu().numpy().reshape(comps, N, DY), var.cpu().numpy().reshape(comps, N, DY),
+                                                          np.asarray(Ynew, dtype=np.float64))
+
+    def evaluate(self, Xs, Ys, S, run=None, Y_std=1.0, return_rows=False):
+        """Held-out scores of the mixture of the T S components of `run` (None: the S of the current state) by dsdgp_eval_mixture: the
+        dict of DGP_Base.evaluate — `rmse` / `rmse_per_output` (MultiClass: `error_rate`), `log_density`, `n`, and with return_rows
+        `rows` (N*, D, 3)."""
+        from .gpflow_compat import MultiClass, likelihood_args
+        ctx = self._context()
+        lik = self.likelihood.likelihood
+        if not hasattr(Ys, "data_ptr"):
+            self.likelihood.check_targets(Ys)
+        gaussian = not self.likelihood.needs_broadcasting
+        Y_std = float(Y_std)
+        if not Y_std > 0.0 or (not gaussian and Y_std != 1.0):
+            raise ValueError("Y_std rescales a Gaussian density only (and must be positive)")
+        kind, p0, p1 = likelihood_args(lik)
+        D = self.layers[-1].num_outputs
+        N = Xs.shape[0]
+        acc = ctx.empty(3, D)
+        rows = ctx.empty(N, D, 3) if return_rows else None
+        self._score_batches(Xs, Ys, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_eval_mixture(
+            ctx.handle, kind, p0, p1, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(Yb.data_ptr()), b - a, comps, D,
+            C.c_void_p(rows[a:b].data_ptr() if return_rows else 0), C.c_void_p(acc.data_ptr()), int(a > 0))))
+        sums = acc.cpu().numpy()
+        out = {"n": N}
+        if isinstance(lik, MultiClass):
+            cnt = float(sums[2, 0])
+            out["error_rate"], out["log_density"] = float(sums[0, 0]) / cnt, float(sums[1, 0]) / cnt
+        else:
+            cnt = float(sums[2].sum())
+            out["rmse"] = Y_std * float(np.sqrt(sums[0].sum() / cnt))
+            out["rmse_per_output"] = Y_std * np.sqrt(sums[0] / sums[2])
+            out["log_density"] = float(sums[1].sum()) / cnt - (np.log(Y_std) if gaussian else 0.0)
+        if return_rows:
+            out["rows"] = rows.cpu().numpy()
+        return out
+
+    def _noise(self, what, level):
+        if level not in ("f", "y"):
+            raise ValueError(f"level must be \"f\" or \"y\", not {level!r}")
+        if level == "y" and self.likelihood.needs_broadcasting:
+            raise NotImplementedError(f"{what}: the predictive y of {type(self.likelihood.likelihood).__name__} is not a mixture of "
+                                      "Gaussians; only level=\"f\" (the latent function) is covered")
+        return float(self.likelihood.likelihood.variance.value) if level == "y" else 0.0
+
+    def predict_quantiles(self, Xnew, S, probs=(0.025, 0.5, 0.975), level="y", run=None, Y_std=1.0, Y_mean=0.0):
+        """Quantiles of the predictive mixture of the T S Gaussians of `run` (dsdgp_mixture_quantiles): (N*, D, P), as
+        DGP_Base.predict_quantiles"""
+        noise = self._noise("predict_quantiles", level)
+        S, _, Y_std, probs = self._calibration_args("predict_quantiles", Xnew, S, probs, 1, Y_std, None, False)
+        ctx = self._context()
+        N, D, P = Xnew.shape[0], self.layers[-1].num_outputs, probs.size
+        q = ctx.empty(N, D, P)
+        self._score_batches(Xnew, None, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_mixture_quantiles(
+            ctx.handle, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), noise, b - a, comps, D,
+            probs.ctypes.data_as(_lib.c_double_p), P, C.c_void_p(q[a:b].data_ptr()))))
+        return float(Y_mean) + Y_std * q.cpu().numpy()
+
+    def calibration(self, Xs, Ys, S, probs=(0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975), run=None, Y_std=1.0, return_rows=False):
+        """Calibration scores of held-out targets under the mixture of the T S Gaussians of `run` (dsdgp_mixture_calibration; Gaussian
+        likelihood): the dict of DGP_Base.calibration"""
+        from .dgp import calibration_scores
+        noise = self._noise("calibration", "y")
+        S, _, Y_std, probs = self._calibration_args("calibration", Xs, S, probs, 1, Y_std, None, True, Y=Ys)
+        ctx = self._context()
+        N, D, P = Xs.shape[0], self.layers[-1].num_outputs, probs.size
+        acc = ctx.empty(2 + P, D)
+        rows = ctx.empty(N, D, 2) if return_rows else None
+        self._score_batches(Xs, Ys, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_mixture_calibration(
+            ctx.handle, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), noise, C.c_void_p(Yb.data_ptr()), b - a, comps, D,
+            probs.ctypes.data_as(_lib.c_double_p), P, C.c_void_p(rows[a:b].data_ptr() if return_rows else 0), C.c_void_p(acc.data_ptr()),
+            int(a > 0))))
+        out = calibration_scores(acc.cpu().numpy(), probs, Y_std)
+        out["n"] = N
+        if return_rows:
+            out["rows"] = rows.cpu().numpy()
+        return out
+
+    def classification_report(self, Xs, Ys, S, bins=10, run=None, return_rows=False):
+        """The classification report of the mixture class probabilities over the T S components of `run`
+        (dsdgp_mixture_classification; MultiClass or Bernoulli): the dict of DGP_Base.classification_report"""
+        from .dgp import classification_scores
+        kind, Cn, ND, S, bins, _ = self._classification_args(Xs, Ys, S, bins, 1, None)
+        ctx = self._context()
+        N, D = Xs.shape[0], self.layers[-1].num_outputs
+        acc = ctx.empty(4 + 3 * bins + Cn + Cn * Cn, ND)
+        probs = ctx.empty(N, D) if return_rows else None
+        rows = ctx.empty(N, ND, 4) if return_rows else None
+        self._score_batches(Xs, Ys, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_mixture_classification(
+            ctx.handle, kind, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(Yb.data_ptr()), b - a, comps, D, bins,
+            C.c_void_p(probs[a:b].data_ptr() if return_rows else 0), C.c_void_p(rows[a:b].data_ptr() if return_rows else 0),
+            C.c_void_p(acc.data_ptr()), int(a > 0))))
+        out = classification_scores(acc.cpu().numpy(), bins, Cn)
+        out["n"] = N
+        if return_rows:
+            out["probs"], out["rows"] = probs.cpu().numpy(), rows.cpu().numpy()
+        return out
+
+
+def split_kernel_ard(kern):
+    """whether the stationary part of kern has one lengthscale per input"""
+    from .gpflow_compat import split_kernel
+    return bool(split_kernel(kern)[0].ARD)

@@ -353,3 +353,112 @@ class HMC:
         accepted = np.array(accepted, dtype=bool)
         return dict(samples={n: np.stack(v) for n, v in kept.items()}, logprobs=np.array(logps), accepted=accepted,
                     accept_rate=float(np.mean(accepted)))
+
+
+class SGHMC:
+    """Stochastic-gradient Hamiltonian Monte Carlo (Chen, Fox and Guestrin 2014, eq. 15, with the gradient-noise estimate at 0) on the
+    log density of a `model_zoo.DGP_SGPMC`: per iteration ONE minibatch gradient (`compute_log_density_gradients`) and ONE
+    dsdgp_sghmc_step over the flat vector of the variables,
+        theta += v;   v = (1 - friction) v + learning_rate g + sqrt(2 friction learning_rate) xi,
+    g the gradient of the log density at the position the iteration started from, xi = dsdgp_randn(seed, stream = iteration): a run
+    replays from its seed (together with the model's minibatch and draw sequences; `model.fix_draws` pins the latter).  No
+    accept / reject step: the sampler is biased at the order of the learning rate.
+    The variables are `var_list`, by default every layer's `q_mu`; any Parameter among the pairs of `compute_log_density_gradients`
+    may be added.  A positive parameter moves in unconstrained space, theta = softplus(x) + 1e-6, with a FLAT density there, exactly as
+    `training.HMC` documents: only the q_mu have priors, no Jacobian term is added.  Position and momentum are device tensors; the
+    model's Parameters are assigned at every position, which is how the gradient sees it.  A CholeskyError at a new position restores
+    the previous position and momentum and draws the next minibatch."""
+
+    def __init__(self, learning_rate=1e-4, friction=0.05):
+        self.eta, self.alpha = float(learning_rate), float(friction)
+        if not self.eta > 0.0 or not 0.0 <= self.alpha <= 1.0:
+            raise ValueError("SGHMC: learning_rate > 0 and 0 <= friction <= 1")
+
+    @staticmethod
+    def _check(model):
+        from .model_zoo import DGP_SGPMC
+        if not isinstance(model, DGP_SGPMC):
+            raise NotImplementedError(f"SGHMC samples a DGP_SGPMC; {type(model).__name__} is trained by its own optimisers "
+                                      "(a DGP_Heinonen is sampled by HMC)")
+
+    @staticmethod
+    def _names(model, var_list):
+        qs = {id(layer.q_mu): l for l, layer in enumerate(model.layers)}
+        return ["q_mu%d" % qs[id(p)] if id(p) in qs else f"var{i}" for i, p in enumerate(var_list)]
+
+    @staticmethod
+    def _split(var_list, flat):
+        out, at = [], 0
+        for p in var_list:
+            k = int(np.prod(p.shape))
+            out.append(flat[at:at + k].reshape(p.shape))
+            at += k
+        return out
+
+    @classmethod
+    def _assign(cls, var_list, theta):
+        from .gpflow_compat import positive_forward
+        for p, x in zip(var_list, cls._split(var_list, theta.cpu().numpy())):
+            p.assign(positive_forward(x) if p.transform == "positive" else x)
+
+    @staticmethod
+    def _gradient(model, var_list, ctx):
+        """(log density, its gradient in the unconstrained variables as one flat device tensor) at the model's Parameters, on the next
+        minibatch"""
+        from .gpflow_compat import positive_slope
+        logp, pairs = model.compute_log_density_gradients()
+        grads = {id(p): g for p, g in pairs}
+        out = []
+        for p in var_list:
+            if id(p) not in grads:
+                raise ValueError("SGHMC: a Parameter of var_list has no gradient of the model's log density")
+            g = np.asarray(grads[id(p)], dtype=np.float64).reshape(p.shape)
+            out.append((g * positive_slope(p.value) if p.transform == "positive" else g).ravel())
+        return logp, ctx.to_device(np.concatenate(out))
+
+    def step(self, ctx, theta, v, g, xi):
+        """one dsdgp_sghmc_step on flat device tensors, in place"""
+        import ctypes as C
+        from . import _lib
+        p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
+        _lib.check(ctx.lib.dsdgp_sghmc_step(ctx.handle, theta.numel(), p(theta), p(v), p(g), p(xi), self.alpha, self.eta))
+
+    def sample(self, model, num_samples, thin=1, burn=0, var_list=None, seed=0):
+        """-> dict(samples={name: (num_samples, *shape)} of the CONSTRAINED values — names "q_mu<layer>", then "var<i>" by position in
+        var_list for any other Parameter —, logprobs (num_samples,): the minibatch log density at each kept state, names, variables (the
+        Parameters, in the order of names: what DGP_SGPMC's scoring methods take as `run`)).  burn + num_samples thin iterations;
+        every thin-th state after the burn-in is kept.  The model is left at the last state."""
+        import ctypes as C
+        from . import _lib
+        from .gpflow_compat import positive_backward, positive_forward
+        self._check(model)
+        if int(num_samples) < 1 or int(thin) < 1 or int(burn) < 0:
+            raise ValueError("SGHMC.sample: num_samples, thin >= 1, burn >= 0")
+        var_list = [layer.q_mu for layer in model.layers] if var_list is None else list(var_list)
+        if not var_list:
+            raise ValueError("SGHMC: var_list is empty")
+        names = self._names(model, var_list)
+        ctx = model._context()
+        theta = ctx.to_device(np.concatenate([np.ravel(positive_backward(p.value) if p.transform == "positive" else p.value)
+                                              for p in var_list]))
+        v = ctx.torch.zeros_like(theta)
+        xi = ctx.empty(theta.numel())
+        logp, g = self._gradient(model, var_list, ctx)
+        kept, logps = {n: [] for n in names}, []
+        for it in range(int(burn) + int(num_samples) * int(thin)):
+            _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(int(seed)), C.c_uint64(it), theta.numel(), C.c_void_p(xi.data_ptr())))
+            theta0, v0 = theta.clone(), v.clone()
+            self.step(ctx, theta, v, g, xi)
+            self._assign(var_list, theta)
+            try:
+                logp, g = self._gradient(model, var_list, ctx)
+            except _lib.CholeskyError:
+                theta, v = theta0, v0                       # the previous state, and the gradient there on the next minibatch
+                self._assign(var_list, theta)
+                logp, g = self._gradient(model, var_list, ctx)
+            if it >= int(burn) and (it - int(burn) + 1) % int(thin) == 0:
+                for n, p, x in zip(names, var_list, self._split(var_list, theta.cpu().numpy())):
+                    kept[n].append(positive_forward(x) if p.transform == "positive" else x.copy())
+                logps.append(logp)
+        self._assign(var_list, theta)
+        return dict(samples={n: np.stack(x) for n, x in kept.items()}, logprobs=np.array(logps), names=names, variables=var_list)

@@ -680,6 +680,68 @@ int dsdgp_sparse_conditional_grad(dsdgp_ctx* ctx, const dsdgp_kernel* kern, cons
                                   void* scratch, int64_t scratch_bytes, double* d_q_mu, double* d_Z, double* d_X, double* d_kern,
                                   int* info);
 
+/* A stack of sparse sampled layers: DGP_Base(X, Y, likelihood, [SGPMC_Layer, ...], minibatch_size, num_samples) of the reference
+ * (dgp.py:42-98 over layers.py:249-260) — dsdgp_sparse_conditional at every depth, a draw between the layers (sample_from_conditional,
+ * layers.py:76-119; utils.py:40-41), the last layer not sampled (dgp.py:78-90) — its log density and the reverse pass tf.gradients builds
+ * through it (csrc/sgpmc_stack.hip).  Rows r = s n + i, R = S n, as dsdgp_model_propagate.  Layer l, with input Xin (R x D_l; layer 0: X
+ * repeated S times), D_l = kern.input_dim, p = input_prop_dim:
+ *   Fmean = mean + m(Xin),  m = Zero, Identity (D_l = DO) or a FIXED Linear Xin A + b (mean_A (D_l x DO), mean_b (DO) or NULL: device);
+ *   F = [Xin[:, :p] | Fmean + z sqrt(var + jitter)] (R x (p + DO)) = the next layer's input, so D_{l+1} = p + DO;
+ *   the last layer: input_prop_dim = 0, DO = lik_width (MultiClass: the class count), no draw; its F is its Fmean.
+ * Z (M x D_l), q_mu (M x DO): device.  lik_kind = any DSDGP_LIK_*, lik_p0 / lik_p1 as for dsdgp_eval_mixture. */
+typedef struct {
+  dsdgp_kernel kern;
+  const double* Z;
+  const double* q_mu;
+  const double* mean_A;
+  const double* mean_b;
+  int32_t M, DO, white, mean_kind, input_prop_dim, reserved;
+} dsdgp_stack_layer;
+typedef struct {
+  int32_t L, lik_kind, lik_width, reserved;
+  double lik_p0, lik_p1, jitter;
+  dsdgp_stack_layer layers[DSDGP_MAX_LAYERS];
+} dsdgp_stack_desc;
+int dsdgp_sizeof_stack_desc(void);
+/* SCRATCH: everything that lives from one composed call to the next is in a block the CALLER holds (device, 256-byte aligned) of at least
+ * dsdgp_stack_scratch_bytes(desc, n, S, reverse) bytes (reverse != 0: for dsdgp_stack_logdensity with a gradient); its carve-up and every
+ * summation order follow from the shapes alone (csrc/sgpmc_stack_plan.hpp): no floating-point atomics, the same call gives the same bits.
+ * dsdgp_stack_propagate: DGP_Base.propagate, full_cov = False (dgp.py:61-76).  zs: host array of L device pointers (R x DO_l each), or NULL
+ *   / NULL entries: layer l's draws are dsdgp_randn(seed, stream = l, R DO_l); zs[L - 1] is never read.  F_out / mean_out / var_out: host
+ *   arrays of L device pointers — F (R x (p + DO_l)), Fmean (R x DO_l), var (R: ONE column) — or NULL / NULL entries.
+ * dsdgp_stack_logdensity: DGP_Base._build_likelihood (dgp.py:92-98) without KL terms plus the priors of layers.py:257.  Y (n x lik_width;
+ *   MultiClass: n x 1 labels).  out (device, 4 doubles): [log density, data_scale / S * sum E_q log p(y | f), sum_l (-1/2 sum q_mu_l^2 -
+ *   1/2 M_l DO_l log 2 pi), potrf info = 0].  grad (device, or NULL): OVERWRITTEN with the gradient of out[0] in the CONSTRAINED parameters,
+ *   flat: per layer d_Z (M x D_l), d_q_mu (M x DO), d_kern (2 + (ard ? D_l : 1): variance, lengthscales, the diagonal add, as
+ *   dsdgp_sparse_conditional_grad), then ONE entry for the likelihood's parameter (+0 where it has none).  The reverse pass repeats each
+ *   layer's factorisation and solves (dsdgp_sparse_conditional_grad does).
+ * info (host, may be NULL): the Cholesky status of the first layer whose Ku is not positive definite; every layer is factorised before
+ * anything else runs, so a failure in ANY layer returns DSDGP_ERR_NOT_SPD and writes no output.  M <= 2048; the reverse inherits
+ * input_dim <= 32 for every layer (DSDGP_ERR_UNSUPPORTED, nothing launched); DSDGP_ERR_UNSUPPORTED for more than 8 GB of scratch;
+ * DSDGP_ERR_BAD_ARG for shapes that do not chain, a NULL input or a scratch block that is too small. */
+int dsdgp_stack_scratch_bytes(const dsdgp_stack_desc* desc, int64_t n, int32_t S, int32_t reverse, int64_t* bytes);
+int dsdgp_stack_propagate(dsdgp_ctx* ctx, const dsdgp_stack_desc* desc, const double* X, int64_t n, int32_t S, const double* const* zs,
+                          uint64_t seed, void* scratch, int64_t scratch_bytes, double* const* F_out, double* const* mean_out,
+                          double* const* var_out, int* info);
+int dsdgp_stack_logdensity(dsdgp_ctx* ctx, const dsdgp_stack_desc* desc, const double* X, const double* Y, int64_t n, int32_t S,
+                           const double* const* zs, uint64_t seed, double data_scale, void* scratch, int64_t scratch_bytes, double* out,
+                           double* grad, int* info);
+/* The hop between two layers of the stack and its reverse as calls of their own (sample_from_conditional, layers.py:76-119, and
+ * utils.py:40-41; the launches the composed calls make, on the caller's arrays).  cm (R x DO), var (R), Xin (R x D_in), z (R x DO):
+ *   Fmean (R x DO, or NULL) = cm + m(Xin), m by mean_kind: Zero, Identity (D_in = DO), Linear lin + b with lin = Xin A (R x DO) formed
+ *   by the caller (dsdgp_gemm) and b (DO) or NULL;   F (R x (p + DO)) = [Xin[:, :p] | Fmean + z sqrt(var + jitter)].
+ * Reverse, from dF (R x (p + DO)):  gm (R x DO) = dF[:, p:],  gv (R) = sum_o dF[r, p + o] z[r, o] / (2 sqrt(var_r + jitter)), ascending o
+ * (a row with var + jitter = 0 has no finite gv). */
+int dsdgp_stack_hop(dsdgp_ctx* ctx, const double* cm, const double* var, const double* Xin, int64_t R, int32_t D_in, int32_t mean_kind,
+                    const double* lin, const double* b, int32_t p, int32_t DO, const double* z, double jitter, double* Fmean, double* F);
+int dsdgp_stack_hop_bwd(dsdgp_ctx* ctx, const double* dF, int64_t R, int32_t p, int32_t DO, const double* z, const double* var,
+                        double jitter, double* gm, double* gv);
+/* One step of stochastic-gradient HMC (Chen, Fox and Guestrin 2014, eq. 15, noise estimate 0) over a flat vector, one launch; no
+ * reference counterpart (the reference samples with gpflow.train.HMC, model_zoo.py:60-88):
+ *   theta += v;  then  v = (1 - alpha) v + eta g + sqrt(2 alpha eta) xi,   g the gradient of the log density, xi N(0, 1) draws.
+ * alpha = 0: plain momentum, xi is not read (and may be NULL).  DSDGP_ERR_BAD_ARG, nothing launched: alpha outside [0, 1], eta <= 0. */
+int dsdgp_sghmc_step(dsdgp_ctx* ctx, int64_t count, double* theta, double* v, const double* g, const double* xi, double alpha, double eta);
+
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
 
