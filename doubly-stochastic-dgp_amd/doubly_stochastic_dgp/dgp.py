@@ -6,8 +6,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .gpflow_compat import Gaussian, Parameterized, Zero
+from .engine import Context
+from .gpflow_compat import Gaussian, MultiClass, Parameterized, Zero
 from .layer_initializations import greedy_inducing, init_layers_linear, kmeans_inducing
+from .layers import prepend_input_prop, propagate_layers
 from .distributed import shard_terms
 from .utils import BroadcastingLikelihood
 
@@ -90,11 +92,24 @@ class DGP_Base(Parameterized):
             object.__setattr__(self, "_eng", eng)
         return self._eng
 
+    def _context(self):
+        return Context.get()
+
     def _device_data(self):
         if self._dev_data is None:
-            ctx = self.engine().ctx
+            ctx = self._context()
             object.__setattr__(self, "_dev_data", (ctx.to_device(self.X_data), ctx.to_device(self.Y_data)))
         return self._dev_data
+
+    def _randn(self, shape, seed, stream):
+        """dsdgp_randn(seed, stream) as a numpy array: where a model without an engine over all its layers draws for
+        Layer.sample_from_conditional without z"""
+        ctx = self._context()
+        n = int(np.prod(shape))
+        out = ctx.empty(n)
+        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(seed), C.c_uint64(stream), n, C.c_void_p(out.data_ptr())))
+        ctx.sync()
+        return out.cpu().numpy().reshape(shape)
 
     def _next_seed(self):
         self._seed += 1
@@ -113,7 +128,7 @@ class DGP_Base(Parameterized):
         when a minibatch straddles an epoch boundary — 2 of every 7 steps at 7372 / 1000) stalled the host behind the stream and the
         GPU behind the host: ~50 us on each such step."""
         Xd, _ = self._device_data()
-        ctx = self.engine().ctx
+        ctx = self._context()
         mb = self._minibatch
         if getattr(self, "_idx_src", None) is not mb or self._idx_pos >= self._idx_cnt:
             k = max(1, min(512, (1 << 18) // max(1, mb.batch_size)))
@@ -137,7 +152,7 @@ class DGP_Base(Parameterized):
         Xd, Yd = self._device_data()
         if self._minibatch is None:
             return Xd, Yd
-        ctx = self.engine().ctx
+        ctx = self._context()
         idx, off, n = self._next_index_span()
         Xb, Yb = ctx.empty(n, Xd.shape[1]), ctx.empty(n, Yd.shape[1])
         _lib.check(ctx.lib.dsdgp_gather_rows2(ctx.handle, C.c_void_p(Xd.data_ptr()), Xd.shape[1], C.c_void_p(Xb.data_ptr()),
@@ -154,28 +169,14 @@ class DGP_Base(Parameterized):
     def propagate(self, X, full_cov=False, S=1, zs=None):
         eng = self.engine()
         if full_cov:
-            # plotting path (dgp.py:104-114): the layer loop of dgp.py:69-74 with (S,N,N,D) covariances; every piece of
-            # arithmetic is a libdsdgp call (layers.py / utils.py mirrors), the loop itself stays on the host
-            F = np.tile(np.asarray(X, dtype=np.float64)[None], [int(S), 1, 1])
-            Fs, Fmeans, Fvars = [], [], []
-            zs = zs or [None] * len(self.layers)
-            for layer, z in zip(self.layers, zs):
-                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=True)
-                Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
-            return Fs, Fmeans, Fvars
+            # plotting path (dgp.py:104-114): the layer loop of dgp.py:69-74 with (S,N,N,D) covariances, on the host
+            return propagate_layers(self.layers, np.tile(np.asarray(X, dtype=np.float64)[None], [int(S), 1, 1]), zs, full_cov=True)
         Fs, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._draw_seed())
         eng.ctx.sync()
         Fs, Fmeans, Fvars = self._np(Fs), self._np(Fmeans), self._np(Fvars)
         if any(layer.input_prop_dim for layer in self.layers):
-            # the device hands the concatenated [X_prop | F] to the next layer itself; the returned lists get the same
-            # copies prepended here (layers.py:105-117)
-            from .layers import concat_input_prop
             Xh = X.cpu().numpy() if hasattr(X, "data_ptr") else np.asarray(X, dtype=np.float64)
-            Fin = np.tile(Xh[None], [int(S), 1, 1])
-            for l, layer in enumerate(self.layers):
-                if layer.input_prop_dim:
-                    Fs[l], Fmeans[l], Fvars[l] = concat_input_prop(Fin, layer.input_prop_dim, Fs[l], Fmeans[l], Fvars[l])
-                Fin = Fs[l]
+            prepend_input_prop(np.tile(Xh[None], [int(S), 1, 1]), self.layers, Fs, Fmeans, Fvars)
         return Fs, Fmeans, Fvars
 
     # dgp.py:78-81
@@ -288,6 +289,58 @@ class DGP_Base(Parameterized):
         Fmean, Fvar = self._build_predict(Xnew, full_cov=False, S=num_samples)
         return self.likelihood.predict_density_logmeanexp(Fmean, Fvar, np.asarray(Ynew, dtype=np.float64))
 
+    # ------------------------------------------------------------------ held-out scoring: one front end for every model
+    # Each of evaluate, predict_quantiles, calibration and classification_report has ONE body (_evaluate, ...), shared with
+    # model_zoo.DGP_SGPMC: refusals before any device is touched, uploads, the accumulator and `rows`, the batch loop, one
+    # synchronisation, the host finish.  A model supplies _score_context() and _score_batches(): how rows become batches and what one
+    # batch launches for a reduction.  `how` is what the model's _score_batches cuts by: batch_size and zs here, run there.
+    MAX_PROBS = 16
+    MAX_BINS = 32
+
+    def _score_context(self):
+        """the context a scoring call works in, asked for once its arguments have passed: the engine models build their engine here"""
+        return self.engine().ctx
+
+    @staticmethod
+    def _zs_on_device(ctx, zs):
+        if zs is None:
+            return None
+        return [z if z is None or hasattr(z, "data_ptr") else ctx.to_device(np.asarray(z, dtype=np.float64)) for z in zs]
+
+    def _score_batches(self, ctx, Xd, Yd, S, batch_size=1000, zs=None):
+        """(a, b, launch) over the row batches [a, b) of Xd in order, then one synchronisation.  launch(what, ...) is the batch's library
+        call Engine.<what>_batch on its rows with zs = the batch's rows of every draw that is not broadcast over rows and seed = one
+        `_draw_seed()` per batch, in batch order.  What the calls return (the arrays their asynchronous launches read) is kept alive
+        until the synchronisation."""
+        eng, zs, keep = self.engine(), self._zs_on_device(ctx, zs), []
+        for a in range(0, Xd.shape[0], batch_size):
+            b = min(a + batch_size, Xd.shape[0])
+            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
+            seed, data = self._draw_seed(), (Xd[a:b],) if Yd is None else (Xd[a:b], Yd[a:b])
+            yield a, b, lambda what, *args, **kw: keep.append(getattr(eng, what + "_batch")(*data, S, *args, zs=zb, seed=seed, **kw))
+        ctx.sync()
+
+    @staticmethod
+    def _batch_args(num_samples, batch_size):
+        S, batch_size = int(num_samples), int(batch_size)
+        if batch_size < 1 or S < 1:
+            raise ValueError("batch_size and num_samples must be positive")
+        return S, batch_size
+
+    def _zs_args(self, zs):
+        if zs is not None:
+            if len(zs) != len(self.layers):
+                raise ValueError("zs needs one entry (or None) per layer")
+            if any(z is not None and len(_shape(z)) != 3 for z in zs):
+                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
+
+    def _row_args(self, X, Y, width, hint, zs):
+        if len(_shape(X)) != 2 or _shape(X)[0] < 1:
+            raise ValueError("X must be a non-empty (N, D_in) array")
+        if Y is not None and _shape(Y) != (_shape(X)[0], width):
+            raise ValueError(f"Ys has shape {_shape(Y)}, expected {(_shape(X)[0], width)}{hint}")
+        self._zs_args(zs)
+
     def evaluate(self, Xs, Ys, num_samples, batch_size=1000, Y_std=1.0, zs=None, return_rows=False):
         """Held-out scores as demos/run_regression.py:108-123 computes them, without leaving the device: over row batches of
         `batch_size` (a ragged last one allowed) the forward pass and the reduction over the `num_samples` mixture components add into
@@ -297,59 +350,36 @@ class DGP_Base(Parameterized):
         (MultiClass: `error_rate` of argmax_k of the mixture class probabilities instead), `log_density` = the mean over rows and
         outputs of logsumexp_S log p(y | .) - log S (dgp.py:121-126), `n`, and with return_rows the (N*, D, 3) array `rows` of
         [mixture mean, mixture variance, log density]."""
-        from .gpflow_compat import MultiClass
-        eng = self.engine()
-        ctx = eng.ctx
-        torch = ctx.torch
-        S = int(num_samples)
-        batch_size = int(batch_size)
-        if batch_size < 1 or S < 1:
-            raise ValueError("batch_size and num_samples must be positive")
+        return self._evaluate(Xs, Ys, num_samples, Y_std, return_rows, batch_size=batch_size, zs=zs)
+
+    def _evaluate(self, Xs, Ys, num_samples, Y_std, return_rows, **how):
+        S, how["batch_size"] = self._batch_args(num_samples, how.get("batch_size", 1))
         gaussian = not self.likelihood.needs_broadcasting
         Y_std = float(Y_std)
         if not Y_std > 0.0 or (not gaussian and Y_std != 1.0):
             raise ValueError("Y_std rescales a Gaussian density only (and must be positive)")
         if not hasattr(Ys, "data_ptr"):
             self.likelihood.check_targets(Ys)
-        Xd = Xs.contiguous() if hasattr(Xs, "data_ptr") else ctx.to_device(Xs)
-        Yd = Ys.contiguous() if hasattr(Ys, "data_ptr") else ctx.to_device(Ys)
-        N = Xd.shape[0]
-        if N < 1 or Yd.shape[0] != N:
-            raise ValueError(f"Xs has {N} rows, Ys {Yd.shape[0]}")
+        N = _shape(Xs)[0]
+        if N < 1 or _shape(Ys)[0] != N:
+            raise ValueError(f"Xs has {N} rows, Ys {_shape(Ys)[0]}")
+        self._zs_args(how.get("zs"))
+        ctx = self._score_context()
+        Xd, Yd = ctx.as_device(Xs), ctx.as_device(Ys)
         D = self.layers[-1].num_outputs
-        if zs is not None:
-            if len(zs) != len(self.layers):
-                raise ValueError("zs needs one entry (or None) per layer")
-            zs = self._device_zs(ctx, zs)
-            if any(z is not None and z.dim() != 3 for z in zs):
-                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
         acc = ctx.empty(3, D)
         rows = ctx.empty(N, D, 3) if return_rows else None
-        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.evaluate_batch(
-            Xd[a:b], Yd[a:b], S, acc, a > 0, zs=zb, seed=seed, rows=rows[a:b] if return_rows else None))
-        sums = acc.cpu().numpy()
-        cnt = float(sums[2].sum()) if not isinstance(self.likelihood.likelihood, MultiClass) else float(sums[2, 0])
-        out = {"n": N}
-        if isinstance(self.likelihood.likelihood, MultiClass):
-            out["error_rate"] = float(sums[0, 0]) / cnt
-            out["log_density"] = float(sums[1, 0]) / cnt
-        else:
-            out["rmse"] = Y_std * float(np.sqrt(sums[0].sum() / cnt))
-            out["rmse_per_output"] = Y_std * np.sqrt(sums[0] / sums[2])
-            # the model lives in standardised units y = y_orig / Y_std; the density of y_orig is that of y divided by Y_std,
-            # N(y c | m c, v c^2) = N(y | m, v) / c, component by component, hence also for the mixture: log p(y_orig) = l - log Y_std
-            # (run_regression.py:122 scales targets, means and standard deviations by Y_std before norm.logpdf)
-            out["log_density"] = float(sums[1].sum()) / cnt - (np.log(Y_std) if gaussian else 0.0)
+        for a, b, launch in self._score_batches(ctx, Xd, Yd, S, **how):
+            launch("evaluate", acc, a > 0, rows=rows[a:b] if return_rows else None)
+        out = {"n": N, **evaluation_scores(acc.cpu().numpy(), isinstance(self.likelihood.likelihood, MultiClass), gaussian, Y_std)}
         if return_rows:
             out["rows"] = rows.cpu().numpy()
         return out
 
     # ------------------------------------------------------------------ calibration of the predictive mixture
-    MAX_PROBS = 16
-
     def _calibration_args(self, what, X, num_samples, probs, batch_size, Y_std, zs, needs_gaussian, Y=None):
         """Everything predict_quantiles / calibration can refuse without a device: (S, batch_size, Y_std, probs as a float64 array).
-        Called before self.engine() is touched, so a machine without a GPU reports the bad argument and not the missing device."""
+        Called before any device is touched, so a machine without a GPU reports the bad argument and not the missing device."""
         if needs_gaussian and self.likelihood.needs_broadcasting:
             raise NotImplementedError(f"{what}: the predictive y of {type(self.likelihood.likelihood).__name__} is not a mixture of "
                                       "Gaussians; only level=\"f\" (the latent function) is covered")
@@ -358,42 +388,12 @@ class DGP_Base(Parameterized):
             raise ValueError(f"probs must hold 1 .. {self.MAX_PROBS} probabilities")
         if not np.all((probs > 0.0) & (probs < 1.0)):
             raise ValueError("every probability must lie inside (0, 1)")
-        S, batch_size = int(num_samples), int(batch_size)
-        if batch_size < 1 or S < 1:
-            raise ValueError("batch_size and num_samples must be positive")
+        S, batch_size = self._batch_args(num_samples, batch_size)
         Y_std = float(Y_std)
         if not (Y_std > 0.0 and np.isfinite(Y_std)):
             raise ValueError("Y_std must be positive")
-        shape = lambda a: tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-        if len(shape(X)) != 2 or shape(X)[0] < 1:
-            raise ValueError("X must be a non-empty (N, D_in) array")
-        if Y is not None:
-            want = (shape(X)[0], self.layers[-1].num_outputs)
-            if shape(Y) != want:
-                raise ValueError(f"Ys has shape {shape(Y)}, expected {want} (rows of Xs x outputs of the last layer)")
-        if zs is not None:
-            if len(zs) != len(self.layers):
-                raise ValueError("zs needs one entry (or None) per layer")
-            if any(z is not None and len(shape(z)) != 3 for z in zs):
-                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
+        self._row_args(X, Y, self.layers[-1].num_outputs, " (rows of Xs x outputs of the last layer)", zs)
         return S, batch_size, Y_std, np.ascontiguousarray(probs)
-
-    @staticmethod
-    def _device_zs(ctx, zs):
-        if zs is None:
-            return None
-        return [z if z is None or hasattr(z, "data_ptr") else ctx.to_device(np.asarray(z, dtype=np.float64)) for z in zs]
-
-    def _over_row_batches(self, ctx, N, batch_size, zs, call):
-        """call(a, b, zb, seed) on the row batches [a, b) of N rows in order, then one synchronisation: zb = the batch's rows of every
-        draw of the device list `zs` that is not broadcast over rows, seed = one `_draw_seed()` per batch.  What the calls return (the
-        arrays their asynchronous launches read) is kept alive until the synchronisation."""
-        keep = []
-        for a in range(0, N, batch_size):
-            b = min(a + batch_size, N)
-            zb = None if zs is None else [z if z is None or z.shape[1] == 1 else z[:, a:b].contiguous() for z in zs]
-            keep.append(call(a, b, zb, self._draw_seed()))
-        ctx.sync()
 
     def predict_quantiles(self, Xnew, num_samples, probs=(0.025, 0.5, 0.975), level="y", batch_size=1000, Y_std=1.0, Y_mean=0.0,
                           zs=None):
@@ -403,18 +403,18 @@ class DGP_Base(Parameterized):
         observations (Gaussian likelihood only; the noise variance is added), "f": the latent function of any likelihood.  Xnew: numpy
         or a device tensor, in row batches of `batch_size` (a ragged last one allowed).  zs as in `evaluate`; else one `_draw_seed()`
         per batch, in batch order."""
+        return self._predict_quantiles(Xnew, num_samples, probs, level, Y_std, Y_mean, batch_size=batch_size, zs=zs)
+
+    def _predict_quantiles(self, Xnew, num_samples, probs, level, Y_std, Y_mean, **how):
         if level not in ("f", "y"):
             raise ValueError(f"level must be \"f\" or \"y\", not {level!r}")
-        S, batch_size, Y_std, probs = self._calibration_args("predict_quantiles", Xnew, num_samples, probs, batch_size, Y_std, zs,
-                                                             level == "y")
-        eng = self.engine()
-        ctx = eng.ctx
-        Xd = Xnew.contiguous() if hasattr(Xnew, "data_ptr") else ctx.to_device(Xnew)
-        zs = self._device_zs(ctx, zs)
-        N, D, P = Xd.shape[0], self.layers[-1].num_outputs, probs.size
-        q = ctx.empty(N, D, P)
-        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.quantiles_batch(
-            Xd[a:b], S, probs, q[a:b], level=1 if level == "y" else 0, zs=zb, seed=seed))
+        S, how["batch_size"], Y_std, probs = self._calibration_args("predict_quantiles", Xnew, num_samples, probs, how.get("batch_size", 1),
+                                                                    Y_std, how.get("zs"), level == "y")
+        ctx = self._score_context()
+        Xd = ctx.as_device(Xnew)
+        q = ctx.empty(Xd.shape[0], self.layers[-1].num_outputs, probs.size)
+        for a, b, launch in self._score_batches(ctx, Xd, None, S, **how):
+            launch("quantiles", probs, q[a:b], level=1 if level == "y" else 0)
         return float(Y_mean) + Y_std * q.cpu().numpy()
 
     def calibration(self, Xs, Ys, num_samples, probs=(0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975), batch_size=1000, Y_std=1.0, zs=None,
@@ -425,17 +425,18 @@ class DGP_Base(Parameterized):
         probability integral transform u = F(y) is <= probs[k] (a calibrated model gives probs[k]); `coverage`: for every pair p, 1 - p
         both in probs, {1 - 2p: fraction of targets with p < u <= 1 - p}, the coverage of the central interval, over rows and outputs;
         `n`; with return_rows the (N*, D, 2) array `rows` of [u, CRPS] in model units."""
-        S, batch_size, Y_std, probs = self._calibration_args("calibration", Xs, num_samples, probs, batch_size, Y_std, zs, True, Y=Ys)
-        eng = self.engine()
-        ctx = eng.ctx
-        Xd = Xs.contiguous() if hasattr(Xs, "data_ptr") else ctx.to_device(Xs)
-        Yd = Ys.contiguous() if hasattr(Ys, "data_ptr") else ctx.to_device(Ys)
-        zs = self._device_zs(ctx, zs)
-        N, D, P = Xd.shape[0], self.layers[-1].num_outputs, probs.size
-        acc = ctx.empty(2 + P, D)
+        return self._calibration(Xs, Ys, num_samples, probs, Y_std, return_rows, batch_size=batch_size, zs=zs)
+
+    def _calibration(self, Xs, Ys, num_samples, probs, Y_std, return_rows, **how):
+        S, how["batch_size"], Y_std, probs = self._calibration_args("calibration", Xs, num_samples, probs, how.get("batch_size", 1), Y_std,
+                                                                    how.get("zs"), True, Y=Ys)
+        ctx = self._score_context()
+        Xd, Yd = ctx.as_device(Xs), ctx.as_device(Ys)
+        N, D = Xd.shape[0], self.layers[-1].num_outputs
+        acc = ctx.empty(2 + probs.size, D)
         rows = ctx.empty(N, D, 2) if return_rows else None
-        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.calibration_batch(
-            Xd[a:b], Yd[a:b], S, probs, acc, a > 0, zs=zb, seed=seed, rows=rows[a:b] if return_rows else None))
+        for a, b, launch in self._score_batches(ctx, Xd, Yd, S, **how):
+            launch("calibration", probs, acc, a > 0, rows=rows[a:b] if return_rows else None)
         out = calibration_scores(acc.cpu().numpy(), probs, Y_std)
         out["n"] = N
         if return_rows:
@@ -443,30 +444,16 @@ class DGP_Base(Parameterized):
         return out
 
     # ------------------------------------------------------------------ classification report (MultiClass / Bernoulli)
-    MAX_BINS = 32
-
     def _classification_args(self, X, Y, num_samples, bins, batch_size, zs):
-        """Everything classification_report can refuse without a device -> (kind, C, ND, S, bins, batch_size); called before
-        self.engine() is touched."""
+        """Everything classification_report can refuse without a device -> (kind, C, ND, S, bins, batch_size); called before any
+        device is touched."""
         kind, Cn = self.likelihood.classification_args("classification_report")
         bins = int(bins)
         if not 1 <= bins <= self.MAX_BINS:
             raise ValueError(f"bins must lie in 1 .. {self.MAX_BINS}")
-        S, batch_size = int(num_samples), int(batch_size)
-        if batch_size < 1 or S < 1:
-            raise ValueError("batch_size and num_samples must be positive")
-        shape = lambda a: tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-        if len(shape(X)) != 2 or shape(X)[0] < 1:
-            raise ValueError("X must be a non-empty (N, D_in) array")
+        S, batch_size = self._batch_args(num_samples, batch_size)
         ND = self.layers[-1].num_outputs if self.likelihood.bernoulli else 1
-        want = (shape(X)[0], ND)
-        if shape(Y) != want:
-            raise ValueError(f"Ys has shape {shape(Y)}, expected {want}")
-        if zs is not None:
-            if len(zs) != len(self.layers):
-                raise ValueError("zs needs one entry (or None) per layer")
-            if any(z is not None and len(shape(z)) != 3 for z in zs):
-                raise ValueError("z must be rank-3, broadcastable to (S, N, D_out)")
+        self._row_args(X, Y, ND, "", zs)
         if not hasattr(Y, "data_ptr"):
             self.likelihood.check_targets(Y)
         return kind, Cn, ND, S, bins, batch_size
@@ -486,25 +473,42 @@ class DGP_Base(Parameterized):
         with D > 1 outputs: the scalars pooled over outputs, `error_rate_per_output`, `log_density_per_output`, `brier_per_output`,
         `ece_per_output`, `confusion` (D, 2, 2), the reliability and per_class arrays with a leading D.  With return_rows: `probs`
         (N*, K) (Bernoulli: (N*, D), p(y = 1)) and `rows` (N*, ND, 4) = [predicted class, confidence, log pi_y, brier]."""
-        kind, Cn, ND, S, bins, batch_size = self._classification_args(Xs, Ys, num_samples, bins, batch_size, zs)
-        eng = self.engine()
-        ctx = eng.ctx
-        Xd = Xs.contiguous() if hasattr(Xs, "data_ptr") else ctx.to_device(Xs)
-        Yd = Ys.contiguous() if hasattr(Ys, "data_ptr") else ctx.to_device(Ys)
-        zs = self._device_zs(ctx, zs)
+        return self._classification_report(Xs, Ys, num_samples, bins, return_rows, batch_size=batch_size, zs=zs)
+
+    def _classification_report(self, Xs, Ys, num_samples, bins, return_rows, **how):
+        kind, Cn, ND, S, bins, how["batch_size"] = self._classification_args(Xs, Ys, num_samples, bins, how.get("batch_size", 1),
+                                                                             how.get("zs"))
+        ctx = self._score_context()
+        Xd, Yd = ctx.as_device(Xs), ctx.as_device(Ys)
         N, D = Xd.shape[0], self.layers[-1].num_outputs
         acc = ctx.empty(4 + 3 * bins + Cn + Cn * Cn, ND)
         probs = ctx.empty(N, D) if return_rows else None
         rows = ctx.empty(N, ND, 4) if return_rows else None
-        self._over_row_batches(ctx, N, batch_size, zs, lambda a, b, zb, seed: eng.classification_batch(
-            Xd[a:b], Yd[a:b], S, bins, acc, a > 0, zs=zb, seed=seed, probs=probs[a:b] if return_rows else None,
-            rows=rows[a:b] if return_rows else None))
+        for a, b, launch in self._score_batches(ctx, Xd, Yd, S, **how):
+            launch("classification", bins, acc, a > 0, probs=probs[a:b] if return_rows else None, rows=rows[a:b] if return_rows else None)
         out = classification_scores(acc.cpu().numpy(), bins, Cn)
         out["n"] = N
         if return_rows:
             out["probs"] = probs.cpu().numpy()
             out["rows"] = rows.cpu().numpy()
         return out
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def evaluation_scores(sums, multiclass, gaussian, Y_std=1.0):
+    """The dict of DGP_Base.evaluate (without `n` and `rows`) from the (3, D) accumulator of dsdgp_model_evaluate / dsdgp_eval_mixture."""
+    if multiclass:
+        cnt = float(sums[2, 0])
+        return {"error_rate": float(sums[0, 0]) / cnt, "log_density": float(sums[1, 0]) / cnt}
+    cnt = float(sums[2].sum())
+    # the model lives in standardised units y = y_orig / Y_std; the density of y_orig is that of y divided by Y_std,
+    # N(y c | m c, v c^2) = N(y | m, v) / c, component by component, hence also for the mixture: log p(y_orig) = l - log Y_std
+    # (run_regression.py:122 scales targets, means and standard deviations by Y_std before norm.logpdf)
+    return {"rmse": Y_std * float(np.sqrt(sums[0].sum() / cnt)), "rmse_per_output": Y_std * np.sqrt(sums[0] / sums[2]),
+            "log_density": float(sums[1].sum()) / cnt - (np.log(Y_std) if gaussian else 0.0)}
 
 
 def classification_scores(sums, bins, C):

@@ -46,7 +46,54 @@ def concat_input_prop(X, p, samples, mean, var, full_cov=False):
     return samples, mean, var
 
 
+def prepend_input_prop(X, layers, Fs, Fmeans, Fvars):
+    """concat_input_prop layer by layer, in place on the lists of per-layer device results: the device hands the concatenated
+    [X_prop | F] to the next layer itself, the returned lists get the same copies prepended here.  X: the tiled (S, N, D_in) input."""
+    for l, layer in enumerate(layers):
+        if layer.input_prop_dim:
+            Fs[l], Fmeans[l], Fvars[l] = concat_input_prop(X, layer.input_prop_dim, Fs[l], Fmeans[l], Fvars[l])
+        X = Fs[l]
+
+
+def propagate_layers(layers, F, zs=None, full_cov=False):
+    """The layer loop of dgp.py:69-74 on the host, from the tiled (S, N, D_in) input F -> Fs, Fmeans, Fvars.  Every piece of arithmetic
+    is a libdsdgp call (the layers' conditionals, utils.reparameterize); zs: a draw (or None) per layer."""
+    Fs, Fmeans, Fvars = [], [], []
+    for layer, z in zip(layers, zs or [None] * len(layers)):
+        F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=full_cov)
+        Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
+    return Fs, Fmeans, Fvars
+
+
+def layer_parameters(layer, mean=True):
+    """[(Parameter, key), ...] of what a layer owns, in the order of the engine's layout (trainable or not): `Z`, `q_mu`, `q_sqrt`, the
+    kernel's `variance` and `lengthscales`, a White part's `white_variance`, and with `mean` the `A`, `b` of a Linear mean that is not a
+    fixed map.  What a layer does not have (a dense layer's Z, a sampled layer's q_sqrt) is left out.  Host only."""
+    stat, wk = split_kernel(layer.kern)
+    out = [(layer.feature.Z, "Z")] if getattr(layer, "feature", None) is not None else []
+    out += [(p, k) for k in ("q_mu", "q_sqrt") for p in [getattr(layer, k, None)] if p is not None]
+    out += [(stat.variance, "variance"), (stat.lengthscales, "lengthscales")] + ([(wk.variance, "white_variance")] if wk is not None else [])
+    mf = layer.mean_function
+    if mean and getattr(mf, "kind", None) == "linear" and mf.in_theta():
+        out += [(mf.A, "A"), (mf.b, "b")]
+    return out
+
+
+def _refuse_trainable_mean(mean_function, what):
+    if getattr(mean_function, "kind", None) == "linear" and (mean_function.A.trainable or mean_function.b.trainable):
+        raise NotImplementedError(f"{what}: a trainable Linear mean function — the gradients of its A and b are not "
+                                  "formed; fix it with set_trainable(False)")
+
+
+def _log_prior(layer):
+    """the standard-normal prior of q_mu (layers.py:257, 272): -1/2 sum q_mu^2 - 1/2 (rows x outputs) log(2 pi)"""
+    q = layer.q_mu.value
+    return float(-0.5 * np.sum(q * q) - 0.5 * q.size * np.log(2.0 * np.pi))
+
+
 class Layer(Parameterized):
+    _no_owner = "a layer outside a model owns no random numbers: pass z to sample_from_conditional"
+
     def __init__(self, input_prop_dim=None, **kwargs):
         """input_prop_dim: the first dimensions of X to propagate (layers.py:36-50); None = no input propagation."""
         self.input_prop_dim = input_prop_dim
@@ -56,6 +103,14 @@ class Layer(Parameterized):
 
     def KL(self):
         return 0.0
+
+    def _engine(self):
+        """where sample_from_conditional draws when it is given no z: the owning model (its `randn`, under its seeds)"""
+        ref = getattr(self, "_model", None)          # a weak reference: the model is not one of the layer's parameters
+        model = ref() if ref is not None else None
+        if model is None:
+            raise RuntimeError(self._no_owner)
+        return model
 
     # layers.py:52-74
     def conditional_SND(self, X, full_cov=False):
@@ -184,12 +239,23 @@ def kernel_expectations_grad(kern, Z, X_mean, X_var, g_psi0, g_psi1, g_psi2, on_
     N, M, D = mu.shape[0], Zd.shape[0], mu.shape[1]
     if (g1 is not None and tuple(g1.shape) != (N, M)) or (g2 is not None and tuple(g2.shape) != (M, M)):
         raise ValueError("kernel_expectations_grad: g_psi1 must be (N, M) and g_psi2 (M, M)")
-    nls = D if spec.ard else 1
-    d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(1 + nls)
+    d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(kernel_grad_size(spec, False))
     _lib.check(ctx.lib.dsdgp_rbf_expectations_grad(ctx.handle, C.byref(spec), ptr(Zd), M, ptr(mu), ptr(s), N, float(g_psi0), ptr(g1), M,
                                                    ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k)))
-    out = dict(X_mean=d_mu, X_var=d_s, Z=d_Z, variance=d_k[:1], lengthscales=d_k[1:])
+    variance, lengthscales, _ = cut_kernel_grad(spec, d_k)
+    out = dict(X_mean=d_mu, X_var=d_s, Z=d_Z, variance=variance, lengthscales=lengthscales)
     return out if on_device else _to_host(ctx, out, ("variance",))
+
+
+def kernel_grad_size(spec, diag):
+    """the entries of a kernel's gradient block: variance, lengthscales (D with ARD, else one) and, with `diag`, a trailing diagonal entry"""
+    return 1 + (int(spec.input_dim) if spec.ard else 1) + int(bool(diag))
+
+
+def cut_kernel_grad(spec, d_k):
+    """(variance, lengthscales, the trailing diagonal entry — empty where the block has none) of the kernel gradient block d_k"""
+    nls = kernel_grad_size(spec, False) - 1
+    return d_k[:1], d_k[1:1 + nls], d_k[1 + nls:]
 
 
 _KERN_KIND = {"rbf": _lib.KERN_RBF, "matern52": _lib.KERN_MATERN52}
@@ -221,10 +287,10 @@ def kernel_gram_grad(kern, X, X2, G, on_device=False):
     if Xd.dim() != 2 or Xd.shape[1] != D or (X2d is not None and (X2d.dim() != 2 or X2d.shape[1] != D)) or \
             tuple(Gd.shape) != (Xd.shape[0], Xd.shape[0] if X2d is None else X2d.shape[0]):
         raise ValueError("kernel_gram_grad: X must be (N, D), X2 (N2, D) or None, G (N, N2) — (N, N) with X2=None — D the kernel's input_dim")
-    nls = D if spec.ard else 1
-    d_X, d_X2, d_k = ctx.empty(Xd.shape[0], D), None if X2d is None else ctx.empty(X2d.shape[0], D), ctx.empty(2 + nls)
+    d_X, d_X2, d_k = ctx.empty(Xd.shape[0], D), None if X2d is None else ctx.empty(X2d.shape[0], D), ctx.empty(kernel_grad_size(spec, True))
     ctx.gram_grad(spec, Xd, X2d, Gd, d_X, d_X2, d_k)
-    out = dict(X=d_X, variance=d_k[:1], lengthscales=d_k[1:1 + nls], diag=d_k[1 + nls:])
+    variance, lengthscales, diag = cut_kernel_grad(spec, d_k)
+    out = dict(X=d_X, variance=variance, lengthscales=lengthscales, diag=diag)
     if d_X2 is not None:
         out["X2"] = d_X2
     out = out if on_device else _to_host(ctx, out, ("variance", "diag"))
@@ -258,6 +324,7 @@ class GPMC_Layer(Layer):
     (dsdgp_gram, dsdgp_potrf; `settings.jitter`) and is a constant afterwards, as in the reference (layers.py:278-279): the layer's
     own kernel hyper-parameters therefore have no gradient, and changing them later does not change Lu."""
     white = True
+    _no_owner = "a GPMC_Layer outside a DGP_Heinonen owns no random numbers: pass z to sample_from_conditional"
 
     def __init__(self, kern, X, num_outputs, mean_function, input_prop_dim=None, **kwargs):
         Layer.__init__(self, input_prop_dim, **kwargs)
@@ -275,18 +342,7 @@ class GPMC_Layer(Layer):
         ctx.potrf(Lu)
         object.__setattr__(self, "_dev", dict(ctx=ctx, spec=spec, ls=ls, X=Xd, Lu=Lu))
 
-    def _engine(self):
-        """where sample_from_conditional draws when it is given no z: the owning DGP_Heinonen (its `randn`, under its seeds)"""
-        ref = getattr(self, "_model", None)
-        model = ref() if ref is not None else None
-        if model is None:
-            raise RuntimeError("a GPMC_Layer outside a DGP_Heinonen owns no random numbers: pass z to sample_from_conditional")
-        return model
-
-    def log_prior(self):
-        """the standard-normal prior of q_mu (layers.py:272): -1/2 sum q_mu^2 - 1/2 N D log(2 pi)"""
-        q = self.q_mu.value
-        return float(-0.5 * np.sum(q * q) - 0.5 * q.size * np.log(2.0 * np.pi))
+    log_prior = _log_prior
 
     def build_latents(self, on_device=False):
         """f = Lu q_mu + m(X) (N, num_outputs), the propagated columns X[:, :input_prop_dim] prepended (layers.py:282-287)"""
@@ -363,6 +419,7 @@ class SGPMC_Layer(Layer):
     frozen at construction: Z and the kernel are read at every evaluation and have gradients.  Constructing the layer touches no
     device.  It lives under a collapsed layer in a DGP_Collapsed, or at every depth of a model_zoo.DGP_SGPMC; the engine does not take it
     (its KL tail reads a q_sqrt)."""
+    _no_owner = "an SGPMC_Layer outside a DGP_Collapsed owns no random numbers: pass z to sample_from_conditional"
 
     def __init__(self, kern, Z, num_outputs, mean_function, white=False, input_prop_dim=None, **kwargs):
         Layer.__init__(self, input_prop_dim, **kwargs)
@@ -377,27 +434,10 @@ class SGPMC_Layer(Layer):
         self.num_outputs = int(num_outputs)
         self.white = bool(white)
 
-    def _engine(self):
-        """where sample_from_conditional draws when it is given no z: the owning DGP_Collapsed (its `randn`, under its seeds)"""
-        ref = getattr(self, "_model", None)
-        model = ref() if ref is not None else None
-        if model is None:
-            raise RuntimeError("an SGPMC_Layer outside a DGP_Collapsed owns no random numbers: pass z to sample_from_conditional")
-        return model
-
-    def KL(self):
-        return 0.0
-
-    def log_prior(self):
-        """the standard-normal prior of q_mu (layers.py:257): -1/2 sum q_mu^2 - 1/2 M D log(2 pi)"""
-        q = self.q_mu.value
-        return float(-0.5 * np.sum(q * q) - 0.5 * q.size * np.log(2.0 * np.pi))
+    log_prior = _log_prior
 
     def _check_mean(self, what):
-        mf = self.mean_function
-        if getattr(mf, "kind", None) == "linear" and (mf.A.trainable or mf.b.trainable):
-            raise NotImplementedError(f"SGPMC_Layer.{what}: a trainable Linear mean function — the gradients of its A and b are not "
-                                      "formed; fix it with set_trainable(False)")
+        _refuse_trainable_mean(self.mean_function, f"SGPMC_Layer.{what}")
 
     def _operands(self, X):
         ctx = Context.get()
@@ -455,18 +495,18 @@ class SGPMC_Layer(Layer):
         gv = gv.contiguous()
         if tuple(gm.shape) != (n, DO) or tuple(gv.shape) != (n,):
             raise ValueError(f"conditional_vjp: dmean must be {(n, DO)} and dvar {(n, DO)} or {(n,)}")
-        nls = D if spec.ard else 1
-        d_q, d_Z, d_X, d_k = ctx.empty(M, DO), ctx.empty(M, D), ctx.empty(n, D), ctx.empty(2 + nls)
+        d_q, d_Z, d_X, d_k = ctx.empty(M, DO), ctx.empty(M, D), ctx.empty(n, D), ctx.empty(kernel_grad_size(spec, True))
         ctx.sparse_conditional_grad(spec, Z, Xd, q, self.white, settings.jitter, gm, gv, d_q, d_Z, d_X, d_k)
         mf = self.mean_function
         if mf.kind == "identity":
             d_X = d_X + gm
         elif mf.kind == "linear":
             ctx.gemm(0, 1, 1.0, gm, ctx.to_device(mf.A.value), 1.0, d_X)
-        res = dict(q_mu=d_q, Z=d_Z, X=d_X, variance=d_k[:1], lengthscales=d_k[1:1 + nls])
+        variance, lengthscales, diag = cut_kernel_grad(spec, d_k)
+        res = dict(q_mu=d_q, Z=d_Z, X=d_X, variance=variance, lengthscales=lengthscales)
         scalars = ["variance"]
         if spec.has_white:
-            res["white_variance"] = d_k[1 + nls:]
+            res["white_variance"] = diag
             scalars.append("white_variance")
         return res if on_device else _to_host(ctx, res, tuple(scalars))
 
@@ -475,6 +515,7 @@ class Collapsed_Layer(Layer):
     """Extra functions for a collapsed layer (layers.py:296-307): a last layer whose Gaussian posterior is at its exact optimum for
     the data it has been given, so it carries no variational parameters and no KL term of its own."""
     white = False
+    _no_owner = "a collapsed layer outside a DGP_Collapsed owns no random numbers: pass z to sample_from_conditional"
 
     def set_data(self, X_mean, X_var, Y, lik_variance):
         self._X_mean = X_mean
@@ -484,14 +525,6 @@ class Collapsed_Layer(Layer):
 
     def build_likelihood(self):
         raise NotImplementedError
-
-    def _engine(self):
-        """where sample_from_conditional draws when it is given no z: the owning DGP_Collapsed (its `randn`, under its seeds)"""
-        ref = getattr(self, "_model", None)          # a weak reference: the model is not one of the layer's parameters
-        model = ref() if ref is not None else None
-        if model is None:
-            raise RuntimeError("a collapsed layer outside a DGP_Collapsed owns no random numbers: pass z to sample_from_conditional")
-        return model
 
 
 class SGPR_Layer(Collapsed_Layer):
@@ -601,16 +634,15 @@ class SGPR_Layer(Collapsed_Layer):
         ctx.collapsed_adjoints(Si, Ki, KpK, psi2, alpha, c, Y, psi0, s2, g2, dK, out)
         ctx.collapsed_bound(LB, f["G"], c, Y, psi0, s2, bound)
         spec = f["spec"]
-        D = int(spec.input_dim)
-        nls = D if spec.ard else 1
-        d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(1 + nls)
-        k_mu, k_Z, k_k = ctx.empty(M, D), ctx.empty(M, D), ctx.empty(1 + nls)
+        D, nk = int(spec.input_dim), kernel_grad_size(spec, False)
+        d_mu, d_s, d_Z, d_k = ctx.empty(N, D), ctx.empty(N, D), ctx.empty(M, D), ctx.empty(nk)
+        k_mu, k_Z, k_k = ctx.empty(M, D), ctx.empty(M, D), ctx.empty(nk)
         grad = lambda *args: _lib.check(ctx.lib.dsdgp_rbf_expectations_grad(ctx.handle, C.byref(spec), ptr(Z), M, *args))
         grad(ptr(self._X_mean), ptr(self._X_var), N, -0.5 * DY / s2, ptr(g1), M, ptr(g2), M, ptr(d_mu), ptr(d_s), ptr(d_Z), ptr(d_k))
         grad(ptr(Z), None, M, 0.0, ptr(dK), M, None, 0, ptr(k_mu), None, ptr(k_Z), ptr(k_k))
         d_Z = d_Z + (k_Z + k_mu)                     # element-wise sums of the two calls' results, on the context's stream
-        d_k = d_k + k_k
-        res = dict(bound=bound[:1], Z=d_Z, variance=d_k[:1], lengthscales=d_k[1:], lik_variance=out[:1], X_mean=d_mu, X_var=d_s)
+        variance, lengthscales, _ = cut_kernel_grad(spec, d_k + k_k)
+        res = dict(bound=bound[:1], Z=d_Z, variance=variance, lengthscales=lengthscales, lik_variance=out[:1], X_mean=d_mu, X_var=d_s)
         return res if on_device else _to_host(ctx, res, ("bound", "variance", "lik_variance"))
 
     # layers.py:483-525
@@ -703,13 +735,10 @@ class GPR_Layer(Collapsed_Layer):
         mean with trainable A or b raises NotImplementedError: their gradients are not formed."""
         f = self._need_factors()
         mf = self.mean_function
-        if getattr(mf, "kind", None) == "linear" and (mf.A.trainable or mf.b.trainable):
-            raise NotImplementedError("GPR_Layer.bound_gradients: a trainable Linear mean function — the gradients of its A and b are not "
-                                      "formed; fix it with set_trainable(False)")
+        _refuse_trainable_mean(mf, "GPR_Layer.bound_gradients")
         ctx, N, DY, L, V, spec = f["ctx"], f["N"], f["DY"], f["L"], f["V"], f["spec"]
         F = self._X_mean
         D = int(spec.input_dim)
-        nls = D if spec.ard else 1
         alpha = V.clone()
         ctx.trsm(L, alpha, trans=1)                  # alpha = L^-T V
         zeros = ctx.torch.zeros(N, N, dtype=ctx.torch.float64, device=F.device)
@@ -718,18 +747,19 @@ class GPR_Layer(Collapsed_Layer):
         ctx.trsm(L, Li)                              # L^-1
         ctx.gemm(1, 0, 1.0, Li, Li, 0.0, dK)         # K^-1
         ctx.gemm(0, 1, 0.5, alpha, alpha, -0.5 * DY, dK)      # dF/dK = 1/2 (alpha alpha^T - D_Y K^-1)
-        d_X, d_k, bound = ctx.empty(N, D), ctx.empty(2 + nls), ctx.empty(4)
+        d_X, d_k, bound = ctx.empty(N, D), ctx.empty(kernel_grad_size(spec, True)), ctx.empty(4)
         ctx.gram_grad(spec, F, None, dK, d_X, None, d_k)
         if mf.kind == "identity":
             d_X = d_X + alpha
         elif mf.kind == "linear":
             ctx.gemm(0, 1, 1.0, alpha, ctx.to_device(mf.A.value), 1.0, d_X)
         ctx.gpr_bound(L, V, bound)
-        res = dict(bound=bound[:1], variance=d_k[:1], lengthscales=d_k[1:1 + nls], lik_variance=d_k[1 + nls:], X_mean=d_X,
+        variance, lengthscales, diag = cut_kernel_grad(spec, d_k)
+        res = dict(bound=bound[:1], variance=variance, lengthscales=lengthscales, lik_variance=diag, X_mean=d_X,
                    X_var=ctx.torch.zeros_like(d_X))
         scalars = ["bound", "variance", "lik_variance"]
         if spec.has_white:
-            res["white_variance"] = d_k[1 + nls:]
+            res["white_variance"] = diag
             scalars.append("white_variance")
         return res if on_device else _to_host(ctx, res, tuple(scalars))
 

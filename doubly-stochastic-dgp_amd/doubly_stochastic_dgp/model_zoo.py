@@ -24,8 +24,10 @@ import numpy as np
 
 from . import _lib
 from .dgp import DGP_Base
-from .gpflow_compat import Gaussian
-from .layers import Collapsed_Layer, GPMC_Layer, GPR_Layer, SGPMC_Layer, SGPR_Layer, _to_host, concat_input_prop
+from .engine import ptr
+from .gpflow_compat import Gaussian, likelihood_args, likelihood_entry, positive_slope, split_kernel
+from .layers import (Collapsed_Layer, GPMC_Layer, GPR_Layer, SGPMC_Layer, SGPR_Layer, _to_host, layer_parameters, prepend_input_prop,
+                     propagate_layers)
 
 
 class DGP_Collapsed(DGP_Base):
@@ -107,26 +109,10 @@ class DGP_Collapsed(DGP_Base):
             object.__setattr__(self, "_eng", eng)
         return self._eng
 
-    def _context(self):
-        from .engine import Context
-        return Context.get()
-
-    def _device_data(self):
-        if self._dev_data is None:
-            ctx = self._context()
-            object.__setattr__(self, "_dev_data", (ctx.to_device(self.X_data), ctx.to_device(self.Y_data)))
-        return self._dev_data
-
     def randn(self, shape, seed=None):
         """N(0, 1) draws for the last layer's samples (Layer.sample_from_conditional without z) under this model's seed sequence:
         stream len(layers) - 1 of `_draw_seed()`, as the engine numbers the streams of the layers it draws for."""
-        ctx = self._context()
-        n = int(np.prod(shape))
-        out = ctx.empty(n)
-        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(self._draw_seed() if seed is None else seed),
-                                       C.c_uint64(len(self.layers) - 1), n, C.c_void_p(out.data_ptr())))
-        ctx.sync()
-        return out.cpu().numpy().reshape(shape)
+        return self._randn(shape, self._draw_seed() if seed is None else seed, len(self.layers) - 1)
 
     def _refresh(self):
         """Parameters that another engine (the DGP the inner layers are shared with) has trained since the last evaluation: reading
@@ -153,20 +139,12 @@ class DGP_Collapsed(DGP_Base):
         zs = list(zs)[:len(inner)] if zs is not None else None
         self._refresh()
         if full_cov or self._sgpmc:                                 # the host layer loop; an SGPMC_Layer is in no engine
-            F, Fs, Fmeans, Fvars = sX, [], [], []
-            for layer, z in zip(inner, zs or [None] * len(inner)):
-                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=full_cov)
-                Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
-            return Fs, Fmeans, Fvars
+            return propagate_layers(inner, sX, zs, full_cov=full_cov)
         eng = self.inner_engine()
         Fs, Fmeans, Fvars = eng.propagate(X, int(S), zs=zs, seed=self._draw_seed())
         eng.ctx.sync()
         Fs, Fmeans, Fvars = self._np(Fs), self._np(Fmeans), self._np(Fvars)
-        Fin = sX
-        for l, layer in enumerate(inner):                           # layers.py:105-117, as DGP_Base.propagate
-            if layer.input_prop_dim:
-                Fs[l], Fmeans[l], Fvars[l] = concat_input_prop(Fin, layer.input_prop_dim, Fs[l], Fmeans[l], Fvars[l])
-            Fin = Fs[l]
+        prepend_input_prop(sX, inner, Fs, Fmeans, Fvars)            # layers.py:105-117, as DGP_Base.propagate
         return Fs, Fmeans, Fvars
 
     def _set_data(self, zs=None, seed=None):
@@ -279,7 +257,6 @@ class DGP_Collapsed(DGP_Base):
         """compute_log_likelihood_gradients over an SGPMC_Layer: the top layer's adjoints in X_mean and X_var (the propagated columns'
         dropped: they are copies of the fixed inputs) pushed through SGPMC_Layer.conditional_vjp, all on the device; with `inner` the
         pairs go on with the layer's `feature.Z`, `q_mu`, kernel `variance`, `lengthscales` and a White part's `variance`."""
-        from .gpflow_compat import split_kernel
         top, low = self.layers[-1], self.layers[0]
         self._set_data()
         g = top.bound_gradients(on_device=True)
@@ -289,9 +266,7 @@ class DGP_Collapsed(DGP_Base):
             p = low.input_prop_dim or 0
             v = low.conditional_vjp(g["X_mean"][:, p:].contiguous(), g["X_var"][:, p:].contiguous(), X=self._device_data()[0],
                                     on_device=True)
-            stat, wk = split_kernel(low.kern)
-            low_pairs = [(low.feature.Z, "Z"), (low.q_mu, "q_mu"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales")] + \
-                        ([(wk.variance, "white_variance")] if wk is not None else [])
+            low_pairs = layer_parameters(low, mean=False)
             g.update({"low_" + k: v[k] for _, k in low_pairs})
             scalars += ["low_variance", "low_white_variance"]
         g = _to_host(self._context(), g, tuple(scalars))
@@ -299,62 +274,44 @@ class DGP_Collapsed(DGP_Base):
         pairs += [(p, np.asarray(g["low_" + k], dtype=np.float64).reshape(p.shape)) for p, k in low_pairs]
         return g["bound"], pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
 
-    def _need_sgpmc(self, what):
-        if not self._sgpmc:
+    def _prior_layer(self, what):
+        """the layer whose q_mu carries the prior of a log density: the SGPMC_Layer (DGP_Heinonen: the GPMC_Layer) below the top"""
+        if not hasattr(self.layers[0], "log_prior"):
             raise NotImplementedError(f"DGP_Collapsed.{what}: a log density needs a sampled inner layer with a prior — an SGPMC_Layer "
                                       "below the collapsed layer (or a DGP_Heinonen)")
+        return self.layers[0]
 
     def compute_log_prior(self):
-        """the standard-normal prior of the SGPMC_Layer's q_mu"""
-        self._need_sgpmc("compute_log_prior")
-        return self.layers[0].log_prior()
+        """the standard-normal prior of the sampled layer's q_mu"""
+        return self._prior_layer("compute_log_prior").log_prior()
 
     def compute_log_density(self):
         """compute_log_likelihood() + compute_log_prior(): the target of training.HMC and, with inner=True, of training.ScipyOptimizer"""
-        self._need_sgpmc("compute_log_density")
+        self._prior_layer("compute_log_density")
         return self.compute_log_likelihood() + self.compute_log_prior()
 
     def compute_log_density_gradients(self):
         """(log density, [(Parameter, gradient), ...]): compute_log_likelihood_gradients(inner=True) with the prior added — -q_mu to
         q_mu's pair"""
-        self._need_sgpmc("compute_log_density_gradients")
+        low = self._prior_layer("compute_log_density_gradients")
         bound, pairs, _ = self.compute_log_likelihood_gradients(inner=True)
-        low = self.layers[0]
         return bound + low.log_prior(), [(p, g - low.q_mu.value if p is low.q_mu else g) for p, g in pairs]
 
     def top_parameters(self):
         """[(Parameter, its key in the last layer's bound_gradients), ...]: what the collapsed last layer owns and the likelihood's
         variance.  SGPR_Layer: `feature.Z`, the kernel's `variance` and `lengthscales`, the noise variance.  GPR_Layer: no inducing
         inputs; the kernel's `variance` and `lengthscales`, a White part's `variance`, the noise variance."""
-        from .gpflow_compat import split_kernel
-        top = self.layers[-1]
-        stat, wk = split_kernel(top.kern)
-        lik = self.likelihood.likelihood
-        if isinstance(top, GPR_Layer):
-            return [(stat.variance, "variance"), (stat.lengthscales, "lengthscales")] + \
-                   ([(wk.variance, "white_variance")] if wk is not None else []) + [(lik.variance, "lik_variance")]
-        return [(top.feature.Z, "Z"), (stat.variance, "variance"), (stat.lengthscales, "lengthscales"), (lik.variance, "lik_variance")]
+        return layer_parameters(self.layers[-1], mean=False) + [(self.likelihood.likelihood.variance, "lik_variance")]
 
     def inner_parameters(self):
         """The Parameters of the inner layers in the order of the engine's layout (trainable or not) — per layer `feature.Z`, `q_mu`,
         `q_sqrt`, the kernel's `variance` and `lengthscales`, a White part's `variance`, and `A`, `b` of a Linear mean that is not a
         fixed map.  Host only: no engine is built."""
-        from .gpflow_compat import split_kernel
-        out = []
-        for layer in self.layers[:-1]:
-            stat, wk = split_kernel(layer.kern)
-            out += [layer.feature.Z, layer.q_mu] + ([layer.q_sqrt] if layer.q_sqrt is not None else []) + [stat.variance, stat.lengthscales]
-            if wk is not None:
-                out.append(wk.variance)
-            mf = layer.mean_function
-            if mf.kind == "linear" and mf.in_theta():
-                out += [mf.A, mf.b]
-        return out
+        return [p for layer in self.layers[:-1] for p, _ in layer_parameters(layer)]
 
     def _inner_pairs(self, eng):
         """[(Parameter, gradient), ...] of the inner layers' trainable parameters from the engine's gradient buffer, which holds
         d(-bound)/d(unconstrained): sign flipped, a positive parameter's entry divided by d theta / dx (gpflow_compat.positive_slope)."""
-        from .gpflow_compat import positive_slope
         eng.ctx.sync()
         out4 = eng.out4.cpu().numpy()
         if out4[3] != 0.0:
@@ -420,18 +377,7 @@ class DGP_Heinonen(DGP_Collapsed):
         """model_zoo.py:46-50: the latents at the training inputs become the GPR_Layer's data, then DGP_Base.propagate's loop over the
         layers (dgp.py:61-76) on the host, each layer's arithmetic on the device."""
         self._set_data()
-        F = np.tile(np.asarray(X, dtype=np.float64)[None], [int(S), 1, 1])
-        Fs, Fmeans, Fvars = [], [], []
-        for layer, z in zip(self.layers, zs or [None] * len(self.layers)):
-            F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=full_cov)
-            Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
-        return Fs, Fmeans, Fvars
-
-    def compute_log_prior(self):
-        return self.layers[0].log_prior()
-
-    def compute_log_density(self):
-        return self.compute_log_likelihood() + self.compute_log_prior()
+        return propagate_layers(self.layers, np.tile(np.asarray(X, dtype=np.float64)[None], [int(S), 1, 1]), zs, full_cov=full_cov)
 
     def compute_log_likelihood_gradients(self, zs=None, inner=False):
         """(bound, [(Parameter, gradient), ...], {"X_mean": ..., "X_var": ...}): log p(Y | q_mu) and its gradients with respect to the
@@ -446,12 +392,6 @@ class DGP_Heinonen(DGP_Collapsed):
         g = _to_host(self._context(), dict(g, q_mu=dq), ("bound", "variance", "lik_variance", "white_variance"))
         pairs = [(low.q_mu, g["q_mu"])] + [(p, np.asarray(g[k], dtype=np.float64).reshape(p.shape)) for p, k in self.top_parameters()]
         return g["bound"], pairs, {"X_mean": g["X_mean"], "X_var": g["X_var"]}
-
-    def compute_log_density_gradients(self):
-        """(log density, [(Parameter, gradient), ...]): compute_log_likelihood_gradients with the prior added — -q_mu to q_mu's pair"""
-        bound, pairs, _ = self.compute_log_likelihood_gradients()
-        low = self.layers[0]
-        return bound + low.log_prior(), [(p, g - low.q_mu.value if p is low.q_mu else g) for p, g in pairs]
 
 
 class DGP_SGPMC(DGP_Base):
@@ -474,7 +414,6 @@ class DGP_SGPMC(DGP_Base):
     scratch_budget = 1 << 30
 
     def __init__(self, X, Y, likelihood, layers, minibatch_size=None, num_samples=1, num_data=None, **kwargs):
-        from .gpflow_compat import likelihood_entry
         layers = list(layers)
         if not layers or len(layers) > _lib.DSDGP_MAX_LAYERS:
             raise ValueError(f"DGP_SGPMC: 1 .. {_lib.DSDGP_MAX_LAYERS} layers, not {len(layers)}")
@@ -500,40 +439,11 @@ class DGP_SGPMC(DGP_Base):
     def train_step(self, *args, **kwargs):
         raise NotImplementedError("DGP_SGPMC.train_step: the model is sampled, not optimised on a bound: training.SGHMC")
 
-    def _context(self):
-        from .engine import Context
-        return Context.get()
-
-    def _device_data(self):
-        if self._dev_data is None:
-            ctx = self._context()
-            object.__setattr__(self, "_dev_data", (ctx.to_device(self.X_data), ctx.to_device(self.Y_data)))
-        return self._dev_data
-
-    def next_minibatch(self):
-        """Device tensors (Xb, Yb) of the next minibatch (dgp.py:51-52), or the full data when not minibatching"""
-        Xd, Yd = self._device_data()
-        if self._minibatch is None:
-            return Xd, Yd
-        ctx = self._context()
-        idx = ctx.torch.from_numpy(self._minibatch.next_indices()).to(Xd.device)
-        n = idx.shape[0]
-        Xb, Yb = ctx.empty(n, Xd.shape[1]), ctx.empty(n, Yd.shape[1])
-        _lib.check(ctx.lib.dsdgp_gather_rows2(ctx.handle, C.c_void_p(Xd.data_ptr()), Xd.shape[1], C.c_void_p(Xb.data_ptr()),
-                                              C.c_void_p(Yd.data_ptr()), Yd.shape[1], C.c_void_p(Yb.data_ptr()),
-                                              C.c_void_p(idx.data_ptr()), n, 0))
-        object.__setattr__(self, "_keep_idx", idx)
-        return Xb, Yb
+    _score_context = DGP_Base._context
 
     def randn(self, shape, seed=None):
         """N(0, 1) draws for Layer.sample_from_conditional without z, under this model's seed sequence"""
-        ctx = self._context()
-        n = int(np.prod(shape))
-        out = ctx.empty(n)
-        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(self._eval_seed() if seed is None else seed), C.c_uint64(0), n,
-                                       C.c_void_p(out.data_ptr())))
-        ctx.sync()
-        return out.cpu().numpy().reshape(shape)
+        return self._randn(shape, self._eval_seed() if seed is None else seed, 0)
 
     def fix_draws(self, seed):
         """pin the Philox seed of every evaluation that is given no zs (None: back to a fresh seed per evaluation)"""
@@ -546,22 +456,13 @@ class DGP_SGPMC(DGP_Base):
     def parameter_list(self):
         """[(Parameter, its block of the flat gradient: layer index or None, key)] in the order of compute_log_density_gradients: per
         layer `feature.Z`, `q_mu`, kernel `variance`, `lengthscales`, a White part's `variance`; then the likelihood's parameter"""
-        from .gpflow_compat import likelihood_entry, split_kernel
-        out = []
-        for l, layer in enumerate(self.layers):
-            stat, wk = split_kernel(layer.kern)
-            out += [(layer.feature.Z, l, "Z"), (layer.q_mu, l, "q_mu"), (stat.variance, l, "variance"), (stat.lengthscales, l, "lengthscales")]
-            if wk is not None:
-                out.append((wk.variance, l, "white_variance"))
+        out = [(p, l, k) for l, layer in enumerate(self.layers) for p, k in layer_parameters(layer, mean=False)]
         par = likelihood_entry(self.likelihood.likelihood)[1]
-        if par is not None:
-            out.append((par, None, "lik"))
-        return out
+        return out + ([(par, None, "lik")] if par is not None else [])
 
     def _stack_desc(self, ctx):
         """(StackDesc at the Parameters' current values, what its pointers point to: keep it until the device is done)"""
         from . import settings
-        from .gpflow_compat import likelihood_args
         from .layers import _kernel_spec
         keep = []
         if ctx.lib.dsdgp_sizeof_stack_desc() != C.sizeof(_lib.StackDesc):
@@ -693,29 +594,19 @@ class DGP_SGPMC(DGP_Base):
         S = int(S)
         Xh = X.cpu().numpy() if hasattr(X, "data_ptr") else np.asarray(X, dtype=np.float64)
         if full_cov:                                                # the host layer loop of dgp.py:69-74, as DGP_Base.propagate
-            F, Fs, Fmeans, Fvars = np.tile(Xh[None], [S, 1, 1]), [], [], []
-            for layer, z in zip(self.layers, zs or [None] * len(self.layers)):
-                F, Fmean, Fvar = layer.sample_from_conditional(F, z=z, full_cov=True)
-                Fs.append(F); Fmeans.append(Fmean); Fvars.append(Fvar)
-            return Fs, Fmeans, Fvars
+            return propagate_layers(self.layers, np.tile(Xh[None], [S, 1, 1]), zs, full_cov=True)
         ctx = self._context()
         N, L = Xh.shape[0], len(self.layers)
         widths = [(layer.num_outputs, int(layer.input_prop_dim or 0)) for layer in self.layers]
-        Fs = [np.empty((S, N, p + DO)) for DO, p in widths]
-        Fmeans, Fvars = [np.empty((S, N, DO)) for DO, p in widths], [np.empty((S, N, DO)) for DO, p in widths]
+        Fs, Fmeans, Fvars = ([np.empty((S, N, DO)) for DO, p in widths] for _ in range(3))
         for a, b, zb in self._batches(Xh, S, zs):
             r = self.propagate_device(Xh[a:b], S, zs=zb)
             ctx.sync()
             for l, (DO, p) in enumerate(widths):
-                Fs[l][:, a:b] = r["F"][l].cpu().numpy().reshape(S, b - a, p + DO)
+                Fs[l][:, a:b] = r["F"][l].cpu().numpy().reshape(S, b - a, p + DO)[:, :, p:]     # its propagated columns come back below
                 Fmeans[l][:, a:b] = r["mean"][l].cpu().numpy().reshape(S, b - a, DO)
                 Fvars[l][:, a:b] = r["var"][l].cpu().numpy().reshape(S, b - a, 1)
-        Fin = np.tile(Xh[None], [S, 1, 1])
-        for l, (DO, p) in enumerate(widths):                       # layers.py:105-117: the means get the same copies, the variances zeros
-            if p:
-                Fmeans[l] = np.concatenate([Fin[:, :, :p], Fmeans[l]], 2)
-                Fvars[l] = np.concatenate([np.zeros((S, N, p)), Fvars[l]], 2)
-            Fin = Fs[l]
+        prepend_input_prop(np.tile(Xh[None], [S, 1, 1]), self.layers, Fs, Fmeans, Fvars)       # layers.py:105-117
         return Fs, Fmeans, Fvars
 
     def _build_predict(self, X, full_cov=False, S=1, zs=None):
@@ -742,11 +633,7 @@ class DGP_SGPMC(DGP_Base):
         out = ctx.empty(4)
         grad = None
         if with_grad:
-            count = 1
-            for layer in self.layers:
-                M, D = layer.feature.Z.shape
-                count += M * D + M * layer.num_outputs + 2 + (D if split_kernel_ard(layer.kern) else 1)
-            grad = ctx.empty(count)
+            grad = ctx.empty(self._gradient_layout()[2])
         zarr = self._device_zs(ctx, zs, n, S, keep)
         _lib.check(ctx.lib.dsdgp_stack_logdensity(ctx.handle, C.byref(d), C.c_void_p(Xd.data_ptr()), C.c_void_p(Yd.data_ptr()), n, S, zarr,
                                                   C.c_uint64(self._eval_seed() if seed is None else int(seed)),
@@ -774,19 +661,18 @@ class DGP_SGPMC(DGP_Base):
     def compute_log_density(self, X=None, Y=None, zs=None):
         return float(self._out4(X, Y, zs)[0])
 
+    def _gradient_layout(self):
+        return stack_gradient_layout([(*layer.feature.Z.shape, layer.num_outputs, bool(split_kernel(layer.kern)[0].ARD))
+                                      for layer in self.layers])
+
     def split_gradient(self, grad):
         """the flat gradient of the library (a numpy array) as [(Parameter, gradient), ...] in the order of parameter_list()"""
-        blocks, at = [], 0
-        for layer in self.layers:
-            M, D = layer.feature.Z.shape
-            DO, nls = layer.num_outputs, (D if split_kernel_ard(layer.kern) else 1)
-            b = dict(Z=grad[at:at + M * D].reshape(M, D), q_mu=grad[at + M * D:at + M * D + M * DO].reshape(M, DO))
-            at += M * D + M * DO
-            b.update(variance=grad[at:at + 1], lengthscales=grad[at + 1:at + 1 + nls], white_variance=grad[at + 1 + nls:at + 2 + nls])
-            at += 2 + nls
-            blocks.append(b)
-        return [(p, np.array((blocks[l][k] if l is not None else grad[at:at + 1]), dtype=np.float64).reshape(p.shape))
-                for p, l, k in self.parameter_list()]
+        blocks, lik, _ = self._gradient_layout()
+        out = []
+        for p, l, k in self.parameter_list():
+            at, shape = blocks[l][k] if l is not None else (lik, (1,))
+            out.append((p, np.array(grad[at:at + int(np.prod(shape))], dtype=np.float64).reshape(p.shape)))
+        return out
 
     def compute_log_density_gradients(self, X=None, Y=None, zs=None):
         """(log density, [(Parameter, gradient), ...]) of one evaluation: the next minibatch (or X, Y), S = num_samples draws"""
@@ -817,38 +703,36 @@ class DGP_SGPMC(DGP_Base):
             vars_.append(r["var"][-1][:, None].expand(-1, DY))
         return ctx.torch.cat(means, 0).contiguous(), ctx.torch.cat(vars_, 0).contiguous(), len(means) * int(S)
 
-    def _score_batches(self, Xs, Ys, S, run, call):
-        """call(a, b, mean, var, Yb, components) over the row batches of Xs that fit the scratch, then one synchronisation"""
-        ctx = self._context()
-        Xd = ctx.as_device(Xs)
-        Yd = None if Ys is None else ctx.as_device(Ys)
+    def _score_batches(self, ctx, Xd, Yd, S, batch_size=None, run=None):
+        """(a, b, launch) over the row batches of Xd that fit the scratch, then one synchronisation: DGP_Base's scoring bodies on
+        components_device.  launch(what, ...) is the batch's one mixture call _MIXTURE[what] on the T S components of its rows."""
+        # (kind, p0, p1) are read before a state of `run` is assigned: the states may move the likelihood's parameter
+        fixed = dict(lik=likelihood_args(self.likelihood.likelihood), D=self.layers[-1].num_outputs)
         N = Xd.shape[0]
-        if N < 1 or (Yd is not None and Yd.shape[0] != N):
-            raise ValueError(f"Xs has {N} rows, Ys {None if Yd is None else Yd.shape[0]}")
-        nb = self._row_batch(ctx, N, int(S))
+        nb = self._row_batch(ctx, N, S)
         keep = []
         for a in range(0, N, nb):
             b = min(a + nb, N)
             mean, var, comps = self.components_device(Xd[a:b], S, run)
-            Yb = None if Yd is None else Yd[a:b].contiguous()
-            keep.append((mean, var, Yb, call(a, b, mean, var, Yb, comps)))
+            m = dict(fixed, mean=mean, var=var, Y=None if Yd is None else Yd[a:b].contiguous(), n=b - a, comps=comps)
+            keep.append(m)
+            yield a, b, lambda what, *args, **kw: _MIXTURE[what](ctx, m, *args, **kw)
         ctx.sync()
 
     def predict_y_samples(self, Xs, S, run):
         """(mean, variance) of y for every component: (T S, N*, D_Y) arrays, the likelihood's predict_mean_and_var of each kept state's
         S components (dgp.py:116-119)"""
         ctx = self._context()
-        outs = []
-
-        def call(a, b, mean, var, Yb, comps):
-            outs.append((a, b, mean, var, comps))
-        self._score_batches(Xs, None, S, run, call)
-        N, DY = ctx.as_device(Xs).shape[0], self.layers[-1].num_outputs
-        comps = outs[0][4]
+        Xd = ctx.as_device(Xs)
+        N, DY = Xd.shape[0], self.layers[-1].num_outputs
+        if N < 1:
+            raise ValueError(f"Xs has {N} rows, Ys None")
+        outs = [(a, b, launch("components")) for a, b, launch in self._score_batches(ctx, Xd, None, int(S), run=run)]
+        comps = outs[0][2]["comps"]
         m, v = np.empty((comps, N, DY)), np.empty((comps, N, DY))
-        for a, b, mean, var, _ in outs:
-            pm, pv = self.likelihood.predict_mean_and_var(mean.cpu().numpy().reshape(comps, b - a, DY), var.cpu().numpy().reshape(comps, b - a, DY))
-            m[:, a:b], v[:, a:b] = pm, pv
+        for a, b, r in outs:
+            m[:, a:b], v[:, a:b] = self.likelihood.predict_mean_and_var(r["mean"].cpu().numpy().reshape(comps, b - a, DY),
+                                                                        r["var"].cpu().numpy().reshape(comps, b - a, DY))
         return m, v
 
     def predict_density(self, Xnew, Ynew, num_samples, run=None):
@@ -867,100 +751,61 @@ class DGP_SGPMC(DGP_Base):
         """Held-out scores of the mixture of the T S components of `run` (None: the S of the current state) by dsdgp_eval_mixture: the
         dict of DGP_Base.evaluate — `rmse` / `rmse_per_output` (MultiClass: `error_rate`), `log_density`, `n`, and with return_rows
         `rows` (N*, D, 3)."""
-        from .gpflow_compat import MultiClass, likelihood_args
-        ctx = self._context()
-        lik = self.likelihood.likelihood
-        if not hasattr(Ys, "data_ptr"):
-            self.likelihood.check_targets(Ys)
-        gaussian = not self.likelihood.needs_broadcasting
-        Y_std = float(Y_std)
-        if not Y_std > 0.0 or (not gaussian and Y_std != 1.0):
-            raise ValueError("Y_std rescales a Gaussian density only (and must be positive)")
-        kind, p0, p1 = likelihood_args(lik)
-        D = self.layers[-1].num_outputs
-        N = Xs.shape[0]
-        acc = ctx.empty(3, D)
-        rows = ctx.empty(N, D, 3) if return_rows else None
-        self._score_batches(Xs, Ys, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_eval_mixture(
-            ctx.handle, kind, p0, p1, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(Yb.data_ptr()), b - a, comps, D,
-            C.c_void_p(rows[a:b].data_ptr() if return_rows else 0), C.c_void_p(acc.data_ptr()), int(a > 0))))
-        sums = acc.cpu().numpy()
-        out = {"n": N}
-        if isinstance(lik, MultiClass):
-            cnt = float(sums[2, 0])
-            out["error_rate"], out["log_density"] = float(sums[0, 0]) / cnt, float(sums[1, 0]) / cnt
-        else:
-            cnt = float(sums[2].sum())
-            out["rmse"] = Y_std * float(np.sqrt(sums[0].sum() / cnt))
-            out["rmse_per_output"] = Y_std * np.sqrt(sums[0] / sums[2])
-            out["log_density"] = float(sums[1].sum()) / cnt - (np.log(Y_std) if gaussian else 0.0)
-        if return_rows:
-            out["rows"] = rows.cpu().numpy()
-        return out
-
-    def _noise(self, what, level):
-        if level not in ("f", "y"):
-            raise ValueError(f"level must be \"f\" or \"y\", not {level!r}")
-        if level == "y" and self.likelihood.needs_broadcasting:
-            raise NotImplementedError(f"{what}: the predictive y of {type(self.likelihood.likelihood).__name__} is not a mixture of "
-                                      "Gaussians; only level=\"f\" (the latent function) is covered")
-        return float(self.likelihood.likelihood.variance.value) if level == "y" else 0.0
+        return self._evaluate(Xs, Ys, S, Y_std, return_rows, run=run)
 
     def predict_quantiles(self, Xnew, S, probs=(0.025, 0.5, 0.975), level="y", run=None, Y_std=1.0, Y_mean=0.0):
         """Quantiles of the predictive mixture of the T S Gaussians of `run` (dsdgp_mixture_quantiles): (N*, D, P), as
         DGP_Base.predict_quantiles"""
-        noise = self._noise("predict_quantiles", level)
-        S, _, Y_std, probs = self._calibration_args("predict_quantiles", Xnew, S, probs, 1, Y_std, None, False)
-        ctx = self._context()
-        N, D, P = Xnew.shape[0], self.layers[-1].num_outputs, probs.size
-        q = ctx.empty(N, D, P)
-        self._score_batches(Xnew, None, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_mixture_quantiles(
-            ctx.handle, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), noise, b - a, comps, D,
-            probs.ctypes.data_as(_lib.c_double_p), P, C.c_void_p(q[a:b].data_ptr()))))
-        return float(Y_mean) + Y_std * q.cpu().numpy()
+        return self._predict_quantiles(Xnew, S, probs, level, Y_std, Y_mean, run=run)
 
     def calibration(self, Xs, Ys, S, probs=(0.025, 0.05, 0.25, 0.5, 0.75, 0.95, 0.975), run=None, Y_std=1.0, return_rows=False):
         """Calibration scores of held-out targets under the mixture of the T S Gaussians of `run` (dsdgp_mixture_calibration; Gaussian
         likelihood): the dict of DGP_Base.calibration"""
-        from .dgp import calibration_scores
-        noise = self._noise("calibration", "y")
-        S, _, Y_std, probs = self._calibration_args("calibration", Xs, S, probs, 1, Y_std, None, True, Y=Ys)
-        ctx = self._context()
-        N, D, P = Xs.shape[0], self.layers[-1].num_outputs, probs.size
-        acc = ctx.empty(2 + P, D)
-        rows = ctx.empty(N, D, 2) if return_rows else None
-        self._score_batches(Xs, Ys, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_mixture_calibration(
-            ctx.handle, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), noise, C.c_void_p(Yb.data_ptr()), b - a, comps, D,
-            probs.ctypes.data_as(_lib.c_double_p), P, C.c_void_p(rows[a:b].data_ptr() if return_rows else 0), C.c_void_p(acc.data_ptr()),
-            int(a > 0))))
-        out = calibration_scores(acc.cpu().numpy(), probs, Y_std)
-        out["n"] = N
-        if return_rows:
-            out["rows"] = rows.cpu().numpy()
-        return out
+        return self._calibration(Xs, Ys, S, probs, Y_std, return_rows, run=run)
 
     def classification_report(self, Xs, Ys, S, bins=10, run=None, return_rows=False):
         """The classification report of the mixture class probabilities over the T S components of `run`
         (dsdgp_mixture_classification; MultiClass or Bernoulli): the dict of DGP_Base.classification_report"""
-        from .dgp import classification_scores
-        kind, Cn, ND, S, bins, _ = self._classification_args(Xs, Ys, S, bins, 1, None)
-        ctx = self._context()
-        N, D = Xs.shape[0], self.layers[-1].num_outputs
-        acc = ctx.empty(4 + 3 * bins + Cn + Cn * Cn, ND)
-        probs = ctx.empty(N, D) if return_rows else None
-        rows = ctx.empty(N, ND, 4) if return_rows else None
-        self._score_batches(Xs, Ys, S, run, lambda a, b, mean, var, Yb, comps: _lib.check(ctx.lib.dsdgp_mixture_classification(
-            ctx.handle, kind, C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), C.c_void_p(Yb.data_ptr()), b - a, comps, D, bins,
-            C.c_void_p(probs[a:b].data_ptr() if return_rows else 0), C.c_void_p(rows[a:b].data_ptr() if return_rows else 0),
-            C.c_void_p(acc.data_ptr()), int(a > 0))))
-        out = classification_scores(acc.cpu().numpy(), bins, Cn)
-        out["n"] = N
-        if return_rows:
-            out["probs"], out["rows"] = probs.cpu().numpy(), rows.cpu().numpy()
-        return out
+        return self._classification_report(Xs, Ys, S, bins, return_rows, run=run)
 
 
-def split_kernel_ard(kern):
-    """whether the stationary part of kern has one lengthscale per input"""
-    from .gpflow_compat import split_kernel
-    return bool(split_kernel(kern)[0].ARD)
+# What one batch of DGP_SGPMC's scoring launches for a reduction, with the trailing arguments of Engine.<what>_batch.  m: the batch's
+# device means and variances (comps n, D), its targets, and the likelihood's (kind, p0, p1): p0 is the Gaussian's noise variance, which
+# level "y" of the quantiles and the calibration (both refused for any other likelihood) add to every component.
+def _mixture_evaluate(ctx, m, acc, accumulate, rows=None):
+    _lib.check(ctx.lib.dsdgp_eval_mixture(ctx.handle, *m["lik"], ptr(m["mean"]), ptr(m["var"]), ptr(m["Y"]), m["n"], m["comps"], m["D"],
+                                          ptr(rows), ptr(acc), int(accumulate)))
+
+
+def _mixture_quantiles(ctx, m, probs, q, level=1):
+    _lib.check(ctx.lib.dsdgp_mixture_quantiles(ctx.handle, ptr(m["mean"]), ptr(m["var"]), m["lik"][1] if level else 0.0, m["n"], m["comps"],
+                                               m["D"], probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(q)))
+
+
+def _mixture_calibration(ctx, m, probs, acc, accumulate, rows=None):
+    _lib.check(ctx.lib.dsdgp_mixture_calibration(ctx.handle, ptr(m["mean"]), ptr(m["var"]), m["lik"][1], ptr(m["Y"]), m["n"], m["comps"],
+                                                 m["D"], probs.ctypes.data_as(_lib.c_double_p), probs.size, ptr(rows), ptr(acc),
+                                                 int(accumulate)))
+
+
+def _mixture_classification(ctx, m, bins, acc, accumulate, probs=None, rows=None):
+    _lib.check(ctx.lib.dsdgp_mixture_classification(ctx.handle, m["lik"][0], ptr(m["mean"]), ptr(m["var"]), ptr(m["Y"]), m["n"], m["comps"],
+                                                    m["D"], bins, ptr(probs), ptr(rows), ptr(acc), int(accumulate)))
+
+
+_MIXTURE = {"evaluate": _mixture_evaluate, "quantiles": _mixture_quantiles, "calibration": _mixture_calibration,
+            "classification": _mixture_classification, "components": lambda ctx, m: m}
+
+
+def stack_gradient_layout(shapes):
+    """The flat gradient of dsdgp_stack_logdensity, stated once: per layer (M, D, DO, ard) the blocks `Z` (M D), `q_mu` (M DO),
+    `variance`, `lengthscales` (D with ARD, else one), `white_variance`, then one entry for the likelihood
+    -> ([{key: (offset, shape)} per layer], the likelihood's offset, the total)."""
+    layers, at = [], 0
+    for M, D, DO, ard in shapes:
+        blocks = {}
+        for key, shape in (("Z", (M, D)), ("q_mu", (M, DO)), ("variance", (1,)), ("lengthscales", (D if ard else 1,)), ("white_variance", (1,))):
+            blocks[key] = (at, shape)
+            at += int(np.prod(shape))
+        layers.append(blocks)
+    return layers, at, at + 1

@@ -2,8 +2,65 @@
 (demos/demo_regression_UCI.ipynb:324).  The step itself (gradient + Adam update) runs in libdsdgp."""
 import numpy as np
 
+from .gpflow_compat import positive_backward, positive_forward, positive_slope
+
 _NO_SAMPLED_GRADIENT = ("{} takes no minibatch step of a sampled bound: there is no reverse pass of one to step along (a DGP_Collapsed "
                         "trains on its own bound: ScipyOptimizer(inner=True), CollapsedAdamOptimizer)")
+
+
+class Variables:
+    """A list of Parameters seen as unconstrained variables, in list order: a positive Parameter theta = softplus(x) + 1e-6
+    (gpflow_compat) moves as x with d theta / dx = 1 - exp(-(theta - 1e-6)), any other as itself.  masks: per Parameter a boolean array
+    of the entries that are variables (the lower triangle of a `tril` q_sqrt) or None for all of them; a masked Parameter's values
+    travel as the 1-d array of its masked entries, and the others are set to zero.  who: the trainer named in the errors."""
+
+    def __init__(self, params, masks=None, who="Variables"):
+        self.params, self.who = list(params), who
+        self.masks = list(masks) if masks is not None else [None] * len(self.params)
+
+    def values(self):
+        """the current unconstrained values, one array per Parameter"""
+        xs = [positive_backward(p.value) if p.transform == "positive" else p.value for p in self.params]
+        return [x if m is None else x[m] for m, x in zip(self.masks, xs)]
+
+    def constrained(self, xs):
+        """the Parameters' values at the unconstrained values xs (fresh arrays)"""
+        out = []
+        for p, m, x in zip(self.params, self.masks, xs):
+            if m is not None:
+                x, masked = np.zeros(p.shape), x
+                x[m] = masked
+            out.append(positive_forward(x) if p.transform == "positive" else np.array(x, dtype=np.float64))
+        return out
+
+    def assign(self, xs):
+        for p, v in zip(self.params, self.constrained(xs)):
+            p.assign(v)
+
+    def chain(self, pairs):
+        """the gradients [(Parameter, dF / d theta), ...] as dF / dx per variable, at the Parameters' current values"""
+        grads = {id(p): g for p, g in pairs}
+        out = []
+        for p, m in zip(self.params, self.masks):
+            if id(p) not in grads:
+                raise ValueError(f"{self.who}: a Parameter of var_list has no gradient of the model's log density")
+            g = np.asarray(grads[id(p)], dtype=np.float64).reshape(p.shape)
+            g = g * positive_slope(p.value) if p.transform == "positive" else g
+            out.append(g if m is None else g[m])
+        return out
+
+    @staticmethod
+    def flat(xs):
+        return np.concatenate([np.ravel(x) for x in xs])
+
+    def cut(self, flat):
+        """a flat vector (numpy or a device tensor) in variable order as one piece per Parameter"""
+        out, at = [], 0
+        for p, m in zip(self.params, self.masks):
+            k = int(np.prod(p.shape) if m is None else np.count_nonzero(m))
+            out.append(flat[at:at + k].reshape(p.shape) if m is None else flat[at:at + k])
+            at += k
+        return out
 
 
 class AdamOptimizer:
@@ -75,17 +132,15 @@ class ScipyOptimizer:
         """returns scipy's OptimizeResult (`fun` = minus the bound); zs: fixed draws for the inner layers, as compute_log_likelihood.
         inner=True: the search is over the trainable parameters of ALL layers — the four above, then `DGP_Collapsed.inner_parameters()`
         — with the gradients of `compute_log_likelihood_gradients(inner=True)`; of a `q_sqrt` only the lower triangle is a variable."""
-        import numpy as np
         import scipy.optimize
         from ._lib import CholeskyError
-        from .gpflow_compat import positive_backward, positive_forward, positive_slope, split_kernel
         from .model_zoo import DGP_Collapsed
         if not isinstance(model, DGP_Collapsed):
             raise NotImplementedError(f"ScipyOptimizer fits the collapsed last layer of a DGP_Collapsed; {type(model).__name__} is "
                                       "trained by AdamOptimizer / NatGradOptimizer")
         from .model_zoo import DGP_Heinonen
-        train, free = _collapsed_variables(model, inner)
-        if not train:
+        variables = Variables(*_collapsed_variables(model, inner), who="ScipyOptimizer")
+        if not variables.params:
             raise ValueError("ScipyOptimizer: none of the collapsed layer's parameters is trainable" if not inner else
                              "ScipyOptimizer: none of the model's parameters is trainable")
         kw = {"inner": True} if inner else {}
@@ -95,22 +150,10 @@ class ScipyOptimizer:
         else:
             gradients = lambda: model.compute_log_likelihood_gradients(zs=zs, **kw)
 
-        def pack(values):
-            return np.concatenate([np.asarray(v, dtype=np.float64)[m] for v, m in zip(values, free)])
-
-        def assign(x):
-            at = 0
-            for p, m in zip(train, free):
-                k = int(np.count_nonzero(m))
-                v = np.zeros(p.shape)
-                v[m] = x[at:at + k]
-                p.assign(positive_forward(v) if p.transform == "positive" else v)
-                at += k
-
         last = [None]                                 # the last objective that succeeded
 
         def objective(x):
-            assign(x)
+            variables.assign(variables.cut(x))
             try:
                 bound, pairs, _ = gradients()
             except CholeskyError:
@@ -118,28 +161,20 @@ class ScipyOptimizer:
                     raise
                 return last[0] + 10.0 * (abs(last[0]) + 1.0), np.zeros_like(x)
             last[0] = -float(bound)
-            grads = {id(p): g for p, g in pairs}
-            out = []
-            for p in train:
-                g = grads[id(p)]
-                if p.transform == "positive":
-                    g = g * positive_slope(p.value)
-                out.append(-g)
-            return -float(bound), pack(out)
+            return -float(bound), -variables.flat(variables.chain(pairs))
 
-        x0 = pack([positive_backward(p.value) if p.transform == "positive" else p.value for p in train])
+        x0 = variables.flat(variables.values())
         options = dict(self.options)
         options["maxiter"] = int(maxiter)
         res = scipy.optimize.minimize(objective, x0, jac=True, method=self.method, tol=self.tol, options=options)
-        assign(res.x)
+        variables.assign(variables.cut(res.x))
         return res
 
 
 def _collapsed_variables(model, inner):
     """(the trainable Parameters a collapsed model is fitted over, a boolean mask per Parameter of the entries that are variables):
     the collapsed layer's `feature.Z`, kernel `variance` and `lengthscales` and the likelihood's `variance`; with `inner` the inner
-    layers' as well.  Every entry is a variable, except above the diagonal of a `q_sqrt` (transform "tril")."""
-    import numpy as np
+    layers' as well.  Every entry is a variable, except above the diagonal of a `q_sqrt` (transform "tril").  What training.Variables takes."""
     from .model_zoo import DGP_Heinonen
     # DGP_Collapsed.top_parameters: an SGPR_Layer's four as above; a GPR_Layer has no inducing inputs and may have a White variance
     params = [p for p, _ in model.top_parameters()]
@@ -172,8 +207,6 @@ class CollapsedAdamOptimizer:
 
     def minimize(self, model, maxiter=1000, zs=None):
         """returns the bound at the last evaluated point (before the last step); zs as for compute_log_likelihood"""
-        import numpy as np
-        from .gpflow_compat import positive_backward, positive_forward, positive_slope
         from .model_zoo import DGP_Collapsed, DGP_Heinonen
         if not isinstance(model, DGP_Collapsed):
             raise NotImplementedError(f"CollapsedAdamOptimizer trains a DGP_Collapsed; {type(model).__name__} is trained by AdamOptimizer")
@@ -183,7 +216,7 @@ class CollapsedAdamOptimizer:
         if isinstance(model, DGP_Heinonen):
             raise NotImplementedError("CollapsedAdamOptimizer steps the inner layers through their engine, which a DGP_Heinonen does not "
                                       "have: sample it with HMC or fit it with ScipyOptimizer (MAP)")
-        top4, _ = _collapsed_variables(model, False)
+        top4 = Variables(_collapsed_variables(model, False)[0], who="CollapsedAdamOptimizer")
         deep = len(model.layers) > 1
         # moments and step count of the four live with the model, as the engine's do with the engine: a second call goes on (TF's slots)
         state = getattr(model, "_collapsed_adam", None)
@@ -193,19 +226,18 @@ class CollapsedAdamOptimizer:
         bound = None
         for _ in range(int(maxiter)):
             bound, pairs, _adj = model.compute_log_likelihood_gradients(zs=zs, inner=True)
-            grads = {id(p): g for p, g in pairs}
             if deep:
                 model.inner_engine().adam_step(self.lr, self.b1, self.b2, self.eps)
             state["t"] += 1
             lr_t = self.lr * np.sqrt(1.0 - self.b2 ** state["t"]) / (1.0 - self.b1 ** state["t"])
-            for p in top4:
-                pos = p.transform == "positive"
-                g = -grads[id(p)] * (positive_slope(p.value) if pos else 1.0)          # d(-bound)/dx
+            xs = []
+            for p, g, x in zip(top4.params, top4.chain(pairs), top4.values()):
+                g = -g                                                                  # d(-bound)/dx
                 m, v = state.setdefault(id(p), (np.zeros(p.shape), np.zeros(p.shape)))
                 m[...] = self.b1 * m + (1.0 - self.b1) * g
                 v[...] = self.b2 * v + (1.0 - self.b2) * g * g
-                x = (positive_backward(p.value) if pos else p.value) - lr_t * m / (np.sqrt(v) + self.eps)
-                p.assign(positive_forward(x) if pos else x)
+                xs.append(x - lr_t * m / (np.sqrt(v) + self.eps))
+            top4.assign(xs)
         if deep and bound is not None:
             model.inner_engine().prepare()      # the last host step reaches the device; a failed factorisation there is raised here
         return bound
@@ -229,43 +261,21 @@ class HMC:
         var_list = [model.layers[0].q_mu] if var_list is None else list(var_list)
         if not var_list:
             raise ValueError("HMC: var_list is empty")
-        return var_list
+        return Variables(var_list, who="HMC")
 
     @staticmethod
-    def _ctx(model):
-        return model._context()
-
-    @classmethod
-    def _position(cls, model, var_list):
-        """the unconstrained values of var_list as device tensors"""
-        from .gpflow_compat import positive_backward
-        ctx = cls._ctx(model)
-        return [ctx.to_device(positive_backward(p.value) if p.transform == "positive" else p.value) for p in var_list]
+    def _assign(variables, q):
+        variables.assign([x.cpu().numpy() for x in q])
 
     @staticmethod
-    def _assign(var_list, q):
-        from .gpflow_compat import positive_forward
-        for p, x in zip(var_list, q):
-            x = x.cpu().numpy()
-            p.assign(positive_forward(x) if p.transform == "positive" else x)
-
-    @classmethod
-    def _logp_and_grad(cls, model, var_list):
+    def _logp_and_grad(model, variables):
         """(log density, its gradient in the unconstrained variables as device tensors) at the model's current parameters"""
-        from .gpflow_compat import positive_slope
-        ctx = cls._ctx(model)
+        ctx = model._context()
         logp, pairs = model.compute_log_density_gradients()
-        grads = {id(p): g for p, g in pairs}
-        out = []
-        for p in var_list:
-            if id(p) not in grads:
-                raise ValueError("HMC: a Parameter of var_list has no gradient of the model's log density")
-            g = np.asarray(grads[id(p)], dtype=np.float64).reshape(p.shape)
-            out.append(ctx.to_device(g * positive_slope(p.value) if p.transform == "positive" else g))
-        return float(logp), out
+        return float(logp), [ctx.to_device(g) for g in variables.chain(pairs)]
 
     @classmethod
-    def _leapfrog(cls, model, var_list, q, p, grad, epsilon, steps):
+    def _leapfrog(cls, model, variables, q, p, grad, epsilon, steps):
         """`steps` leapfrog steps from (q, p) with the gradient `grad` at q -> (q, p, log density at q, gradient at q); q, p: lists of
         device tensors, not modified"""
         eps = float(epsilon)
@@ -275,8 +285,8 @@ class HMC:
         for s in range(int(steps)):
             for x, m in zip(q, p):
                 x += eps * m
-            cls._assign(var_list, q)
-            logp, grad = cls._logp_and_grad(model, var_list)
+            cls._assign(variables, q)
+            logp, grad = cls._logp_and_grad(model, variables)
             w = eps if s + 1 < int(steps) else 0.5 * eps
             p = [m + w * g for m, g in zip(p, grad)]
         return q, p, logp, grad
@@ -286,16 +296,17 @@ class HMC:
         """`steps` leapfrog steps of size epsilon from position q and momentum p (arrays shaped like the variables — unconstrained
         values — or lists of them, one per entry of var_list) -> (q, p, log density at the new q) as numpy arrays (lists if lists were
         given).  The model's Parameters are left at the new position."""
-        var_list = cls._variables(model, var_list)
-        ctx = cls._ctx(model)
+        variables = cls._variables(model, var_list)
+        ctx = model._context()
         single = not isinstance(q, (list, tuple))
         qd = [ctx.to_device(x) for x in ([q] if single else q)]
         pd = [ctx.to_device(x) for x in ([p] if single else p)]
-        if len(qd) != len(var_list) or any(tuple(x.shape) != v.shape or tuple(m.shape) != v.shape for x, m, v in zip(qd, pd, var_list)):
+        if len(qd) != len(variables.params) or any(tuple(x.shape) != v.shape or tuple(m.shape) != v.shape
+                                                   for x, m, v in zip(qd, pd, variables.params)):
             raise ValueError("HMC.leapfrog: q and p must have the shapes of var_list")
-        cls._assign(var_list, qd)
-        _, grad = cls._logp_and_grad(model, var_list)
-        qd, pd, logp, _ = cls._leapfrog(model, var_list, qd, pd, grad, epsilon, steps)
+        cls._assign(variables, qd)
+        _, grad = cls._logp_and_grad(model, variables)
+        qd, pd, logp, _ = cls._leapfrog(model, variables, qd, pd, grad, epsilon, steps)
         qn, pn = [x.cpu().numpy() for x in qd], [m.cpu().numpy() for m in pd]
         return (qn[0], pn[0], logp) if single else (qn, pn, logp)
 
@@ -304,39 +315,34 @@ class HMC:
         """the momenta of one iteration: dsdgp_randn(seed, stream = iteration), cut in var_list order (device tensors)"""
         import ctypes as C
         from . import _lib
-        ctx = cls._ctx(model)
-        sizes = [int(np.prod(p.shape)) for p in var_list]
-        flat = ctx.empty(sum(sizes))
-        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(int(seed)), C.c_uint64(int(iteration)), sum(sizes), C.c_void_p(flat.data_ptr())))
-        out, at = [], 0
-        for p, k in zip(var_list, sizes):
-            out.append(flat[at:at + k].reshape(p.shape))
-            at += k
-        return out
+        ctx = model._context()
+        flat = ctx.empty(sum(int(np.prod(p.shape)) for p in var_list))
+        _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(int(seed)), C.c_uint64(int(iteration)), flat.numel(), C.c_void_p(flat.data_ptr())))
+        return Variables(var_list).cut(flat)
 
     def sample(self, model, num_samples, epsilon, lmin=1, lmax=1, thin=1, burn=0, var_list=None, seed=0):
         """-> dict(samples={name: (num_samples, *shape)} of the CONSTRAINED values — names "q_mu", then "var<i>" by position in var_list
         for any other Parameter —, logprobs (num_samples,), accepted (one flag per iteration, burn-in included), accept_rate).
         burn + num_samples thin iterations; every thin-th state after the burn-in is kept.  The model is left at the last state."""
         from ._lib import CholeskyError
-        from .gpflow_compat import positive_forward
         from .model_zoo import DGP_Heinonen
         if not isinstance(model, DGP_Heinonen) and not getattr(model, "_sgpmc", False):
             raise NotImplementedError(f"HMC samples a DGP_Heinonen; {type(model).__name__} has no log density to sample from")
         if int(num_samples) < 1 or int(thin) < 1 or int(burn) < 0 or int(lmin) < 1 or int(lmax) < int(lmin) or not float(epsilon) > 0.0:
             raise ValueError("HMC.sample: num_samples, thin >= 1, burn >= 0, 1 <= lmin <= lmax, epsilon > 0")
-        var_list = self._variables(model, var_list)
+        variables = self._variables(model, var_list)
+        var_list = variables.params
         names = ["q_mu" if p is model.layers[0].q_mu else f"var{i}" for i, p in enumerate(var_list)]
         rng = np.random.default_rng(seed)
-        q = self._position(model, var_list)
-        logp, grad = self._logp_and_grad(model, var_list)
+        q = [model._context().to_device(x) for x in variables.values()]
+        logp, grad = self._logp_and_grad(model, variables)
         kept, logps, accepted = {n: [] for n in names}, [], []
         for it in range(int(burn) + int(num_samples) * int(thin)):
             steps, u = int(rng.integers(int(lmin), int(lmax) + 1)), float(rng.uniform())
             p0 = self.momenta(model, var_list, seed, it)
             H0 = -logp + 0.5 * sum(float((m * m).sum()) for m in p0)
             try:
-                q1, p1, logp1, grad1 = self._leapfrog(model, var_list, q, p0, grad, epsilon, steps)
+                q1, p1, logp1, grad1 = self._leapfrog(model, variables, q, p0, grad, epsilon, steps)
                 H1 = -logp1 + 0.5 * sum(float((m * m).sum()) for m in p1)
                 ok = bool(np.log(u) < H0 - H1)
             except CholeskyError:
@@ -345,11 +351,10 @@ class HMC:
                 q, logp, grad = q1, logp1, grad1
             accepted.append(ok)
             if it >= int(burn) and (it - int(burn) + 1) % int(thin) == 0:
-                for n, p, x in zip(names, var_list, q):
-                    x = x.cpu().numpy()
-                    kept[n].append(positive_forward(x) if p.transform == "positive" else x.copy())
+                for n, x in zip(names, variables.constrained([x.cpu().numpy() for x in q])):
+                    kept[n].append(x)
                 logps.append(logp)
-        self._assign(var_list, q)
+        self._assign(variables, q)
         accepted = np.array(accepted, dtype=bool)
         return dict(samples={n: np.stack(v) for n, v in kept.items()}, logprobs=np.array(logps), accepted=accepted,
                     accept_rate=float(np.mean(accepted)))
@@ -387,34 +392,11 @@ class SGHMC:
         return ["q_mu%d" % qs[id(p)] if id(p) in qs else f"var{i}" for i, p in enumerate(var_list)]
 
     @staticmethod
-    def _split(var_list, flat):
-        out, at = [], 0
-        for p in var_list:
-            k = int(np.prod(p.shape))
-            out.append(flat[at:at + k].reshape(p.shape))
-            at += k
-        return out
-
-    @classmethod
-    def _assign(cls, var_list, theta):
-        from .gpflow_compat import positive_forward
-        for p, x in zip(var_list, cls._split(var_list, theta.cpu().numpy())):
-            p.assign(positive_forward(x) if p.transform == "positive" else x)
-
-    @staticmethod
-    def _gradient(model, var_list, ctx):
+    def _gradient(model, variables, ctx):
         """(log density, its gradient in the unconstrained variables as one flat device tensor) at the model's Parameters, on the next
         minibatch"""
-        from .gpflow_compat import positive_slope
         logp, pairs = model.compute_log_density_gradients()
-        grads = {id(p): g for p, g in pairs}
-        out = []
-        for p in var_list:
-            if id(p) not in grads:
-                raise ValueError("SGHMC: a Parameter of var_list has no gradient of the model's log density")
-            g = np.asarray(grads[id(p)], dtype=np.float64).reshape(p.shape)
-            out.append((g * positive_slope(p.value) if p.transform == "positive" else g).ravel())
-        return logp, ctx.to_device(np.concatenate(out))
+        return logp, ctx.to_device(variables.flat(variables.chain(pairs)))
 
     def step(self, ctx, theta, v, g, xi):
         """one dsdgp_sghmc_step on flat device tensors, in place"""
@@ -430,7 +412,6 @@ class SGHMC:
         every thin-th state after the burn-in is kept.  The model is left at the last state."""
         import ctypes as C
         from . import _lib
-        from .gpflow_compat import positive_backward, positive_forward
         self._check(model)
         if int(num_samples) < 1 or int(thin) < 1 or int(burn) < 0:
             raise ValueError("SGHMC.sample: num_samples, thin >= 1, burn >= 0")
@@ -439,26 +420,27 @@ class SGHMC:
             raise ValueError("SGHMC: var_list is empty")
         names = self._names(model, var_list)
         ctx = model._context()
-        theta = ctx.to_device(np.concatenate([np.ravel(positive_backward(p.value) if p.transform == "positive" else p.value)
-                                              for p in var_list]))
+        variables = Variables(var_list, who="SGHMC")
+        assign = lambda theta: variables.assign(variables.cut(theta.cpu().numpy()))
+        theta = ctx.to_device(variables.flat(variables.values()))
         v = ctx.torch.zeros_like(theta)
         xi = ctx.empty(theta.numel())
-        logp, g = self._gradient(model, var_list, ctx)
+        logp, g = self._gradient(model, variables, ctx)
         kept, logps = {n: [] for n in names}, []
         for it in range(int(burn) + int(num_samples) * int(thin)):
             _lib.check(ctx.lib.dsdgp_randn(ctx.handle, C.c_uint64(int(seed)), C.c_uint64(it), theta.numel(), C.c_void_p(xi.data_ptr())))
             theta0, v0 = theta.clone(), v.clone()
             self.step(ctx, theta, v, g, xi)
-            self._assign(var_list, theta)
+            assign(theta)
             try:
-                logp, g = self._gradient(model, var_list, ctx)
+                logp, g = self._gradient(model, variables, ctx)
             except _lib.CholeskyError:
                 theta, v = theta0, v0                       # the previous state, and the gradient there on the next minibatch
-                self._assign(var_list, theta)
-                logp, g = self._gradient(model, var_list, ctx)
+                assign(theta)
+                logp, g = self._gradient(model, variables, ctx)
             if it >= int(burn) and (it - int(burn) + 1) % int(thin) == 0:
-                for n, p, x in zip(names, var_list, self._split(var_list, theta.cpu().numpy())):
-                    kept[n].append(positive_forward(x) if p.transform == "positive" else x.copy())
+                for n, x in zip(names, variables.constrained(variables.cut(theta.cpu().numpy()))):
+                    kept[n].append(x)
                 logps.append(logp)
-        self._assign(var_list, theta)
+        assign(theta)
         return dict(samples={n: np.stack(x) for n, x in kept.items()}, logprobs=np.array(logps), names=names, variables=var_list)
