@@ -771,7 +771,7 @@ __global__ __launch_bounds__(256) void k_potrf_trtri(const PotrfItem* __restrict
     __syncthreads();
     if (tid == 0) {
       const double ldv = s_red[0] + s_red[1] + s_red[2] + s_red[3];
-      if (it.pad & 16) {          // block of a larger matrix: accumulate (launches of one matrix are sequential)
+      if (it.pad & POTRF_PAD_ACCUM) {          // block of a larger matrix: accumulate (launches of one matrix are sequential)
         it.scal[0] += ldv;
         if (s_info && it.scal[1] == 0.0) it.scal[1] = (double)(s_info + it.info_offset);
       } else {
@@ -781,7 +781,7 @@ __global__ __launch_bounds__(256) void k_potrf_trtri(const PotrfItem* __restrict
     }
   }
   // write the factor back (LDS variant) with a zeroed strict upper triangle — unless the caller never reads it
-  if (!(INLDS && (it.pad & 8)))
+  if (!(INLDS && (it.pad & POTRF_PAD_SKIP_WB)))
   for (int idx = tid; idx < n * n; idx += 256) {
     const int i = idx / n, j = idx % n;
     const double v = (j > i) ? 0.0 : W[(int64_t)i * ld + j];
@@ -868,37 +868,22 @@ __global__ __launch_bounds__(256) void k_potrf_trtri(const PotrfItem* __restrict
     }
   }
   PH(5);
-  if (tid == 0 && it.pad == 7)
+  if (tid == 0 && it.pad == POTRF_PAD_TIMING)
     for (int q = 0; q < 6; ++q) it.scal[2 + q] = (double)tph[q];
 #undef PH
 }
 
 int potrf_launch(dsdgp_ctx* ctx, const PotrfItem* dev_items, int nitems, int n_max) {
   ProfScope ps(ctx, "potrf");
-  const int nb_max = n_max / 16;
-  const size_t base = (16 * 17 + 8 + (size_t)nb_max * 16 * 17) * sizeof(double);
-  if (n_max <= 128) {
-    const size_t lds = base + (size_t)n_max * (n_max + 4) * sizeof(double);
-    if (lds > 64 * 1024)
-      {
-        static int lds_set = 0;   // the attribute is sticky: one driver call per instance and size
-        if ((int)lds > lds_set) {
-          DS_HIP(hipFuncSetAttribute((const void*)k_potrf_trtri<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          lds_set = (int)lds;
-        }
-      }
-    DS_LAUNCH(k_potrf_trtri<true>, dim3(nitems), dim3(256), lds, ctx->stream, dev_items, nb_max);
-  } else {
-    if (base > 64 * 1024)
-      {
-        static int lds_set = 0;   // the attribute is sticky: one driver call per instance and size
-        if ((int)base > lds_set) {
-          DS_HIP(hipFuncSetAttribute((const void*)k_potrf_trtri<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)base));
-          lds_set = (int)base;
-        }
-      }
-    DS_LAUNCH(k_potrf_trtri<false>, dim3(nitems), dim3(256), base, ctx->stream, dev_items, nb_max);
+  const PotrfLds L = potrf_lds(n_max);
+  static int lds_set[2] = {0, 0};   // the attribute is sticky: one driver call per instance and size
+  const void* fn = L.in_lds ? (const void*)k_potrf_trtri<true> : (const void*)k_potrf_trtri<false>;
+  if (L.bytes > 64 * 1024 && (int)L.bytes > lds_set[L.in_lds]) {
+    DS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
+    lds_set[L.in_lds] = (int)L.bytes;
   }
+  if (L.in_lds) DS_LAUNCH(k_potrf_trtri<true>, dim3(nitems), dim3(256), L.bytes, ctx->stream, dev_items, L.nb_max);
+  else DS_LAUNCH(k_potrf_trtri<false>, dim3(nitems), dim3(256), L.bytes, ctx->stream, dev_items, L.nb_max);
   DS_HIP(hipGetLastError());
   return DSDGP_OK;
 }
@@ -929,7 +914,8 @@ __global__ void k_unpad(const double* __restrict__ P, int np, double* __restrict
 
 extern "C" int dsdgp_potrf(dsdgp_ctx* ctx, int batch, int n, double* A, int64_t lda, int64_t stride, int* info) {
   DS_CHECK_ARG(ctx && A && batch > 0 && n > 0 && lda >= n);
-  const int np = n > 176 ? (int)round_up(n, 64) : (int)round_up(n, 16);      // from 192 on: the blocked multi-workgroup sequence
+  const CholRoute route = chol_route(n, CHOL_BLOCKED_MIN, true);
+  const int np = route.np;
   const size_t mat_bytes = (size_t)batch * np * np * sizeof(double);
   const size_t item_bytes = round_up(batch * sizeof(PotrfItem), 256);
   const size_t scal_bytes = round_up((size_t)batch * 2 * sizeof(double), 256);
@@ -944,7 +930,7 @@ extern "C" int dsdgp_potrf(dsdgp_ctx* ctx, int batch, int n, double* A, int64_t 
   }
   DS_TRY(ctx_upload(ctx, items_d, items.data(), batch * sizeof(PotrfItem)));   // asynchronous (pinned staging ring)
   DS_LAUNCH(k_pad_spd, dim3(ceil_div(np * np, 256), batch), dim3(256), 0, ctx->stream, A, lda, stride, n, P, np);
-  if (np >= 192 && np % 64 == 0) {
+  if (route.kind == CHOL_BLOCKED) {
     // large matrices: multi-workgroup blocked path; the plan of the last call is kept in the context (the model path pre-builds its plans)
     const int64_t key[4] = {(int64_t)(uintptr_t)P, np, batch, n};
     if (!ctx->potrf_plan || memcmp(key, ctx->potrf_key, sizeof(key)) != 0) {
@@ -952,7 +938,7 @@ extern "C" int dsdgp_potrf(dsdgp_ctx* ctx, int batch, int n, double* A, int64_t 
       if (ctx->potrf_plan) ctx->potrf_plan_free(ctx->potrf_plan);
       ctx->potrf_plan = nullptr;
       BigChol* plan = new BigChol();
-      const int rc = bigchol_build(ctx, *plan, P, nullptr, nullptr, scal_d, batch, (int64_t)np * np, 2, np, n, nullptr, false);
+      const int rc = bigchol_build(ctx, *plan, P, nullptr, nullptr, scal_d, batch, 2, np, n, nullptr, false);
       if (rc != DSDGP_OK) {
         bigchol_free(*plan);
         delete plan;
@@ -1137,7 +1123,7 @@ __global__ __launch_bounds__(256) void k_trtri_diag64(const PotrfItem* __restric
 }
 
 // factor + inverse of ONE diagonal block (n = 128, or 64 at a ragged end) of the blocked factorisation, LDS-resident (chol_lds.hpp):
-// ~25 us for 128 columns where k_potrf_trtri took 23 us for 64.  PotrfItem as for k_potrf_trtri (pad bit 16: accumulate into scal).
+// ~25 us for 128 columns where k_potrf_trtri took 23 us for 64.  PotrfItem as for k_potrf_trtri (POTRF_PAD_ACCUM: accumulate into scal).
 //
 // Look-ahead form of the blocked factorisation (round 6): the launch that factors diagonal block q also carries, in further workgroups, the
 // WIDE part of the trailing update with panel q - 1 (block columns >= q + 1: nothing the factorisation of block q reads), so that only
@@ -1335,7 +1321,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_chol_block(const PotrfItem it0
   if (tid == 0) s_info = 0;
   // accumulated logdet / info of the earlier blocks: requested with the block's loads (the read-modify-write at the end waits for nothing)
   double sc0 = 0.0, sc1 = 0.0;
-  if (tid == 0 && it.scal && (it.pad & 16)) {
+  if (tid == 0 && it.scal && (it.pad & POTRF_PAD_ACCUM)) {
     sc0 = it.scal[0];
     sc1 = it.scal[1];
   }
@@ -1366,7 +1352,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_chol_block(const PotrfItem it0
   for (int i = tid; i < nreal; i += CHOL_THREADS) s += 2.0 * log(W[i * ld + i]);
   s = sum_wave(s);
   if (lane == 0) red[wave] = s;
-  if (!(it.pad & 8))
+  if (!(it.pad & POTRF_PAD_SKIP_WB))
     for (int idx = tid; idx < n * n; idx += CHOL_THREADS) {
       const int i = idx >> sh, j = idx & (n - 1);
       Wg[(int64_t)i * it.ld + j] = (j <= i) ? W[i * ld + j] : 0.0;
@@ -1375,7 +1361,7 @@ __global__ __launch_bounds__(CHOL_THREADS) void k_chol_block(const PotrfItem it0
   if (tid == 0 && it.scal) {
     double ldv = 0.0;
     for (int w = 0; w < CHOL_NW; ++w) ldv += red[w];
-    if (it.pad & 16) {
+    if (it.pad & POTRF_PAD_ACCUM) {
       it.scal[0] = sc0 + ldv;
       if (s_info && sc1 == 0.0) it.scal[1] = (double)(it.info_offset + s_info);
     } else {
@@ -1482,198 +1468,102 @@ __global__ __launch_bounds__(256) void k_chol_panel(const CholPanel a) {
   }
 }
 
-#define BCB 128     // diagonal block of the blocked factorisation
-int bigchol_build(dsdgp_ctx* ctx, BigChol& P, double* W, double* Linv, double* LinvT, double* scal, int batch, int64_t stride,
-                  int64_t scal_stride, int n, int nreal, double* Tbuf, bool from_tri, bool need_factor) {
-  DS_CHECK_ARG(n % 64 == 0 && n >= 128 && batch >= 1);
-  P.need_factor = need_factor;
-  P.n = n; P.batch = batch; P.nb = from_tri ? n / 64 : ceil_div(n, BCB);
-  P.W = W; P.Linv = Linv; P.LinvT = LinvT; P.scal = scal; P.Tbuf = Tbuf;
-  P.stride = stride; P.scal_stride = scal_stride;
-  P.want_inverse = Linv != nullptr;
-  P.from_tri = from_tri;
-  const int nb = P.nb;
-  // plan-owned scratch (BCB x n per matrix) unless the caller supplies one
-  const int bs = from_tri ? 64 : BCB;
-  const size_t tb = Tbuf ? 0 : (size_t)batch * bs * n * sizeof(double);
-  void* tblock = nullptr;
-  if (tb) {
-    DS_HIP(hipMalloc(&tblock, tb));
-    DS_HIP(hipMemset(tblock, 0, tb));
-    Tbuf = (double*)tblock;
-    P.Tbuf = Tbuf;
-  }
-  P.tbuf_block = tblock;
-  std::vector<PotrfItem> items((size_t)nb * batch);
-  for (int p = 0; p < nb; ++p)
-    for (int b = 0; b < batch; ++b) {
-      const int64_t off = (int64_t)b * stride + (int64_t)p * bs * n + p * bs;
-      const int bn = std::min(bs, n - p * bs);                // 64 at a ragged end (n a multiple of 64)
-      int nr = nreal - p * bs;
-      nr = nr < 0 ? 0 : (nr > bn ? bn : nr);
-      // without a requested inverse the inverses of the diagonal blocks (needed by the panel solve) live in Tbuf
-      double* dinv = Linv ? Linv + off : Tbuf + (int64_t)b * bs * n + p * bs;
-      // (block 0 SETS logdet / info, the later blocks accumulate: no memset of `scal` in front of the sequence)
-      items[(size_t)p * batch + b] = PotrfItem{W + off, dinv, nullptr, scal ? scal + b * scal_stride : nullptr,
-                                               bn, n, nr, p == 0 ? 0 : 16, p * bs, 0};
-    }
-  std::vector<GemmProblem> gp;
-  P.tiles.clear();
-  P.nprob.clear();
-  P.first.clear();
-  // one launch = a list of problems planned together (tile_start relative to the launch)
-  auto add_launch = [&](std::vector<GemmProblem>& list, int allow_big) {
-    P.tiles.push_back(gemm_plan(list.data(), (int)list.size(), allow_big));
-    P.nprob.push_back((int)list.size());
-    P.first.push_back((int)gp.size());
-    for (auto& g : list) gp.push_back(g);
-  };
-  auto add = [&](GemmProblem& g, int mode) {
-    std::vector<GemmProblem> one{g};
-    add_launch(one, mode);
-  };
-  auto mk = [&](const double* A, const double* B, double* C, int m, int nn, int k, int tA, int tB, double alpha, double beta, int lower) {
-    GemmProblem g;
-    memset(&g, 0, sizeof(g));
-    g.A = A; g.B = B; g.C = C; g.m = m; g.n = nn; g.k = k;
-    g.lda = n; g.ldb = n; g.ldc = n;
-    g.transA = tA; g.transB = tB; g.batch = batch; g.sA = stride; g.sB = stride; g.sC = stride; g.batch_reduce = 0;
-    g.alpha = alpha; g.beta = beta; g.lower_only = lower;
-    return g;
-  };
+// ---- the blocked sequence: bind a host plan (chol_plan.hpp) to the caller's buffers, then walk its steps ----
+static_assert(sizeof(PotrfItem) == CHOL_ITEM_BYTES && sizeof(GemmProblem) == CHOL_GEMM_BYTES, "chol_plan.hpp sizes the descriptor block");
+
+int bigchol_build(dsdgp_ctx* ctx, BigChol& P, double* W, double* Linv, double* LinvT, double* scal, int batch, int64_t scal_stride, int n,
+                  int nreal, double* Tbuf, bool from_tri, bool need_factor) {
   const bool lookahead_off = getenv("DSDGP_CHOL_LOOKAHEAD") && atoi(getenv("DSDGP_CHOL_LOOKAHEAD")) == 0;      // (A/B aid; read per plan)
-  // the wide-update workgroups of the look-ahead form each hold a whole CU (the factor launch's LDS): beyond 16 blocks the plain sequence
-  P.lookahead = !from_tri && !lookahead_off && P.nb >= 2 && P.nb <= 16;
-  P.dinv = Linv ? Linv : Tbuf;
-  P.dinv_stride = Linv ? stride : (int64_t)bs * n;
-  P.dinv_step = Linv ? (int64_t)BCB * n + BCB : BCB;
-  if (!from_tri && !P.lookahead) {
-    for (int p = 0; p + 1 < P.nb; ++p) {
-      const int rem = n - (p + 1) * BCB;
-      double* panel = W + (int64_t)(p + 1) * BCB * n + p * BCB;
-      // the panel, TRANSPOSED, into the mirror blocks above the diagonal (unused by the factorisation):  L_ip^T = L_pp^-1 A_ip^T.
-      // Out of place, so the LDS-free 64 x 64 kernel can take it (16 us; in place only a kernel whose workgroup owns all 128 columns
-      // of its rows is safe — the 128 x 128 kernel at 8 barrier-separated k-steps: 26 us).  k_mirror_panels moves the panels
-      // back below the diagonal at the end.
-      double* mirror = W + (int64_t)p * BCB * n + (p + 1) * BCB;
-      GemmProblem g1 = mk(Linv ? Linv + (int64_t)p * BCB * n + p * BCB : Tbuf + p * BCB, panel, mirror, BCB, rem, BCB, 0, 1, 1.0, 0.0, 0);
-      if (!Linv) g1.sA = (int64_t)BCB * n;
-      g1.tri = 2;                                        // L_pp^-1 lower-triangular
-      add(g1, 0);
-      // A_ij -= L_ip L_jp^T  (lower tiles only), both operands read from the transposed panel
-      GemmProblem g2 = mk(mirror, mirror, W + (int64_t)(p + 1) * BCB * n + (p + 1) * BCB, rem, rem, BCB, 1, 0, -1.0, 1.0, 1);
-      add(g2, 0);
-    }
-  }
-  P.xrows = P.want_inverse && P.lookahead;      // block rows of X inside the factor launches (chol_xrow) instead
-  if (P.want_inverse && !P.xrows) {
-    // X = L^-1 by RECURSIVE DOUBLING over the 64 x 64 diagonal inverses the factor kernel left on Linv's diagonal: at block
-    // size s every pair of adjacent diagonal blocks [X11 0; X21 X22] gets X21 = -X22 (L21 X11), all n / 2s pairs (and all
-    // matrices of the batch) in ONE grouped launch per product: 2 log2(n / 64) launches (8 at n = 1024) instead of the
-    // 2 (n / 64 - 1) of the block-row recurrence, and the upper levels are big enough for the 128 x 128 kernel.
-    // T = L21 X11 is parked in the mirror position of the X21 block inside the scratch matrix S (LinvT when the caller wants
-    // it — the final transpose overwrites it — else a plan-owned n x n).
-    double* S = LinvT;
-    if (!S) {
-      DS_HIP(hipMalloc(&P.inv_block, (size_t)batch * n * n * sizeof(double)));
-      S = (double*)P.inv_block;
-    }
-    const int64_t sS = LinvT ? stride : (int64_t)n * n;
-    for (int sblk = from_tri ? 64 : BCB; sblk < n; sblk *= 2) {
-      std::vector<GemmProblem> l1, l2;
-      for (int r0 = sblk; r0 < n; r0 += 2 * sblk) {
-        const int c0 = r0 - sblk;
-        const int rows = (n - r0 < sblk) ? n - r0 : sblk;      // ragged last pair (n / 64 not a power of two)
-        GemmProblem g1 = mk(W + (int64_t)r0 * n + c0, Linv + (int64_t)c0 * n + c0, S + (int64_t)r0 * n + c0, rows, sblk, sblk, 0, 0,
-                            1.0, 0.0, 0);
-        g1.sC = sS; g1.tri = 1;                                 // X11 lower-triangular: k >= n
-        l1.push_back(g1);
-        GemmProblem g2 = mk(Linv + (int64_t)r0 * n + r0, S + (int64_t)r0 * n + c0, Linv + (int64_t)r0 * n + c0, rows, sblk, rows, 0, 0,
-                            -1.0, 0.0, 0);
-        g2.sB = sS; g2.tri = 2;                                 // X22 lower-triangular: k <= m
-        l2.push_back(g2);
-      }
-      add_launch(l1, sblk <= 256 ? 0 : 1);      // short K: as above
-      add_launch(l2, sblk <= 256 ? 0 : 1);
-    }
-  }
+  P.plan = chol_plan(CholIn{n, nreal, batch, Linv != nullptr, LinvT != nullptr, from_tri, need_factor, Tbuf != nullptr, !lookahead_off});
+  DS_CHECK_ARG(P.plan.ok);
+  const CholPlan& C = P.plan;
+  // what the plan owns, in one block: Tbuf (zeroed: the panel solve reads whole 128 x 128 blocks of it) | S | items | problems
+  if (C.tbuf_bytes + C.s_bytes + C.desc_bytes) DS_HIP(hipMalloc(&P.block, C.tbuf_bytes + C.s_bytes + C.desc_bytes));
+  char* own = (char*)P.block;
+  if (C.tbuf_bytes) DS_HIP(hipMemset(own, 0, C.tbuf_bytes));
+  P.buf[CB_W] = W;
+  P.buf[CB_LINV] = Linv;
+  P.buf[CB_TBUF] = C.tbuf_bytes ? (double*)own : Tbuf;
+  P.buf[CB_S] = LinvT ? LinvT : (double*)(own + C.tbuf_bytes);
+  P.LinvT = LinvT;
+  P.scal_stride = scal_stride;
+  P.diag_items = (PotrfItem*)(own + C.tbuf_bytes + C.s_bytes);
+  P.gp = (GemmProblem*)(own + C.tbuf_bytes + C.s_bytes + C.items_bytes);
+  // (buffer, offset) -> pointer: here and nowhere else
+  auto at = [&](const CholRef& r) { return P.buf[r.buf] + r.off; };
   P.items0.clear();
-  for (int p = 0; p < nb; ++p) {      // matrix 0's item per block: k_chol_block's argument
-    P.items0.push_back(items[(size_t)p * batch]);
-    // nobody reads L: the panel solve, the wide update and the rows of the inverse all work from L_pp^-1 — the block's own write-back goes too
-    if (P.xrows && !P.need_factor) P.items0.back().pad |= 8;
+  for (const CholItem& it : C.items)
+    P.items0.push_back(PotrfItem{at(CholRef{CB_W, it.w_off}), at(it.inv), nullptr, scal, it.bn, n, it.nreal, it.pad, it.info_offset, 0});
+  if (C.items_bytes) {
+    std::vector<PotrfItem> items;
+    for (int p = 0; p < C.nb; ++p)
+      for (int b = 0; b < batch; ++b) {
+        PotrfItem it = P.items0[p];
+        it.W += b * C.stride[CB_W];
+        it.Linv += b * C.stride[C.items[p].inv.buf];
+        if (it.scal) it.scal += b * scal_stride;
+        items.push_back(it);
+      }
+    DS_HIP(hipMemcpy(P.diag_items, items.data(), items.size() * sizeof(PotrfItem), hipMemcpyHostToDevice));
   }
-  const size_t ib = round_up(items.size() * sizeof(PotrfItem), 256), gb = round_up(gp.size() * sizeof(GemmProblem) + 256, 256);
-  DS_HIP(hipMalloc(&P.dev_block, ib + gb));
-  P.diag_items = (PotrfItem*)P.dev_block;
-  P.gp = (GemmProblem*)((char*)P.dev_block + ib);
-  DS_HIP(hipMemcpy(P.diag_items, items.data(), items.size() * sizeof(PotrfItem), hipMemcpyHostToDevice));
+  std::vector<GemmProblem> gp(C.gemms.size());
+  for (size_t i = 0; i < gp.size(); ++i) {
+    const CholGemm& g = C.gemms[i];
+    GemmProblem& o = gp[i];
+    memset(&o, 0, sizeof(o));
+    o.A = at(g.A); o.B = at(g.B); o.C = at(g.C);
+    o.sA = C.stride[g.A.buf]; o.sB = C.stride[g.B.buf]; o.sC = C.stride[g.C.buf];
+    o.lda = o.ldb = o.ldc = n;
+    o.m = g.m; o.n = g.n; o.k = g.k; o.transA = g.transA; o.transB = g.transB; o.batch = batch;
+    o.alpha = g.alpha; o.beta = g.beta; o.lower_only = g.lower_only; o.tri = g.tri;
+  }
+  // one GEMM step = a list of problems planned together (tile_start relative to the launch); gemm_plan stays here: its choice of the
+  // LDS-free kernel reads the operands' alignment
+  P.tiles.assign(C.steps.size(), 0);
+  for (size_t s = 0; s < C.steps.size(); ++s)
+    if (C.steps[s].kind == CS_GEMM) P.tiles[s] = gemm_plan(gp.data() + C.steps[s].first, C.steps[s].count, C.steps[s].allow_big);
   if (!gp.empty()) DS_HIP(hipMemcpy(P.gp, gp.data(), gp.size() * sizeof(GemmProblem), hipMemcpyHostToDevice));
   return DSDGP_OK;
 }
 
 void bigchol_free(BigChol& P) {
-  if (P.inv_block) hipFree(P.inv_block);
-  P.inv_block = nullptr;
-  if (P.dev_block) hipFree(P.dev_block);
-  if (P.tbuf_block) hipFree(P.tbuf_block);
-  P.dev_block = nullptr;
-  P.tbuf_block = nullptr;
+  if (P.block) hipFree(P.block);
+  P.block = nullptr;
 }
 
 int bigchol_run(dsdgp_ctx* ctx, const BigChol& P) {
   ProfScope ps(ctx, "potrf");
-  const int nb = P.nb, batch = P.batch;
-  int gi = 0;
-  auto launch = [&](int i) { gemm_dispatch(P.gp + P.first[i], P.nprob[i], P.tiles[i], ctx->stream); };
-  if (!P.from_tri) {
-    const size_t lds = chol_lds_bytes(BCB);
-    static bool lds_set = false;      // the attribute is sticky: one driver call
-    if (!lds_set) {
-      DS_HIP(hipFuncSetAttribute((const void*)k_chol_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      lds_set = true;
-    }
-    for (int p = 0; p < nb; ++p) {
-      CholWide wa{P.W, P.stride, P.n, p, 0, batch};
-      if (P.lookahead && p >= 1) {
-        const int ns64 = (P.n - (p + 1) * BCB) / 64;      // 64-row strips from block p + 1 on
-        wa.nwide = ns64 > 0 ? ns64 * (ns64 + 1) / 2 : 0;
-      }
-      CholXrow xa{P.W, P.Linv, P.LinvT, P.stride, P.n, p - 1, 0, batch, 0, 0}, xb = xa;
-      if (P.xrows && p >= 1) xa.nx = 8 * (p - 1 + (P.LinvT ? 1 : 0));
-      if (P.xrows && p == nb - 1) {      // the early terms of the last row
-        xb.i = p;
-        xb.nx = 8 * (p - 1);
-        xb.mode = 1;
-      }
-      const int side = std::min(batch * (wa.nwide + xa.nx + xb.nx), std::max(32, 248 - batch));      // (a CU each: one round of them)
-      DS_LAUNCH(k_chol_block, dim3(batch + side), dim3(CHOL_THREADS), lds, ctx->stream, P.items0[p], P.stride, P.dinv_stride,
-                P.scal_stride, wa, xa, xb);
-      if (p + 1 < nb) {
-        if (P.lookahead) {
-          const int nrem = P.n - (p + 1) * BCB, nbb = std::min(nrem, BCB) / 32, ns = nrem / 32;
-          const CholPanel pa{P.W, P.dinv + (int64_t)p * P.dinv_step, P.stride, P.dinv_stride, P.n, p};
-          DS_LAUNCH(k_chol_panel, dim3(nbb * (nbb + 1) / 2 + (ns - nbb) * nbb, batch), dim3(256), 0, ctx->stream, pa);
-        } else {
-          launch(gi++);
-          launch(gi++);
+  const CholPlan& C = P.plan;
+  const int n = C.in.n, batch = C.in.batch;
+  double *W = P.buf[CB_W], *Linv = P.buf[CB_LINV];
+  const int64_t sW = C.stride[CB_W];
+  auto xrow = [&](const CholXrowArg& x) { return CholXrow{W, Linv, P.LinvT, sW, n, x.i, x.nx, batch, x.mode, 0}; };
+  for (size_t si = 0; si < C.steps.size(); ++si) {
+    const CholStep& s = C.steps[si];
+    switch (s.kind) {
+      case CS_BLOCK: {
+        const size_t lds = chol_lds_bytes(BCB);
+        static bool lds_set = false;      // the attribute is sticky: one driver call
+        if (!lds_set) {
+          DS_HIP(hipFuncSetAttribute((const void*)k_chol_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+          lds_set = true;
         }
+        const CholWide wa{W, sW, n, s.q, s.nwide, batch};
+        DS_LAUNCH(k_chol_block, dim3(s.gx), dim3(CHOL_THREADS), lds, ctx->stream, P.items0[s.q], sW, C.stride[C.items[s.q].inv.buf],
+                  P.scal_stride, wa, xrow(s.xa), xrow(s.xb));
+        break;
       }
+      case CS_PANEL: {
+        const CholPanel pa{W, P.items0[s.q].Linv, sW, C.stride[C.items[s.q].inv.buf], n, s.q};
+        DS_LAUNCH(k_chol_panel, dim3(s.gx, s.gy), dim3(256), 0, ctx->stream, pa);
+        break;
+      }
+      case CS_GEMM: gemm_dispatch(P.gp + s.first, s.count, P.tiles[si], ctx->stream); break;
+      case CS_XROW_LAST: DS_LAUNCH(k_chol_xrow, dim3(s.gx), dim3(CHOL_THREADS), 0, ctx->stream, xrow(s.xa)); break;
+      case CS_MIRROR: DS_LAUNCH(k_mirror_panels, dim3(s.gx, s.gy), dim3(256), 0, ctx->stream, W, n, sW, BCB); break;
+      case CS_TRTRI_DIAG64: DS_LAUNCH(k_trtri_diag64, dim3(s.gx), dim3(256), 0, ctx->stream, P.diag_items); break;
+      case CS_TRANSPOSE: DS_LAUNCH(k_transpose_lower, dim3(s.gx, s.gy), dim3(256), 0, ctx->stream, Linv, P.LinvT, n, sW); break;
     }
-    if (P.xrows) {
-      CholXrow xa{P.W, P.Linv, P.LinvT, P.stride, P.n, nb - 1, 8 * (nb - 1 + (P.LinvT ? 1 : 0)), batch, 2, 0};
-      if (xa.nx) DS_LAUNCH(k_chol_xrow, dim3(std::min(batch * xa.nx, 2048)), dim3(CHOL_THREADS), 0, ctx->stream, xa);
-    }
-    // (with the inverse formed from the parked panels nothing but a caller that reads L itself needs them moved below the diagonal)
-    if (P.need_factor || !P.xrows)
-      DS_LAUNCH(k_mirror_panels, dim3(std::min(1024, (P.n / 16) * (P.n / 16)), batch), dim3(256), 0, ctx->stream, P.W, P.n, P.stride, BCB);
-  } else if (P.want_inverse) {
-    DS_LAUNCH(k_trtri_diag64, dim3(nb * batch), dim3(256), 0, ctx->stream, P.diag_items);
-  }
-  if (P.want_inverse && !P.xrows) {
-    while (gi < (int)P.tiles.size()) launch(gi++);
-    if (P.LinvT)
-      DS_LAUNCH(k_transpose_lower, dim3(256, batch), dim3(256), 0, ctx->stream, P.Linv, P.LinvT, P.n, P.stride);
   }
   DS_HIP(hipGetLastError());
   return DSDGP_OK;

@@ -1,6 +1,7 @@
 // Small dense fp64 linear algebra on gfx950: grouped MFMA GEMM, blocked Cholesky + triangular inverse.
 #pragma once
 #include "common.hpp"
+#include "chol_plan.hpp"
 
 // One GEMM of a grouped launch: C[b] = alpha * op(A[b]) * op(B[b]) + beta * C[b]   (row-major),
 // or, with batch_reduce, C = alpha * sum_b op(A[b]) op(B[b]) + beta * C.
@@ -37,7 +38,7 @@ struct PotrfItem {
                   // one; only the plain blocked sequence rewrites all of LinvT (k_transpose_lower).  Nothing may use those halves as
                   // scratch between two factorisations (tests/test_gpu_factor_direct.py reads them back after every kind of model call).
   double* scal;   // out: [0] = sum_i<nreal 2 log L_ii (= logdet), [1] = info (0 ok, else 1-based bad pivot)
-  int32_t n, ld, nreal, pad;   // pad bits: 8 = skip factor write-back, 16 = accumulate into scal (blocked driver), 7 = timing
+  int32_t n, ld, nreal, pad;   // pad: POTRF_PAD_SKIP_WB | POTRF_PAD_ACCUM (bits), or the value POTRF_PAD_TIMING (chol_plan.hpp)
   int32_t info_offset, pad2;   // added to a failing pivot index (position of this block inside a larger matrix)
 };
 
@@ -53,38 +54,34 @@ int gemm_launch(dsdgp_ctx* ctx, const GemmProblem* dev, int nprob, int total_til
 // layer_gemm.hip: C (m x n) += alpha W (m x k) B (k x n), row-major, 128 x 128 (or 128 x 64) LDS-tiled fp64-MFMA tiles over the whole k
 // range (W, B 16-byte aligned, even leading dimensions, n a multiple of 8)
 int pgemm_accum(dsdgp_ctx* ctx, const double* W, int64_t ldw, const double* B, int64_t ldb, double* C, int64_t ldc, int m, int n, int k, double alpha);
-// n_max: largest (padded) matrix order among the items; <= 128 selects the LDS-resident variant
+// n_max: largest (padded) matrix order among the items (potrf_lds: the LDS-resident variant up to CHOL_ONE_WG_LDS_MAX)
 int potrf_launch(dsdgp_ctx* ctx, const PotrfItem* dev_items, int nitems, int n_max);
 // batched inverse of padded lower-triangular matrices (n multiple of 16, identity pad), one workgroup each
 int trtri_launch(dsdgp_ctx* ctx, double* W, double* Linv, int n, int64_t stride, int batch);
 
-// ---- multi-workgroup blocked Cholesky + triangular inverse for large matrices (n >= 512, multiple of 64) ----
-// Right-looking with NB = 64: diagonal blocks by k_potrf_trtri (LDS variant), panel solve and trailing syrk as grouped
-// MFMA GEMM launches over all 64x64 tiles, inverse by the blocked recurrence X_i,: = -X_ii (L_i,: X) (two GEMMs per block
-// row).  All descriptors are built once (static pointers) so a run is a fixed, fully asynchronous launch sequence.
+// ---- multi-workgroup blocked Cholesky + triangular inverse (orders from CHOL_BLOCKED_MIN on, multiples of 64) ----
+// Right-looking with 128 x 128 diagonal blocks factored and inverted in LDS (k_chol_block).  The launch sequence — look-ahead form or plain
+// GEMM form, the inverse by block rows or by recursive doubling — is a host plan (chol_plan.hpp: CholPlan, one step per launch over
+// (buffer, offset) operands).  bigchol_build binds a plan to the caller's buffers: one device allocation for what the plan owns, the
+// operands turned into pointers, the GEMM steps planned (gemm_plan) and uploaded.  bigchol_run walks the steps: a fixed, fully
+// asynchronous launch sequence.
 struct BigChol {
-  int n = 0, batch = 0, nb = 0;
-  bool want_inverse = false, from_tri = false;   // from_tri: input is already a lower-triangular factor (inverse only)
-  double* W = nullptr; double* Linv = nullptr; double* LinvT = nullptr; double* scal = nullptr; double* Tbuf = nullptr;
-  int64_t stride = 0, scal_stride = 0;
-  bool lookahead = false;              // k_chol_panel + wide update inside the factor launches (linalg.hip)
-  bool need_factor = true;             // false: only the inverse / log det are read (the panels may stay parked above the diagonal)
-  bool xrows = false;                  // ... and the block rows of the inverse (chol_xrow) instead of the recursive doubling
-  const double* dinv = nullptr;        // inverse of diagonal block 0 of matrix 0; block p: + p * dinv_step, matrix b: + b * dinv_stride
-  int64_t dinv_stride = 0, dinv_step = 0;
-  PotrfItem* diag_items = nullptr;     // device: nb * batch
-  std::vector<PotrfItem> items0;       // host: matrix 0's item of every diagonal block
-  GemmProblem* gp = nullptr;           // device: per panel {solve, trailing}, then per block row {T, X}
-  std::vector<int> tiles;              // per launch: planned tile count (bit 30: large-tile kernel)
-  std::vector<int> nprob, first;       // per launch: number of problems and index of the first one in gp
-  void* inv_block = nullptr;           // plan-owned scratch of the recursive-doubling inverse (when no LinvT is requested)
-  void* dev_block = nullptr;
-  void* tbuf_block = nullptr;         // plan-owned Tbuf (when the caller passed none)
+  CholPlan plan;
+  double* buf[CB_COUNT] = {nullptr, nullptr, nullptr, nullptr};      // W, Linv, Tbuf, S of matrix 0
+  double* LinvT = nullptr;
+  int64_t scal_stride = 0;
+  std::vector<PotrfItem> items0;       // host: matrix 0's item of every diagonal block (k_chol_block's argument)
+  PotrfItem* diag_items = nullptr;     // device: nb * batch items (k_trtri_diag64 only)
+  GemmProblem* gp = nullptr;           // device: the plan's GEMM problems
+  std::vector<int> tiles;              // per step: gemm_plan's tile count of a GEMM step (with the kernel flags)
+  void* block = nullptr;               // everything the plan owns: Tbuf | S | items | problems
 };
-// W/Linv/LinvT: `batch` matrices of order n (leading dimension n) `stride` doubles apart; scal: 2 doubles per matrix
-// (`scal_stride` apart); Tbuf: batch * 64 * n doubles of scratch (needed when want_inverse).
-int bigchol_build(dsdgp_ctx* ctx, BigChol& P, double* W, double* Linv, double* LinvT, double* scal, int batch, int64_t stride,
-                  int64_t scal_stride, int n, int nreal, double* Tbuf, bool from_tri, bool need_factor = true);
+// W/Linv/LinvT: `batch` matrices of order n (leading dimension n), n * n doubles apart; scal: 2 doubles per matrix (`scal_stride` apart);
+// Linv NULL: factor only; Tbuf: NULL, or batch * 128 * n zeroed doubles lent by the caller (read only without Linv); from_tri: W holds
+// lower-triangular factors, only Linv is formed; need_factor false: only the inverse and log det are read.  Illegal combinations
+// (chol_in_legal) are refused.
+int bigchol_build(dsdgp_ctx* ctx, BigChol& P, double* W, double* Linv, double* LinvT, double* scal, int batch, int64_t scal_stride, int n,
+                  int nreal, double* Tbuf, bool from_tri, bool need_factor = true);
 int bigchol_run(dsdgp_ctx* ctx, const BigChol& P);
 void bigchol_free(BigChol& P);
 

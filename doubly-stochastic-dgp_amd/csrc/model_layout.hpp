@@ -27,9 +27,8 @@ static void layout(dsdgp_model* m, char* base, size_t* total) {
   for (int l = 0; l < D.L; ++l) m->rjobs_cap += plan_red_slots(D.layers[l].D_out);
   m->rjobs = b.take<RedJob>(m->rjobs_cap);
   // layers with the same (large) M keep their Ku / Lu^-1 / Lu^-T contiguous so that one batched factorisation serves them all
-  bool uniform = D.L > 1 && pad_M(D.layers[0].M) >= big_mp(true);
+  bool uniform = D.L > 1 && mp_blocked(pad_M(D.layers[0].M), true);
   for (int l = 1; l < D.L; ++l) uniform = uniform && D.layers[l].M == D.layers[0].M;
-  uniform = uniform && pad_M(D.layers[0].M) % 64 == 0;
   m->uniform_big = uniform;
   double *Kp_all = nullptr, *Linv_all = nullptr, *LinvT_all = nullptr, *scal_all = nullptr;
   if (uniform) {

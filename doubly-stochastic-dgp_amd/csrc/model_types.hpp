@@ -21,7 +21,7 @@ struct LayerState : PlanBufs {      // (operands and partial buffers of the weig
   int red_off = 0, red_blk0 = 0;   // this layer's first entry of the reduction job list / first of its blocks (they end where the next layer's begin)
   double* bpart = nullptr;      // backward-chain d-split: partial abar tiles [row block][split][Mp * 16 + 16]
   int* bcnt = nullptr;          //   arrival counters per row block (zero between launches)
-  bool big = false;    // Mp >= big_mp(), a multiple of 64: multi-workgroup blocked factorisations (linalg.hpp BigChol)
+  bool big = false;    // mp_blocked(Mp): multi-workgroup blocked factorisations (linalg.hpp BigChol)
   BigChol big_k, big_ngA, big_ngT;
   GemmProblem* ng_gp;  // device: 4 natural-gradient GEMM problems (H, Sinv | Y | X)
   PotrfItem* ng_items; // device: D_out factorisation items (the index-reversed A_d)
@@ -68,7 +68,7 @@ struct dsdgp_model {
   int sample_w_S = 0;
   GemmProblem* gp_wz;   // wm [Z | 1] of the layers with D_in > WIDE_DIN
   int n_wz = 0, t_wz = 0, kuu_blocks = 32, asm_blocks = 64, prep_blocks = PREP_BLOCKS;
-  bool uniform_big = false;     // all layers share M and Mp >= 192: ONE batched multi-workgroup Cholesky for all layers
+  bool uniform_big = false;     // all layers share M and mp_blocked(Mp): ONE batched multi-workgroup Cholesky for all layers
   BigChol big_all;
   bool need_hyp_part = false;   // some layer does not fold its Ku-side hyper-parameter partials into k_asm_kbar
   bool tail_ok = false;         // non-white, every D_in <= WIDE_DIN: gradient assembly in k_asm_rows + k_tail (one wave per inducing row)
@@ -141,10 +141,11 @@ struct Bump {
   }
 };
 
-// padded inducing count from which the multi-workgroup blocked Cholesky / inverse (look-ahead sequence, linalg.hip) replaces the
-// one-workgroup kernel: 192 (Mp a multiple of 64).  Measured, factor + inverse of one matrix: Mp = 192 180 -> 77 us, 256 371 -> 101,
-// 448 1990 -> 181.  Layers that share M are factorised as ONE batch.
+// padded inducing count from which the multi-workgroup blocked Cholesky / inverse replaces the one-workgroup kernel (chol_plan.hpp:
+// chol_route).  Layers that share M are factorised as ONE batch.
 static int big_mp(bool uniform) {
-  static const int nonuniform = getenv("DSDGP_BIG_MP") ? atoi(getenv("DSDGP_BIG_MP")) : 192;      // (A/B aid)
-  return uniform ? 192 : nonuniform;
+  static const int nonuniform = getenv("DSDGP_BIG_MP") ? atoi(getenv("DSDGP_BIG_MP")) : CHOL_BLOCKED_MIN;      // (A/B aid)
+  return uniform ? CHOL_BLOCKED_MIN : nonuniform;
 }
+// a model's Mp is fixed by the chain kernels (pad_M): the blocked sequence takes it from big_mp() on, as a multiple of 64
+static bool mp_blocked(int Mp, bool uniform) { return chol_route(Mp, big_mp(uniform), false).kind == CHOL_BLOCKED; }

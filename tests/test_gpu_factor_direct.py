@@ -34,7 +34,7 @@ alone (DSDGP_BIG_MP=128, read once per process: a child process); the blocked lo
 models; the plain blocked sequence (DSDGP_CHOL_LOOKAHEAD=0); Mp = 1152, which only the GEMM-formulated layers take.
 
 Set DSDGP_FACTOR_PROFILE=<file> to get every measured device and CPU value as one table (profiles/factor_direct_residuals.md).
-134 cases, 208 matrices, about a minute on an MI355X with 16 host cores (the 40-digit factorisations run once, in worker processes)."""
+135 cases, 208 matrices, about a minute on an MI355X with 16 host cores (the 40-digit factorisations run once, in worker processes)."""
 import ctypes as C
 import os
 import subprocess
@@ -657,6 +657,28 @@ def test_potrf_leaves_the_gaps_of_a_strided_batch_alone(ctx, n):
         m = mask[b * stride: b * stride + lda * n].reshape(n, lda)
         m[:, :n] = False
     assert np.all(out[mask] == 7.25)
+
+
+def test_potrf_rebuilds_the_context_held_plan(ctx):
+    """n = 192, then 256, then 192 with batch 2, then 192 again on ONE context: every call finds another plan's key, frees that plan (one
+    device block: bigchol_free) and builds its own.  The last call gives the first call's bits, and every factor meets the factor bar."""
+    rng = np.random.RandomState(192)
+    As = {}
+    for n in (192, 256):
+        A = rng.randn(2, n, n)
+        As[n] = A @ A.transpose(0, 2, 1) + n * np.eye(n)
+    got = []
+    for n, batch in ((192, 1), (256, 1), (192, 2), (192, 1)):
+        rc, info, L = _potrf(ctx, As[n][:batch], n, batch=batch)
+        assert (rc, info) == (0, 0), (n, batch, rc, info)
+        L = L.reshape(batch, n, n)
+        for b in range(batch):
+            assert not np.any(np.triu(L[b], 1))
+            err = R.factor_backward(L[b], As[n][b])
+            print(f"n={n} batch={batch} matrix {b}: factor backward error {err:.3e} (bar {R.factor_bar(n):.3e})")
+            assert err <= R.factor_bar(n), (n, batch, b, err)
+        got.append(L)
+    assert np.array_equal(got[3], got[0])
 
 
 if __name__ == "__main__":
