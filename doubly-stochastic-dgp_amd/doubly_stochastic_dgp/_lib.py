@@ -210,6 +210,14 @@ _PROTOS = {
     "dsdgp_stack_hop_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
                                       C.c_void_p, C.c_void_p]),
     "dsdgp_sghmc_step": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    # pathwise (Matheron) function draws: the fused evaluation and the update weights (no reference counterpart)
+    "dsdgp_pathwise_eval": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]),
+    "dsdgp_pathwise_scratch_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "dsdgp_pathwise_weights": (C.c_int, [C.c_void_p, C.POINTER(KernelSpec), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_double, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int)]),
     "dsdgp_model_set_grad_first_layer":(C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_set_grad_q_only": (C.c_int, [C.c_void_p, C.c_int32]),
     "dsdgp_model_track_theta": (C.c_int, [C.c_void_p, C.c_int]),

@@ -289,6 +289,15 @@ class DGP_Base(Parameterized):
         Fmean, Fvar = self._build_predict(Xnew, full_cov=False, S=num_samples)
         return self.likelihood.predict_density_logmeanexp(Fmean, Fvar, np.asarray(Ynew, dtype=np.float64))
 
+    def sample_functions(self, num_functions=1, num_features=1024, seed=0):
+        """num_functions consistent draws of the model's functions (pathwise.PathwiseFunctions): fs(Xs) is (S, N, D_out), fs.all_layers(Xs)
+        every layer's, the same S functions at any inputs in any number of calls; a snapshot, which later training does not change.
+        num_features: the frequencies of each layer's random Fourier basis (fs.basis_error(l) says whether they are enough).  No
+        reference counterpart.  NotImplementedError for anything but SVGP_Layers under DGP / DGP_Quad without input propagation;
+        CholeskyError where a layer's Ku is not positive definite."""
+        from .pathwise import PathwiseFunctions
+        return PathwiseFunctions(self, num_functions=num_functions, num_features=num_features, seed=seed)
+
     # ------------------------------------------------------------------ held-out scoring: one front end for every model
     # Each of evaluate, predict_quantiles, calibration and classification_report has ONE body (_evaluate, ...), shared with
     # model_zoo.DGP_SGPMC: refusals before any device is touched, uploads, the accumulator and `rows`, the batch loop, one

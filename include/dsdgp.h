@@ -60,7 +60,7 @@ int dsdgp_ctx_destroy(dsdgp_ctx* ctx);
 int dsdgp_sync(dsdgp_ctx* ctx);
 /* HIP-event timing of the most recent launch of a named kernel class on the ctx stream (bench.py roofline):
  * enable, run, then read the accumulated milliseconds and launch count. name in
- * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig","psi","psi2","gram_grad"}. */
+ * {"layer_fwd","layer_bwd","wgrad","gram","potrf","gemm","evaluate","calibration","pca_gram","pca_eig","psi","psi2","gram_grad","pathwise"}. */
 int dsdgp_prof_enable(dsdgp_ctx* ctx, int on);
 int dsdgp_prof_read(dsdgp_ctx* ctx, const char* name, double* total_ms, int64_t* launches, int reset);
 /* Kernel launches this library has enqueued in this process so far (all contexts; memsets / copies not counted): the difference
@@ -741,6 +741,46 @@ int dsdgp_stack_hop_bwd(dsdgp_ctx* ctx, const double* dF, int64_t R, int32_t p, 
  *   theta += v;  then  v = (1 - alpha) v + eta g + sqrt(2 alpha eta) xi,   g the gradient of the log density, xi N(0, 1) draws.
  * alpha = 0: plain momentum, xi is not read (and may be NULL).  DSDGP_ERR_BAD_ARG, nothing launched: alpha outside [0, 1], eta <= 0. */
 int dsdgp_sghmc_step(dsdgp_ctx* ctx, int64_t count, double* theta, double* v, const double* g, const double* xi, double alpha, double eta);
+
+/* dsdgp_pathwise_eval / dsdgp_pathwise_weights: pathwise (Matheron) draws of a sparse GP posterior FUNCTION (Wilson, Borovitskiy, Terenin,
+ * Mostowsky and Deisenroth, ICML 2020).  NO reference counterpart: the reference draws rows independently (layers.py:76-119) or jointly
+ * through an n x n factor (utils.py:43-51); a draw here is one function, evaluated at any inputs in any number of calls (csrc/pathwise.hip).
+ * Layer with k = s2 kappa(. / l) (RBF or Matern52, scalar or ARD l, with or without a White part), inducing inputs Z (M x D):
+ *   Omega (D x L): the frequencies of a random Fourier basis of kappa, ALREADY divided by l row by row;  origin c (D);
+ *   theta_j(x) = sum_d (x_d - c_d) Omega_dj                   (the difference is formed first: data at an offset loses nothing)
+ *   f0(x)_o    = sqrt(s2 / L) sum_j [Wc_jo cos theta_j(x) + Ws_jo sin theta_j(x)],   Wc, Ws ~ N(0, 1):  Var f0(x) = s2 exactly
+ *   Ku = K(Z, Z) + (White variance + jitter) I,  Lu = chol(Ku),   u_o = q_mu_o + q_sqrt_o eps_o  (white != 0: Lu (q_mu_o + q_sqrt_o eps_o)),
+ *   v = Ku^-1 (u - f0(Z))   (M x DO per draw),      f(x)_o = f0(x)_o + sum_m k(x, z_m) v_mo + add(x)_o.
+ * The White part enters Ku only: f is a draw of the function WITHOUT its white component.
+ * dsdgp_pathwise_eval — one launch for S draws of n rows each; every pointer a device pointer, row-major float64:
+ *   X: rows of stride D = kern.input_dim; draw s reads X + s x_stride, x_stride = 0 (the same n rows for every draw) or n D;
+ *   Omega (D x L, row stride L); origin (D); Wc, Ws (S x L x DO); Z (M x D); V (S x M x DO); M = 0: the prior part f0 alone, Z and V unread;
+ *   add (or NULL): entry (s, i, o) at add[s add_stride + i ld_add + o], ld_add >= DO — the mean function: Identity is X itself (ld_add = D,
+ *     add_stride = x_stride), Linear X A + b formed by the caller (dsdgp_gemm), Zero NULL;
+ *   out: entry (s, i, o) at out[(s n + i) ld_out + o], ld_out >= DO: rows r = s n + i as dsdgp_model_propagate.  Nothing else is written.
+ *   kern.lengthscales scale the distances of k(x, z); kern.variance is s2.
+ * theta tiles run on the fp64 MFMA pipe (k over D, any D >= 1), sine and cosine per element, the contraction with [Wc; Ws] and the
+ * K(x, Z) V term tile by tile from LDS-staged chunks; no n x L or n x M array reaches memory.  |theta| < 4096 takes a two-constant
+ * reduction by pi / 2; at and above it the device library's routine: correct for every finite argument.  A NaN or infinite input row
+ * gives NaN in that row's outputs only.  No atomics; the summation order of an entry follows from (L, M, D, DO) alone: the same call gives
+ * the same bits, and a call on any sub-range of the rows of any one draw gives the bits those rows have in the full call.
+ * Limits: L <= 65536, M <= 2048, S <= 65535, n S < 2^31, DO >= 1 (chunks of 16) — DSDGP_ERR_UNSUPPORTED beyond them and for any other
+ * kernel kind; DSDGP_ERR_BAD_ARG for a NULL input, n, S, L, DO < 1, ld_out or ld_add < DO, any other x_stride; nothing is launched then.
+ * dsdgp_pathwise_weights — v for S draws: eps (S x M x DO) standard normal draws, q_mu (M x DO), q_sqrt (DO x M x M, lower triangle read) or
+ *   NULL: u = q_mu (Lu q_mu with white), eps is not read then.  V (S x M x DO) is OVERWRITTEN.  Composed from dsdgp_gram (symmetric form, Z
+ *   moved to its first row), dsdgp_potrf, the evaluation kernel at X = Z, M = 0, dsdgp_gemm (white) and dsdgp_trsm; those use the context's
+ *   scratch, so the intermediates live in `scratch` (device, 256-byte aligned, at least dsdgp_pathwise_scratch_bytes(M, D, DO, S) bytes;
+ *   csrc/pathwise_plan.hpp).  info (host, may be NULL): the Cholesky status, as dsdgp_potrf; a Ku that is not positive definite returns
+ *   DSDGP_ERR_NOT_SPD and writes nothing to V.  M in 1 .. 2048; DSDGP_ERR_UNSUPPORTED for more than 8 GB of scratch; DSDGP_ERR_BAD_ARG for a
+ *   NULL input or a scratch block that is too small.  Asynchronous up to the read of the Cholesky status. */
+int dsdgp_pathwise_eval(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* X, int64_t n, int64_t x_stride, int32_t S,
+                        const double* Omega, const double* origin, int32_t L, const double* Wc, const double* Ws, const double* Z, int32_t M,
+                        const double* V, int32_t DO, const double* add, int64_t ld_add, int64_t add_stride, double* out, int64_t ld_out);
+int dsdgp_pathwise_scratch_bytes(int32_t M, int32_t D, int32_t DO, int32_t S, int64_t* bytes);
+int dsdgp_pathwise_weights(dsdgp_ctx* ctx, const dsdgp_kernel* kern, const double* Z, int32_t M, const double* Omega, const double* origin,
+                           int32_t L, const double* Wc, const double* Ws, int32_t S, const double* q_mu, const double* q_sqrt,
+                           const double* eps, int32_t DO, int32_t white, double jitter, void* scratch, int64_t scratch_bytes, double* V,
+                           int* info);
 
 /* out = in + value (Gaussian.predict_mean_and_var adds the noise variance, dgp.py:116-119). */
 int dsdgp_add_scalar(dsdgp_ctx* ctx, const double* in, double value, int64_t count, double* out);
